@@ -24,6 +24,8 @@ launch, reported only when profiles/traffic_latest.json was collected with the l
 core's own output) after the timed region and fails the run beyond 1e-6. `cpu_baseline` times the reference's own compiled
 core (oracle/_ref, kind "reference") -- or this repo's C restatement (kind "port") where that binary is
 absent -- on the host cores, on a bounded sample of the same workload.
+`--dump-outputs DIR` writes what the last timed step computed (rank 0's shard: solution and statistics per instance, float64,
+at most 64 MB -- a seeded sample of instances beyond that) as DIR/<name>.npy, for comparing two builds output for output.
 """
 from __future__ import annotations
 
@@ -69,6 +71,8 @@ def parse_args():
     ap.add_argument("--cpu-worker-ticks", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--worker-count", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--no-round5-legs", action="store_true", help="skip the setup and batched_tick legs")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (rank 0's shard) as DIR/<name>.npy, float64")
     return ap.parse_args()
 
 
@@ -362,6 +366,41 @@ def cpu_baseline(iters: int, horizon: int, seconds: float, round5: bool = True) 
             "note": note, "cpu_model": cpu_model}
 
 
+DUMP_MAX_BYTES = 64_000_000  # --dump-outputs: at most this much in all
+DUMP_SAMPLE_SEED = 0         # ... and which instances, when the whole shard does not fit (a fixed sample)
+
+
+def dump_outputs(solver, np, out_dir: str, count: int) -> dict:
+    """--dump-outputs: what a caller of the timed path receives from its last step -- per instance the solution (states, controls)
+    and the statistics (iterations, status, the four residuals) -- as float64 .npy files. The whole shard where it fits in
+    DUMP_MAX_BYTES, else a fixed, seeded sample of instances (sorted); instance_index.npy says which either way."""
+    nx, nu, N = solver.nx, solver.nu, solver.N
+    per_instance = 8 * (nx * N + nu * (N - 1) + 1 + 1 + 4 + 1)
+    keep = min(count, DUMP_MAX_BYTES // per_instance)
+    idx = np.arange(count) if keep == count else np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(count, keep, replace=False))
+    out = {"states": np.zeros((nx, N, keep)), "controls": np.zeros((nu, N - 1, keep)), "iterations": np.zeros(keep),
+           "status": np.zeros(keep), "residuals": np.zeros((4, keep)), "instance_index": idx.astype(np.float64)}
+    chunk = 4096
+    for first in range(0, count, chunk):  # (chunk by chunk: a sample of a large shard never holds the whole shard on the host)
+        n = min(chunk, count - first)
+        lo, hi = np.searchsorted(idx, first), np.searchsorted(idx, first + n)
+        if lo == hi:
+            continue
+        pick = idx[lo:hi] - first
+        sol = solver.get_solution_batch(first, n)
+        st = solver.get_stats_batch(first, n)
+        out["states"][:, :, lo:hi] = sol["states"][:, :, pick]
+        out["controls"][:, :, lo:hi] = sol["controls"][:, :, pick]
+        out["iterations"][lo:hi] = st["iter"][pick]
+        out["status"][lo:hi] = st["status"][pick]
+        out["residuals"][:, lo:hi] = st["residuals"][:, pick]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    return {"dir": out_dir, "instances": int(keep), "of": int(count), "sampled": bool(keep < count),
+            "bytes": int(sum(a.nbytes for a in out.values())), "files": sorted(name + ".npy" for name in out)}
+
+
 def main() -> int:
     args = parse_args()
     if args.cpu_worker:
@@ -531,6 +570,8 @@ def main() -> int:
                          "first_controls_prefix": g[7:7 + k * prob.nu].reshape(k, prob.nu).tolist(),
                          "first_controls_sha256": bytes(g[7 + 4 * prob.nu:7 + 4 * prob.nu + 32].astype(np.uint8)).hex()})
     elapsed, kernel_ms_avg, elapsed_asked, kernel_ms_asked_avg = (float(v) for v in t.cpu())
+    # the last timed step's results are still on the device: written out before anything else uses this handle
+    dumped = dump_outputs(solver, np, args.dump_outputs, count) if args.dump_outputs and rank == 0 else None
 
     # after the timed region: the one collective of the batched mode (summary statistics)
     summary = pkg.batch.allreduce_summary(pkg.batch.local_summary(st["iter"], st["status"], st["residuals"]), device=cdev)
@@ -615,6 +656,7 @@ def main() -> int:
                                                      "from HBM (on-chip), so this roof does not bind"},
                          "hbm_measured_frac_of_peak": (traffic / kernel_s / 1e9 / PEAK_HBM_GBS) if traffic else None},
             "parity_check": parity,
+            "dump_outputs": dumped,
             "process_group": ({"backend": dist.get_backend(), "world_size": dist.get_world_size(),
                                "ranks_per_device": ("%d ranks share device(s) %s (rehearsal of the N > 1 path on fewer GPUs than ranks: the rates are "
                                                     "not a scaling measurement)" % (world, sorted({p_["device"] for p_ in per_rank}))

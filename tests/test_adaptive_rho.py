@@ -2,28 +2,59 @@
 
 Pinning chain: the reference's own core, compiled with zero-initialised automatic variables (oracle/Makefile target
 ref_zeroinit -- the plain build reads RhoAdapter::matrices_initialized uninitialised and crashes), pins the plain-C
-restatement (CPU tests); the restatement and the reference then check the device kernel (GPU tests)."""
+restatement (CPU tests); the restatement and the reference then check the device kernel (GPU tests). What the reference
+answers is recorded in tests/golden/adaptive_rho_ref.npz (tests/golden/gen_ref_records.py), so that no test needs oracle/_ref."""
 from __future__ import annotations
-
-import os
 
 import numpy as np
 import pytest
-from conftest import rel_err
+from conftest import golden, rel_err
 
 import pyoracle as O
 
 TOL = 1e-9
+# the cases whose reference answers tests/golden/gen_ref_records.py records
+SOLVE_CASES = [(10, dict(max_iter=30, abs_pri_tol=1e-9, abs_dua_tol=1e-9)),
+               (20, dict(max_iter=200, abs_pri_tol=1e-3, abs_dua_tol=1e-3)),
+               (50, dict(max_iter=60, abs_pri_tol=0.0, abs_dua_tol=0.0, check_termination=4))]
+CLIP_N = 12
+CLIP_SETTINGS = dict(max_iter=40, abs_pri_tol=0.0, abs_dua_tol=0.0)
+CLIP_CASES = [(1.0, 100.0, False), (4.5, 5.5, True), (6.0, 50.0, True)]
 
 
-def _need_zeroinit():
-    if not os.path.exists(O.REF_ZEROINIT_LIB):
-        pytest.fail("oracle/_ref/libtinympc_ref_zeroinit.so missing: run `python __graft_entry__.py` where /root/reference exists")
+def x0_of_solve(prob, solve):
+    return prob.x0 * (1.0 - 0.3 * solve)
 
 
-def _ref_and_port(prob, settings, adaptive=(1.0, 100.0, True)):
-    ref = O.OracleRef(prob, zeroinit=True).load_problem(prob, settings)
-    ref.set_adaptive_rho(True, *adaptive)
+class RefRecord:
+    """The reference core (zero-initialised build, adaptive rho on) for one recorded case, answering the calls the tests make of
+    pyoracle.OracleRef: the sensitivity tables, then per solve -- x0 as recorded -- return code, statistics, solution, cache."""
+
+    def __init__(self, case: str):
+        g = golden("adaptive_rho_ref")
+        self.g = {k[len(case) + 2:]: v for k, v in g.items() if k.startswith(case + "__")}
+        assert self.g, case
+        self.k = -1
+
+    def set_x0(self, x0):
+        self.k += 1
+        np.testing.assert_array_equal(np.asarray(x0, dtype=np.float64), self.g["x0_%d" % self.k])
+
+    def solve(self) -> int:
+        return int(self.g["rc_%d" % self.k])
+
+    def stats(self) -> dict:
+        return {"iter": int(self.g["iter_%d" % self.k]), "status": int(self.g["status_%d" % self.k]), "rho": float(self.g["rho_%d" % self.k])}
+
+    def solution(self):
+        return self.g["x_%d" % self.k], self.g["u_%d" % self.k]
+
+    def get(self, name: str) -> np.ndarray:
+        return self.g["%s_%d" % (name, self.k)] if name in ("Kinf", "Pinf") else self.g[name]
+
+
+def _ref_and_port(prob, settings, case, adaptive=(1.0, 100.0, True)):
+    ref = RefRecord(case)
     port = O.OraclePort(prob).load_problem(prob, settings)
     port.set_adaptive_rho(True, *adaptive)
     port.set_sensitivity(ref.get("dKinf_drho"), ref.get("dPinf_drho"))  # the snapshot's hard-coded quadrotor tables
@@ -33,15 +64,12 @@ def _ref_and_port(prob, settings, adaptive=(1.0, 100.0, True)):
 # ---------------------------------------------------------------------------------------------
 # CPU: restatement vs the reference
 # ---------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("N,settings", [(10, dict(max_iter=30, abs_pri_tol=1e-9, abs_dua_tol=1e-9)),
-                                        (20, dict(max_iter=200, abs_pri_tol=1e-3, abs_dua_tol=1e-3)),
-                                        (50, dict(max_iter=60, abs_pri_tol=0.0, abs_dua_tol=0.0, check_termination=4))])
+@pytest.mark.parametrize("N,settings", SOLVE_CASES)
 def test_oracle_adaptive_rho_matches_the_reference_core(pkg, N, settings):
-    _need_zeroinit()
     prob = pkg.problems.quadrotor(N)
-    ref, port = _ref_and_port(prob, settings)
+    ref, port = _ref_and_port(prob, settings, "N%d" % N)
     for solve in range(3):  # rho and the Taylor-updated cache persist from one solve to the next
-        x0 = prob.x0 * (1.0 - 0.3 * solve)
+        x0 = x0_of_solve(prob, solve)
         ref.set_x0(x0)
         port.set_x0(x0)
         assert ref.solve() == port.solve()
@@ -55,11 +83,10 @@ def test_oracle_adaptive_rho_matches_the_reference_core(pkg, N, settings):
 
 
 def test_oracle_adaptive_rho_without_clipping_and_bounds_of_the_clip(pkg):
-    _need_zeroinit()
-    prob = pkg.problems.quadrotor(12)
-    settings = dict(max_iter=40, abs_pri_tol=0.0, abs_dua_tol=0.0)
-    for adaptive in ((1.0, 100.0, False), (4.5, 5.5, True), (6.0, 50.0, True)):
-        ref, port = _ref_and_port(prob, settings, adaptive)
+    prob = pkg.problems.quadrotor(CLIP_N)
+    settings = CLIP_SETTINGS
+    for i, adaptive in enumerate(CLIP_CASES):
+        ref, port = _ref_and_port(prob, settings, "clip%d" % i, adaptive)
         ref.set_x0(prob.x0)
         port.set_x0(prob.x0)
         ref.solve()
@@ -96,18 +123,14 @@ def _solver(pkg, prob, batch=1, **settings):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("N,settings", [(10, dict(max_iter=30, abs_pri_tol=1e-9, abs_dua_tol=1e-9)),
-                                        (20, dict(max_iter=200, abs_pri_tol=1e-3, abs_dua_tol=1e-3)),
-                                        (50, dict(max_iter=60, abs_pri_tol=0.0, abs_dua_tol=0.0, check_termination=4))])
+@pytest.mark.parametrize("N,settings", SOLVE_CASES)
 def test_device_adaptive_rho_matches_the_reference_core(pkg, N, settings):
-    _need_zeroinit()
     prob = pkg.problems.quadrotor(N)
-    ref = O.OracleRef(prob, zeroinit=True).load_problem(prob, settings)
-    ref.set_adaptive_rho(True, 1.0, 100.0, True)
+    ref = RefRecord("N%d" % N)
     s = _solver(pkg, prob, adaptive_rho=True, adaptive_rho_min=1.0, adaptive_rho_max=100.0, **settings)
     s.set_sensitivity_matrices(ref.get("dKinf_drho"), ref.get("dPinf_drho"), ref.get("dC1_drho"), ref.get("dC2_drho"))
     for solve in range(3):
-        x0 = prob.x0 * (1.0 - 0.3 * solve)
+        x0 = x0_of_solve(prob, solve)
         ref.set_x0(x0)
         s.set_x0(x0)
         ref.solve()

@@ -1,11 +1,13 @@
 """Code generation (reference codegen.cpp:56-431, TinyMPC.m:159-182, 415-434).
 
-CPU tests: the host-only emitter against the REFERENCE's own emitter (oracle/_ref, line by line), and -- where the
-reference tree exists -- the generated project compiled with the reference's solver sources and run.
+CPU tests: the host-only emitter against the REFERENCE's own emitter (line by line: a digest of every line it generated, recorded
+from oracle/_ref in tests/golden/codegen_ref.npz by tests/golden/gen_ref_records.py), and -- where the reference tree exists --
+the generated project compiled with the reference's solver sources and run.
 GPU tests: `solver.codegen()` writes what the device computed."""
 from __future__ import annotations
 
 import ctypes as C
+import hashlib
 import os
 import re
 import shutil
@@ -14,7 +16,7 @@ import sys
 
 import numpy as np
 import pytest
-from conftest import rel_err
+from conftest import golden, rel_err
 
 import pyoracle as O
 
@@ -71,10 +73,21 @@ def _emit(pkg, out, prob, cache, settings, sens=None, it=0, solved=0):
     assert rc == 0, lib.tinympc_last_error()
 
 
-def _body(path):
+def body_lines(path):
     """File content without the leading comment block (it carries a time stamp)."""
     text = open(path).read()
     return text[text.index("*/") + 2:].lstrip("\n").splitlines()
+
+
+_body = body_lines
+
+
+def _line_digests(lines):
+    return [hashlib.sha256(line.encode()).digest() for line in lines]
+
+
+def codegen_problem(P, which):
+    return P.cartpole(20, True) if which == "cartpole" else P.quadrotor(12)
 
 
 def _members(path):
@@ -94,23 +107,16 @@ SETTINGS = dict(abs_pri_tol=1e-4, abs_dua_tol=2e-4, max_iter=77, check_terminati
 
 @pytest.mark.parametrize("which", ["cartpole", "quadrotor"])
 def test_emitter_matches_the_reference_emitter_line_by_line(pkg, tmp_path, which):
-    if not O.ref_available():
-        pytest.fail("oracle/_ref/libtinympc_ref.so missing: run `python __graft_entry__.py` where /root/reference exists")
-    prob = pkg.problems.cartpole(20, True) if which == "cartpole" else pkg.problems.quadrotor(12)
-    ref = O.OracleRef(prob).load_problem(prob, SETTINGS)
-    if not hasattr(ref.L, "ref_codegen"):
-        pytest.fail("oracle/_ref was built before ref_codegen existed: rebuild it (`make -C oracle ref`)")
-    ref.set_x0(prob.x0)
-    ref.solve()  # so that TinySolution.iter / .solved are not trivially zero
-    st = ref.stats()
-    assert ref.codegen(tmp_path / "ref") == 0
-    cache = {n: ref.get(n) for n in ("Kinf", "Pinf", "Quu_inv", "AmBKt")}
-    _emit(pkg, tmp_path / "mine", prob, cache, SETTINGS, it=st["iter"], solved=st["solved"])
+    # the reference emitter was driven after one solve (so that TinySolution.iter / .solved are not trivially zero) with this cache
+    g = {k[len(which) + 2:]: v for k, v in golden("codegen_ref").items() if k.startswith(which + "__")}
+    prob = codegen_problem(pkg.problems, which)
+    cache = {n: g[n] for n in ("Kinf", "Pinf", "Quu_inv", "AmBKt")}
+    _emit(pkg, tmp_path / "mine", prob, cache, SETTINGS, it=int(g["iter"]), solved=int(g["solved"]))
 
-    assert _body(tmp_path / "mine/tinympc/tiny_data.hpp") == _body(tmp_path / "ref/tinympc/tiny_data.hpp")
-    mine, theirs = _body(tmp_path / "mine/src/tiny_data.cpp"), _body(tmp_path / "ref/src/tiny_data.cpp")
+    assert _line_digests(_body(tmp_path / "mine/tinympc/tiny_data.hpp")) == [bytes(d) for d in g["hpp_line_sha256"]]
+    mine, theirs = _body(tmp_path / "mine/src/tiny_data.cpp"), [bytes(d) for d in g["cpp_line_sha256"]]
     assert len(mine) == len(theirs)
-    differing = [i for i, (a, b) in enumerate(zip(mine, theirs)) if a != b]
+    differing = [i for i, (a, b) in enumerate(zip(_line_digests(mine), theirs)) if a != b]
     # the only line allowed to differ is C1: the reference prints nx*nx values out of an nu x nu matrix there
     # (codegen.cpp:229-231), this build prints the nu x nu matrix
     assert all(mine[i].endswith("// C1") for i in differing), [mine[i][:80] for i in differing]

@@ -257,6 +257,7 @@ int dalloc(tinympc_solver *s, T **p, size_t count) {
 int acquire_arenas(tinympc_solver *s, size_t dev_bytes, size_t pin_bytes, bool want_mailbox);  // -> s->arena_dev / arena_pin (from the device's pool when one fits)
 int acquire_stream_kit(tinympc_solver *s);  // stream + event pair from the device's pool (created when the pool is empty)
 int bind_device(tinympc_solver *s);   // every verb that touches the device passes through here first (ends an open session)
+bool queues_may_be_shared(int device);  // the library's streams on `device` may share hardware queues (more than GPU_MAX_HW_QUEUES)
 bool rows_constant(const double *m, int rows, int cols);
 int upload(tinympc_solver *s, double *dst, const double *src, size_t count);
 int download(tinympc_solver *s, void *dst, const void *src, size_t bytes);

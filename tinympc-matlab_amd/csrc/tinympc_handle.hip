@@ -53,10 +53,25 @@ constexpr size_t kArenasKept = 8;
 // HIP streams are multiplexed onto a few hardware queues -- four per process unless GPU_MAX_HW_QUEUES says otherwise --, and a hardware queue
 // runs its packets in order: with more streams alive than queues, a launch can land BEHIND another handle's resident session kernel and
 // wait until that kernel's idle time-out (2 s), tick after tick (tools/thread_sessions.py, round 5: three host threads with a session and
-// a launched twin each stalled in five runs of six; none of twelve with 16 queues). The runtime reads the variable when it initialises:
-// set a default when this library is loaded (never over the user's own value). A process that initialised HIP before loading the library
-// has to set it itself -- INTEGRATION.md.
-__attribute__((constructor(101))) static void tinympc_default_environment() { (void)setenv("GPU_MAX_HW_QUEUES", "16", 0); }
+// a launched twin each stalled in five runs of six). The library leaves the runtime's settings to the process that loads it -- INTEGRATION.md.
+// Instead, where its streams on a device may share queues, a resident kernel leaves after a SHORT idle time (tinympc_session.hip:
+// launch_session_kernel), so that whatever queued behind it waits at most that long; its session restarts it at the next step.
+namespace {
+std::atomic<int> g_streams_alive[64];  // [device]: streams this library has created and not destroyed (pooled ones included)
+int hw_queues_per_process() {
+    static const int q = [] {
+        const char *e = getenv("GPU_MAX_HW_QUEUES");  // (read only)
+        const int v = e ? atoi(e) : 0;
+        return v > 0 ? v : 4;  // (the runtime's default)
+    }();
+    return q;
+}
+}  // namespace
+
+bool queues_may_be_shared(int device) {
+    if (device < 0 || device >= 64) return true;
+    return g_streams_alive[device].load(std::memory_order_relaxed) + 1 > hw_queues_per_process();  // (+1: the runtime's null stream)
+}
 
 // Can the host store into device memory (the whole of it mapped through the PCIe BAR)? Asked once per device.
 static bool device_is_large_bar(int device) {
@@ -141,6 +156,7 @@ int acquire_stream_kit(tinympc_solver *s) {
         }
     }
     HIP_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
+    if (s->device >= 0 && s->device < 64) g_streams_alive[s->device].fetch_add(1, std::memory_order_relaxed);
     HIP_TRY(hipEventCreate(&s->ev0));
     HIP_TRY(hipEventCreate(&s->ev1));
     return TINYMPC_OK;
@@ -158,7 +174,10 @@ static void release_stream_kit(tinympc_solver *s) {
     }
     if (s->ev0) (void)hipEventDestroy(s->ev0);
     if (s->ev1) (void)hipEventDestroy(s->ev1);
-    if (s->stream) (void)hipStreamDestroy(s->stream);
+    if (s->stream) {
+        (void)hipStreamDestroy(s->stream);
+        if (s->device >= 0 && s->device < 64) g_streams_alive[s->device].fetch_sub(1, std::memory_order_relaxed);
+    }
     s->stream = nullptr; s->ev0 = s->ev1 = nullptr;
 }
 

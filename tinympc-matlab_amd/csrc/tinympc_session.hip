@@ -25,7 +25,10 @@ using namespace tinympc::host;
 namespace {
 
 // ---- closed-loop session ------------------------------------------------------------------------------------
-constexpr double kSessionIdleSeconds = 2.0;  // the resident kernel leaves on its own after this long without a command
+constexpr double kSessionIdleSeconds = 2.0;  // the resident kernel leaves on its own after this long without a command ...
+// ... or after this long where the library's streams may share hardware queues (queues_may_be_shared, tinympc_handle.hip): a queue runs its
+// packets in order, and a launch of another handle behind an idle resident kernel waits until that kernel leaves
+constexpr double kSessionIdleSharedSeconds = 5e-3;
 
 void write_command(tinympc_solver *s, int flags, const double *x0) {
     // payload: 0 flags | x0 (nx) | new last column of x_ref (flag 4) | new last column of u_ref (flag 8); line l = [7 payload |
@@ -89,7 +92,7 @@ int launch_session_kernel(tinympc_solver *s) {
     if (s->h_sol) s->h_sol[s->X() + s->U() + 6] = -1.0;  // (the completion stamp of solution + statistics, likewise)
     std::atomic_thread_fence(std::memory_order_seq_cst);
     p.session_expect = (double)(s->session_seq + 1);
-    p.session_idle = (unsigned long long)(kSessionIdleSeconds * 1e8);
+    p.session_idle = (unsigned long long)((queues_may_be_shared(s->device) ? kSessionIdleSharedSeconds : kSessionIdleSeconds) * 1e8);
     if (s->session_on_f) {
         p.const_tables = 0;  // (the session kernel always carries per-knot tables: references may change from tick to tick)
         p.ctab = s->dctab_f; p.ftab = s->dftab; p.chunk_len = s->f_chunk_len; p.chunk_count = s->f_chunks; p.chunk_levels = 4;
