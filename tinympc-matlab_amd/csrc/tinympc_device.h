@@ -384,9 +384,12 @@ size_t precompute_large_scratch_doubles(int nx, int nu);
 hipError_t launch_precompute_large(const PrecomputeParams &p, hipStream_t stream);
 hipError_t launch_build_operators(const OperatorParams &p, hipStream_t stream);
 hipError_t launch_build_tables(const TableParams &p, hipStream_t stream);
-// Layout A: one wavefront per workgroup, all ADMM state in LDS (lowest latency, 2 waves per CU).
-// Chooses the <W,KT> instantiation; returns hipErrorInvalidValue when none fits.
-hipError_t launch_solve(const SolveParams &p, int W, int KT, size_t lds_bytes, hipStream_t stream);
+// Layout A: one wavefront per workgroup, all ADMM state in LDS (lowest latency, 2 waves per CU). One kernel body, three
+// variants: the box path (k_admm_solve), plus the cone / linear slack families (k_admm_solve_fam: extra duals and the extra
+// linear-cost term in HBM), plus adaptive rho (k_admm_solve_adapt: per-instance rho, Taylor-updated operators; needs
+// p.adapt and p.rho_inst). Chooses the <W,KT> instantiation; returns hipErrorInvalidValue when none fits.
+enum class SolveExt { Box, Families, Adaptive };
+hipError_t launch_solve_a(const SolveParams &p, SolveExt ext, int W, int KT, size_t lds_bytes, hipStream_t stream);
 // Layout B: four wavefronts per workgroup sharing the tables in LDS, G and D in LDS, V as an
 // L2-resident ping-pong pair in HBM (4 waves per CU). Only W = 16, N >= 8.
 hipError_t launch_solve_b(const SolveParams &p, int W, int KT, size_t lds_bytes, hipStream_t stream);
@@ -411,8 +414,6 @@ bool solve_dx_supported(int nx, int nu, int N, bool const_tables);
 hipError_t launch_solve_dx(const SolveParams &p, hipStream_t stream);
 int solve_dx_workgroups(int nu, int N, int groups);
 size_t solve_dx_lds_bytes(int nu, int N);
-// Layout A plus the cone / linear slack families (extra duals and the extra linear-cost term in HBM).
-hipError_t launch_solve_fam(const SolveParams &p, int W, int KT, size_t lds_bytes, hipStream_t stream);
 // Layout C: one instance per 256-thread workgroup, the horizon swept in 16 concurrent chunks (latency kernel
 // for small batches). W = 16, N <= 129.
 hipError_t launch_solve_c(const SolveParams &p, int W, int KT, size_t lds_bytes, hipStream_t stream);
@@ -425,8 +426,7 @@ size_t solve_c_lds_bytes(int nx, int Lc);
 size_t solve_c_lds_bytes_refs(int nx, int nu, int N, int Lc);
 size_t chunk_table_doubles(int nx, int Lc);
 int chunk_ks(int nx);
-// Layout A plus adaptive rho (per-instance rho, Taylor-updated operators).
-hipError_t launch_solve_adapt(const SolveParams &p, int W, int KT, size_t lds_bytes, hipStream_t stream);
+// The tables of adaptive rho (adapt_doubles()) from the current cache, the sensitivities and Xref (tinympc_kernels.hip).
 hipError_t launch_build_adapt(const AdaptTableParams &p, hipStream_t stream);
 // Raise a kernel's dynamic-LDS limit to `bytes` unless a previous launch on this device already did
 // (the attribute is sticky per function and device; re-setting it costs ~5 us per launch, which matters

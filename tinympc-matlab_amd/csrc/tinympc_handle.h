@@ -185,7 +185,7 @@ struct tinympc_solver {
     bool state_in_global = false;             // horizon too long for LDS: layout-A kernels work on dscratch
     double *dscratch_state = nullptr;
     bool fam_dirty = true;
-    size_t lds_bytes_a = 0;       // layout-A LDS plan (the families kernel always uses layout A)
+    size_t lds_bytes_a = 0;       // layout-A LDS plan (layout B, where it runs, replaces lds_bytes; the families and adaptive rho always use layout A)
     bool tables_in_lds_a = false;
 
     bool use_layout_d() const {

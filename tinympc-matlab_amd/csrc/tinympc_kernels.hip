@@ -3,6 +3,7 @@
 //   k_precompute        P1  tiny_precompute_and_set_cache         (reference tiny_api.cpp:124-190)
 //   k_build_operators       fuses the cache into the two 1-step sweep operators used by the solve
 //   k_build_tables          per-knot clamp bounds / linear-cost reference terms
+//   k_build_adapt           adaptive rho: the sensitivity rows of the sweep operators and [A'; B']
 //
 // The solve kernel itself (M1: F1, S1, D1, L1, R1, C1, B1) is in tinympc_solve.hip.
 #include "tinympc_device.h"
@@ -571,6 +572,41 @@ __global__ void __launch_bounds__(256) k_build_tables(const TableParams p) {
 hipError_t launch_build_tables(const TableParams &p, hipStream_t stream) {
     const int blocks = ((p.N + 2) * p.W + 255) / 256;
     hipLaunchKernelGGL(k_build_tables, dim3(blocks > 0 ? blocks : 1), dim3(256), 0, stream, p);
+    return hipGetLastError();
+}
+
+// Adaptive rho (k_admm_solve_adapt, layout D's ADAPT variant): the tables of adapt_doubles(), rebuilt per launch from the current
+// cache, the sensitivities and Xref -- mt | pinf | dpinf | dmf | dmb [W][KT], then dpnref[W].
+__global__ void __launch_bounds__(256) k_build_adapt(const AdaptTableParams p) {
+    const int nx = p.nx, nu = p.nu, W = p.W, KT = p.KT, nxu = nx + nu;
+    const size_t M = (size_t)W * KT;
+    double *mt = p.out, *pinf = mt + M, *dpinf = pinf + M, *dmf = dpinf + M, *dmb = dmf + M, *dpn = dmb + M;
+    for (int idx = threadIdx.x; idx < W * KT; idx += 256) {
+        const int r = idx / KT, k = idx % KT;
+        double vt = 0.0, vp = 0.0, vdp = 0.0, vf = 0.0, vb = 0.0;
+        if (r < nx && k < nx) {
+            vt = p.A[k + (size_t)r * nx];  // A'
+            vp = p.Pinf[r + (size_t)k * nx];
+            vdp = p.dP[r + (size_t)k * nx];
+            for (int j = 0; j < nu; ++j) vf -= p.B[r + (size_t)j * nx] * p.dK[j + (size_t)k * nu];  // d(A - B K)
+        } else if (r < nx && k < nxu) {
+            vb = -p.dK[(k - nx) + (size_t)r * nu];  // d(-K')
+        } else if (r < nxu && k < nx) {
+            vt = p.B[k + (size_t)(r - nx) * nx];  // B'
+            vf = -p.dK[(r - nx) + (size_t)k * nu];  // d(-K)
+        }
+        mt[idx] = vt; pinf[idx] = vp; dpinf[idx] = vdp; dmf[idx] = vf; dmb[idx] = vb;
+    }
+    for (int r = threadIdx.x; r < W; r += 256) {
+        double v = 0.0;  // d/drho of -(Xref_{N-1}' Pinf)'  (admm.cpp:81)
+        if (r < nx)
+            for (int i = 0; i < nx; ++i) v -= p.Xref[i + (size_t)(p.N - 1) * nx] * p.dP[i + (size_t)r * nx];
+        dpn[r] = v;
+    }
+}
+
+hipError_t launch_build_adapt(const AdaptTableParams &p, hipStream_t stream) {
+    hipLaunchKernelGGL(k_build_adapt, dim3(1), dim3(256), 0, stream, p);
     return hipGetLastError();
 }
 

@@ -215,14 +215,6 @@ LaunchPlan current_plan(const tinympc_solver *s) {
             pl.workgroups = s->batch;
             pl.lds_bytes = s->lds_bytes_c;
             break;
-        case KernelId::FAM_A:
-        case KernelId::ADAPT_A:  // kernels of their own on layout A's plan
-            pl.layout = 'A';
-            pl.host_exchange = true;
-            pl.workgroups = s->groups;
-            pl.lds_bytes = s->lds_bytes_a;
-            pl.tables_in_lds = s->tables_in_lds_a;
-            break;
         case KernelId::B:
             pl.layout = 'B';
             pl.host_exchange = true;
@@ -231,11 +223,13 @@ LaunchPlan current_plan(const tinympc_solver *s) {
             pl.tables_in_lds = s->tables_in_lds;
             break;
         case KernelId::A:
+        case KernelId::FAM_A:
+        case KernelId::ADAPT_A:  // (layout A's own plan: A itself runs only where layout B does not)
             pl.layout = 'A';
             pl.host_exchange = true;
             pl.workgroups = s->groups;
-            pl.lds_bytes = s->lds_bytes;
-            pl.tables_in_lds = s->tables_in_lds;
+            pl.lds_bytes = s->lds_bytes_a;
+            pl.tables_in_lds = s->tables_in_lds_a;
             break;
     }
     return pl;
@@ -388,18 +382,16 @@ int launch(tinympc_solver *s, bool timed) {
             arm_completion_flag(s, p);
             HIP_TRY(launch_solve_c(p, s->W, s->KT, s->lds_bytes_c, s->stream));
             break;
-        case KernelId::FAM_A:  // shares the persistent state (G, canonical V, D) with every other kernel
-            HIP_TRY(launch_solve_fam(p, s->W, s->KT, s->lds_bytes_a, s->stream));
-            break;
-        case KernelId::ADAPT_A:
-            HIP_TRY(launch_solve_adapt(p, s->W, s->KT, s->lds_bytes_a, s->stream));
-            break;
         case KernelId::B:
             HIP_TRY(launch_solve_b(p, s->W, s->KT, s->lds_bytes, s->stream));
             break;
         case KernelId::A:
-            HIP_TRY(launch_solve(p, s->W, s->KT, s->lds_bytes, s->stream));
+        case KernelId::FAM_A:  // (the families and adaptive rho share the persistent state -- G, canonical V, D -- with every other kernel)
+        case KernelId::ADAPT_A: {
+            const SolveExt ext = pl.kernel == KernelId::FAM_A ? SolveExt::Families : pl.kernel == KernelId::ADAPT_A ? SolveExt::Adaptive : SolveExt::Box;
+            HIP_TRY(launch_solve_a(p, ext, s->W, s->KT, s->lds_bytes_a, s->stream));
             break;
+        }
     }
     if (timed) HIP_TRY(hipEventRecord(s->ev1, s->stream));
     return TINYMPC_OK;
