@@ -203,7 +203,7 @@ int tinympc_get_cache(tinympc_solver *s, double *Kinf, double *Pinf, double *Quu
 int tinympc_get_residuals(tinympc_solver *s, double residuals[4]);
 
 /* Batched setup: `batch` independent MPC instances sharing (A,B,fdyn,Q,R,rho,bounds,refs,settings),
- * each with its own x0 and its own persistent ADMM state. device < 0 keeps the current HIP device. */
+ * each with its own x0 and its own persistent ADMM state (references per instance: tinympc_set_x_ref_batch below). device < 0 keeps the current HIP device. */
 int tinympc_setup_batch(tinympc_solver **out, const double *A, const double *B, const double *fdyn,
                         const double *Q, const double *R, double rho, int nx, int nu, int N,
                         int batch, int device, int verbose);
@@ -215,6 +215,24 @@ int tinympc_set_x0_batch(tinympc_solver *s, const double *x0s, int first, int co
  * non-blocking stream, which is ordered against no other stream); the copy itself has completed when the
  * call returns, so the caller may free or overwrite d_x0s right away. */
 int tinympc_set_x0_batch_device(tinympc_solver *s, const double *d_x0s, int first, int count);
+
+/* Per-instance references for instances [first, first+count) of a batched handle.
+ * Xrefs: nx x cols x count, column-major, instance b's block at b*nx*cols; cols = N (a trajectory per instance)
+ *        or cols = 1 (one goal per instance, held over the whole horizon). Urefs likewise with nu and N-1.
+ * Instance b then solves exactly what it would solve alone after set_x_ref(Xref_b) / set_u_ref(Uref_b). The first call
+ * for a half (x or u) turns per-instance mode on for that half; instances outside the range keep the handle's shared
+ * reference of that moment. A later tinympc_set_x_ref / tinympc_set_u_ref returns that half to shared mode for every
+ * instance. reset_workspace, update_settings, set_bound_constraints, the solve verbs and mpc_step_batch keep them.
+ * Goals run on layout D where the handle runs layout D (compiled in or run-time specialised), everything else on layout A;
+ * with the cone / linear families, adaptive rho or nx+nu > 64 a solve returns TINYMPC_ERR_UNSUPPORTED (never a solve with
+ * the shared reference). The _device forms refuse memory that is not device memory of the handle's GPU.
+ * Single-instance handles: the same as tinympc_set_x_ref / tinympc_set_u_ref. The input has been copied when the call
+ * returns. */
+int tinympc_set_x_ref_batch(tinympc_solver *s, const double *Xrefs, int rows, int cols, int first, int count);
+int tinympc_set_u_ref_batch(tinympc_solver *s, const double *Urefs, int rows, int cols, int first, int count);
+/* Same, from device memory on the handle's GPU; same contract as tinympc_set_x0_batch_device. */
+int tinympc_set_x_ref_batch_device(tinympc_solver *s, const double *d_Xrefs, int rows, int cols, int first, int count);
+int tinympc_set_u_ref_batch_device(tinympc_solver *s, const double *d_Urefs, int rows, int cols, int first, int count);
 
 /* Zero the persistent ADMM state (cold start) of every instance and put every instance's rho back to
  * the setup value; x0 is kept. */

@@ -76,6 +76,10 @@ SIGNATURES = {
                                       C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "tinympc_set_x0_batch": (C.c_int, [Handle, c_double_p, C.c_int, C.c_int]),
     "tinympc_set_x0_batch_device": (C.c_int, [Handle, C.c_void_p, C.c_int, C.c_int]),
+    "tinympc_set_x_ref_batch": (C.c_int, [Handle, c_double_p, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "tinympc_set_u_ref_batch": (C.c_int, [Handle, c_double_p, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "tinympc_set_x_ref_batch_device": (C.c_int, [Handle, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "tinympc_set_u_ref_batch_device": (C.c_int, [Handle, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
     "tinympc_reset_workspace": (C.c_int, [Handle]),
     "tinympc_get_rho_batch": (C.c_int, [Handle, c_double_p, C.c_int, C.c_int]),
     "tinympc_get_solution_batch": (C.c_int, [Handle, c_double_p, c_double_p, C.c_int, C.c_int]),

@@ -286,6 +286,7 @@ int tinympc_set_x_ref(tinympc_solver *s, const double *Xref, int rows, int cols,
     // the workspace shape under the solver; rejected here.
     if (rows != s->nx || cols != s->N)
         return fail(TINYMPC_ERR_INVALID_INPUT, "State reference trajectory (x_ref) is %d x %d. Expected %d x %d.", rows, cols, s->nx, s->N);
+    s->iref_x = false;  // (per-instance references: this half is shared again, for every instance)
     s->xref_const = rows_constant(Xref, s->nx, s->N);
     if (s->host_path()) {  // no device call: the next launch reads the pinned copy and rebuilds the table rows itself
         if (s->host_sol_state == 1 && (rc = tinympc_synchronize(s))) return rc;  // a launch in flight may be reading it
@@ -315,6 +316,7 @@ int tinympc_set_u_ref(tinympc_solver *s, const double *Uref, int rows, int cols,
     if (!Uref) return fail(TINYMPC_ERR_INVALID_INPUT, "set_u_ref: Uref is NULL");
     if (rows != s->nu || cols != s->N - 1)
         return fail(TINYMPC_ERR_INVALID_INPUT, "Control/input reference trajectory (u_ref) is %d x %d. Expected %d x %d.", rows, cols, s->nu, s->N - 1);
+    s->iref_u = false;
     s->uref_const = rows_constant(Uref, s->nu, s->N - 1);
     if (s->host_path()) {
         if (s->host_sol_state == 1 && (rc = tinympc_synchronize(s))) return rc;
@@ -454,6 +456,7 @@ int tinympc_solve_timed(tinympc_solver *s, float *kernel_ms) {
     if (rc) return rc;
     if ((rc = bind_device(s))) return rc;
     if ((rc = refresh_derived(s))) return rc;  // keep table rebuilds out of the timed region
+    if ((rc = refresh_inst_tables(s))) return rc;
     if ((rc = launch(s, true))) return rc;
     HIP_TRY(hipEventSynchronize(s->ev1));
     if (s->host_sol_state == 1) s->host_sol_state = 2;
@@ -470,6 +473,7 @@ int tinympc_solve_queued(tinympc_solver *s) {
     if (s->session_active || s->host_path()) return fail(TINYMPC_ERR_UNSUPPORTED, "solve_queued: batched handles outside a session only");
     if (s->ring_count >= 4096) return fail(TINYMPC_ERR_INVALID_INPUT, "solve_queued: 4096 launches queued, collect their times first");
     if ((rc = refresh_derived(s))) return rc;  // keep table rebuilds out of the timed region
+    if ((rc = refresh_inst_tables(s))) return rc;
     while ((int)s->ring_ev.size() < 2 * (s->ring_count + 1)) {
         hipEvent_t e = nullptr;
         HIP_TRY(hipEventCreate(&e));
@@ -992,6 +996,107 @@ int tinympc_set_x0_batch_device(tinympc_solver *s, const double *d_x0s, int firs
     // d_x0s on another stream must have completed before the call; see the header.)
     HIP_TRY(hipStreamSynchronize(s->stream));
     return TINYMPC_OK;
+}
+
+namespace {
+
+// tinympc_set_x_ref_batch / _u_ref_batch (+ _device): one half (x or u) of instances [first, first+count). The half enters per-instance
+// mode at its first call (every instance then holds the shared reference of that moment); the table rows of the instances named here
+// are rebuilt at the next launch (refresh_inst_tables). Single-instance handles: the shared verb.
+int set_ref_batch(tinympc_solver *s, bool is_x, const double *src, bool on_device, int rows, int cols, int first, int count) {
+    const char *verb = is_x ? "set_x_ref_batch" : "set_u_ref_batch";
+    int rc = check_handle(s);
+    if (rc) return rc;
+    if (!src) return fail(TINYMPC_ERR_INVALID_INPUT, "%s: references are NULL", verb);
+    const int R = is_x ? s->nx : s->nu, C = is_x ? s->N : s->N - 1;
+    if (rows != R || (cols != C && cols != 1))
+        return fail(TINYMPC_ERR_INVALID_INPUT, "%s: the references are %d x %d per instance. Expected %d x %d or %d x 1.", verb, rows, cols, R, C, R);
+    if (first < 0 || count < 0 || first + count > s->batch)
+        return fail(TINYMPC_ERR_INVALID_INPUT, "%s: instance range [%d, %d) outside batch of %d", verb, first, first + count, s->batch);
+    const size_t per = (size_t)R * C, in_per = (size_t)R * cols;
+    if (on_device && count > 0) {  // device memory of the handle's own GPU (a host pointer or another GPU's memory is refused here)
+        hipPointerAttribute_t attr{};
+        const hipError_t e = hipPointerGetAttributes(&attr, src);
+        (void)hipGetLastError();
+        if (e != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != s->device)
+            return fail(TINYMPC_ERR_INVALID_INPUT, "%s_device: the references are not device memory of the handle's GPU %d", verb, s->device);
+    }
+    if (s->batch == 1) {  // the shared verb, pinned-host path included
+        if (count == 0) return TINYMPC_OK;
+        std::vector<double> h(per);
+        if (on_device) {
+            if ((rc = bind_device(s))) return rc;
+            if ((rc = download(s, h.data(), src, sizeof(double) * in_per))) return rc;
+            src = h.data();
+        }
+        for (size_t e = 0; e < per; ++e) h[e] = src[cols == 1 ? e % R : e];
+        return is_x ? tinympc_set_x_ref(s, h.data(), R, C, 0) : tinympc_set_u_ref(s, h.data(), R, C, 0);
+    }
+    if ((rc = bind_device(s))) return rc;
+    bool &mode = is_x ? s->iref_x : s->iref_u;
+    if (s->layout_m) {  // (no kernel carries them: the next launch refuses until the shared verb clears the mode)
+        mode = true;
+        return TINYMPC_OK;
+    }
+    double *&dst = is_x ? s->dXi : s->dUi;
+    if (!dst && (rc = dalloc(s, &dst, per * s->batch))) return rc;
+    if (!s->dIlr) {
+        if ((rc = dalloc(s, &s->dIlr, inst_lr_doubles(s->groups, s->N)))) return rc;
+        if ((rc = dalloc(s, &s->dIpn, (size_t)s->groups * 64))) return rc;
+        if ((rc = dalloc(s, &s->dIgoal, (size_t)s->groups * 64))) return rc;
+        HIP_TRY(hipMemsetAsync(s->dIlr, 0, sizeof(double) * inst_lr_doubles(s->groups, s->N), s->stream));
+        HIP_TRY(hipMemsetAsync(s->dIpn, 0, sizeof(double) * s->groups * 64, s->stream));
+        HIP_TRY(hipMemsetAsync(s->dIgoal, 0, sizeof(double) * s->groups * 64, s->stream));
+    }
+    if (!mode) {  // every instance starts from the shared reference of this moment
+        InstRefStoreParams b{};
+        b.src = is_x ? s->dXref : s->dUref; b.src_stride = 0; b.rows = R; b.src_cols = C; b.cols = C;
+        b.first = 0; b.count = s->batch; b.dst = dst;
+        HIP_TRY(launch_store_inst_refs(b, s->stream));
+        mode = true;
+        (is_x ? s->iref_x_goal : s->iref_u_goal) = is_x ? s->xref_const : s->uref_const;
+        s->iref_mark(0, s->batch);
+    }
+    if (count > 0) {
+        if (cols == C) {  // trajectories: the caller's layout is the handle's
+            bool goal = !on_device;  // (device input: not looked at)
+            for (int b = 0; goal && b < count; ++b) goal = rows_constant(src + (size_t)b * per, R, C);
+            if (!goal) (is_x ? s->iref_x_goal : s->iref_u_goal) = false;
+            HIP_TRY(hipMemcpyAsync(dst + (size_t)first * per, src, sizeof(double) * per * count,
+                                   on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s->stream));
+        } else {  // goals: held over the horizon on the device
+            const double *dsrc = src;
+            if (!on_device) {
+                const size_t cap = (size_t)s->batch * (s->nx > s->nu ? s->nx : s->nu);
+                if (!s->dIstage && (rc = dalloc(s, &s->dIstage, cap))) return rc;
+                HIP_TRY(hipMemcpyAsync(s->dIstage, src, sizeof(double) * in_per * count, hipMemcpyHostToDevice, s->stream));
+                dsrc = s->dIstage;
+            }
+            InstRefStoreParams b{};
+            b.src = dsrc; b.src_stride = in_per; b.rows = R; b.src_cols = 1; b.cols = C;
+            b.first = first; b.count = count; b.dst = dst;
+            HIP_TRY(launch_store_inst_refs(b, s->stream));
+        }
+        s->iref_mark(first, first + count);
+    }
+    // the caller keeps ownership of its buffer: the copies have completed when the call returns (the tinympc_set_x0_batch_device rule)
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return TINYMPC_OK;
+}
+
+}  // namespace
+
+int tinympc_set_x_ref_batch(tinympc_solver *s, const double *Xrefs, int rows, int cols, int first, int count) {
+    return set_ref_batch(s, true, Xrefs, false, rows, cols, first, count);
+}
+int tinympc_set_u_ref_batch(tinympc_solver *s, const double *Urefs, int rows, int cols, int first, int count) {
+    return set_ref_batch(s, false, Urefs, false, rows, cols, first, count);
+}
+int tinympc_set_x_ref_batch_device(tinympc_solver *s, const double *d_Xrefs, int rows, int cols, int first, int count) {
+    return set_ref_batch(s, true, d_Xrefs, true, rows, cols, first, count);
+}
+int tinympc_set_u_ref_batch_device(tinympc_solver *s, const double *d_Urefs, int rows, int cols, int first, int count) {
+    return set_ref_batch(s, false, d_Urefs, true, rows, cols, first, count);
 }
 
 int tinympc_reset_workspace(tinympc_solver *s) {

@@ -178,7 +178,8 @@ struct SolveParams {
     double rho_min, rho_max;
     int rho_clip;
     // Layout C (k_admm_solve_c): horizon cut into chunk_count chunks of chunk_len steps, see chunk_plan()
-    const double *ctab;   // PhiS_l | PsiS_l (l < chunk_levels), each [16][chunk_ks(nx)]: powers S*2^l of the sweeps' state blocks
+    // (iref_lr: per-instance references, layout A only -- see below; shares the slot so that the kernels' argument layout stays as it was)
+    union { const double *ctab; const double *iref_lr; };  // ctab: PhiS_l | PsiS_l (l < chunk_levels), each [16][chunk_ks(nx)]: powers S*2^l of the sweeps' state blocks
     int chunk_len, chunk_count, chunk_levels;
     int families;         // layout C / the specialised layout D: run the cone / linear families too (the other layouts use k_admm_solve_fam)
     int adaptive;         // the specialised layout D: adaptive rho (the other layouts use k_admm_solve_adapt)
@@ -227,7 +228,33 @@ struct SolveParams {
     // so that a wavefront does not idle three rows while its slowest instance iterates. NULL: one instance per row and launch.
     int *refill_next;
     // Layout F (round 4): T_s = Phi^(S-1-s) (-B) as [s][k][16 rows] | aff[16], for the chunk length of the launch (k_build_f_input_tables)
-    const double *ftab;
+    // Per-instance references (tinympc_set_x_ref_batch / _u_ref_batch; layout A's InstRefs variant, which reads neither ctab nor ftab): the
+    // reference-dependent table rows of every instance, in the solve kernel's lane order (k_build_inst_tables) -- iref_lr
+    // [groups][N+2][64] (row k+1 = knot k, the same padding rows as the shared tables), iref_pn [groups][64] = [instance][W].
+    // Layout D's goal form (k_admm_solve_d_goal): iref_lr is knot 0's linref, [instance][16]. NULL otherwise.
+    union { const double *ftab; const double *iref_pn; };
+};
+
+// Per-instance references of a batched handle (k_store_inst_refs, k_build_inst_tables; tinympc_kernels.hip). The references of instance b
+// are column-major nx x N / nu x (N-1) blocks at b*nx*N / b*nu*(N-1); the table rows are laid out as SolveParams::iref_lr / iref_pn say.
+// (iref_lr points INST_LR_PAD rows into its block: layout A prefetches the rows of the backward sweep that many knots ahead)
+constexpr int INST_LR_PAD = 4;
+__host__ __device__ inline size_t inst_lr_doubles(int groups, int N) { return ((size_t)groups * table_rows(N) + INST_LR_PAD) * 64; }
+struct InstRefStoreParams {
+    const double *src;  // count blocks of rows x src_cols, src_stride doubles apart (0: one block for every instance)
+    size_t src_stride;
+    int rows, src_cols, cols;  // src_cols == 1: one column held over all `cols` columns of the destination
+    int first, count;
+    double *dst;        // [batch][cols][rows]
+};
+struct InstTableParams {
+    int nx, nu, N, W, KT;
+    int first, count;                 // instances whose rows are rebuilt
+    const double *Xi, *Ui;            // per-instance references, or NULL: that half is the shared one
+    const double *Xref, *Uref, *Pinf;  // shared references, Pinf for pNref
+    const double *ops;                // for dg[]
+    double *lr, *pn;                  // rows (layout A), pNref [instance][W]
+    double *lrg;                      // knot 0's linref [instance][W] (layout D's goal form: the references are constant over the horizon)
 };
 
 struct ChunkTableParams {
@@ -343,7 +370,7 @@ bool solve_jit_enabled();  // TINYMPC_JIT is not 0
 bool solve_e_supported(int nx, int nu, int N, bool const_tables, bool families, const FamilyStructure &fs);  // plans AND compiles
 hipError_t launch_solve_e(const SolveParams &p, const FamilyStructure &fs, hipStream_t stream);
 void solve_e_describe(int nx, int nu, int N, bool const_tables, bool families, const FamilyStructure &fs, char *buf, size_t len);
-void solve_jit_describe(int W, int nx, int nu, int N, bool const_tables, bool families, bool adaptive, char *buf, size_t len);
+void solve_jit_describe(int W, int nx, int nu, int N, bool const_tables, bool families, bool adaptive, char *buf, size_t len, bool goal = false);
 // Layout F (tinympc_solve_f.hip, run-time specialised only): the latency kernel with compile-time shape and structure
 bool solve_f_plan(int nx, int nu, int N, bool const_tables, bool families, const FamilyStructure &fs, int *chunk_len, int *chunks, int *wpg, size_t *lds_bytes);
 bool solve_f_supported(int nx, int nu, int N, bool const_tables, bool families, const FamilyStructure &fs);  // plans AND compiles
@@ -384,11 +411,15 @@ size_t precompute_large_scratch_doubles(int nx, int nu);
 hipError_t launch_precompute_large(const PrecomputeParams &p, hipStream_t stream);
 hipError_t launch_build_operators(const OperatorParams &p, hipStream_t stream);
 hipError_t launch_build_tables(const TableParams &p, hipStream_t stream);
+hipError_t launch_store_inst_refs(const InstRefStoreParams &p, hipStream_t stream);
+hipError_t launch_build_inst_tables(const InstTableParams &p, hipStream_t stream);
 // Layout A: one wavefront per workgroup, all ADMM state in LDS (lowest latency, 2 waves per CU). One kernel body, three
 // variants: the box path (k_admm_solve), plus the cone / linear slack families (k_admm_solve_fam: extra duals and the extra
 // linear-cost term in HBM), plus adaptive rho (k_admm_solve_adapt: per-instance rho, Taylor-updated operators; needs
 // p.adapt and p.rho_inst). Chooses the <W,KT> instantiation; returns hipErrorInvalidValue when none fits.
-enum class SolveExt { Box, Families, Adaptive };
+// A fourth variant, InstRefs, is the box path with every instance's linref rows and pNref read from SolveParams::iref_lr / iref_pn
+// (k_admm_solve_iref, tinympc_solve.hip).
+enum class SolveExt { Box, Families, Adaptive, InstRefs };
 hipError_t launch_solve_a(const SolveParams &p, SolveExt ext, int W, int KT, size_t lds_bytes, hipStream_t stream);
 // Layout B: four wavefronts per workgroup sharing the tables in LDS, G and D in LDS, V as an
 // L2-resident ping-pong pair in HBM (4 waves per CU). Only W = 16, N >= 8.
@@ -455,12 +486,13 @@ int solve_m_fam_fast_rows();  // up to this many linear rows per side the descri
 hipError_t launch_solve_m(const SolveParams &p, hipStream_t stream);
 // Run-time specialisation of layout D (tinympc_jit.hip): any (nx, nu, N) that fits the register / LDS plan, compiled with
 // hiprtc from the very sources of the compiled-in instantiations on first use and cached (memory + disk).
-bool solve_jit_supported(int W, int nx, int nu, int N, bool const_tables, bool families = false, bool adaptive = false);
+// goal: the per-instance goal form (-DTINY_JIT_IGOAL=1; constant tables, box path)
+bool solve_jit_supported(int W, int nx, int nu, int N, bool const_tables, bool families = false, bool adaptive = false, bool goal = false);
 hipError_t launch_solve_jit(const SolveParams &p, int W, hipStream_t stream);
 bool solve_jit_refill_supported(int W, int nx, int nu, int N, bool const_tables);   // (compiles the slot-refill variant on first use)
 int solve_jit_resident_wavefronts(int W, int nx, int nu, int N, bool const_tables);  // wavefronts of the shape's plan the device holds at once
-int solve_jit_workgroups(int W, int nx, int nu, int N, bool const_tables, int groups, bool families = false, bool adaptive = false);
-size_t solve_jit_lds_bytes(int W, int nx, int nu, int N, bool const_tables, bool families = false, bool adaptive = false);  // per workgroup, from the plan  // 8 wavefronts per workgroup, 4 on the long-horizon plan
+int solve_jit_workgroups(int W, int nx, int nu, int N, bool const_tables, int groups, bool families = false, bool adaptive = false, bool goal = false);
+size_t solve_jit_lds_bytes(int W, int nx, int nu, int N, bool const_tables, bool families = false, bool adaptive = false, bool goal = false);  // per workgroup, from the plan  // 8 wavefronts per workgroup, 4 on the long-horizon plan
 #endif  // !__HIPCC_RTC__
 
 // Doubles of working state per group in layout A (G and V with N+2 rows, D with 64 dummy slots).

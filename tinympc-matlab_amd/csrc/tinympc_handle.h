@@ -185,6 +185,30 @@ struct tinympc_solver {
     bool state_in_global = false;             // horizon too long for LDS: layout-A kernels work on dscratch
     double *dscratch_state = nullptr;
     bool fam_dirty = true;
+    // Per-instance references (tinympc_set_x_ref_batch / _u_ref_batch; batched handles). Each half (x, u) is in per-instance mode from its
+    // first per-instance verb until the next tinympc_set_x_ref / _set_u_ref; instances the verbs did not name hold the shared reference
+    // of the moment the mode began. dXi / dUi: every instance's reference, column-major nx x N / nu x (N-1) blocks; dIlr / dIpn: the
+    // table rows the solve kernel reads (SolveParams::iref_lr / iref_pn), rebuilt at the next launch for the instances in
+    // [iref_dirty_lo, iref_dirty_hi) -- all of them when the shared tables were rebuilt (new references, bounds or cache). One interval:
+    // two small updates far apart rebuild the instances between them too (a rebuild is one element-wise kernel over the interval).
+    // Goal form (every instance's references constant over the horizon, bounds too): layout D's constant-table kernel carries it
+    // (k_admm_solve_d_goal, compiled-in 16-lane shapes) with knot 0's linref per instance in dIgoal; everything else runs on layout A.
+    bool iref_x = false, iref_u = false;
+    // ... every per-instance reference of that half is constant over the horizon. Sticky until the half returns to shared mode: a
+    // trajectory that is later replaced by goals keeps the handle on layout A (nothing looks at the whole batch's data again)
+    bool iref_x_goal = false, iref_u_goal = false;
+    int d_goal = -1;  // the run-time specialised goal kernel (16 lanes beyond the compiled-in shapes, 32 / 64 lanes): -1 not asked yet, 0 no, 1 yes
+    bool iref() const { return iref_x || iref_u; }
+    bool iref_goal() const {
+        return (iref_x ? iref_x_goal : xref_const) && (iref_u ? iref_u_goal : uref_const) && xmin_const && xmax_const && umin_const && umax_const;
+    }
+    double *dXi = nullptr, *dUi = nullptr, *dIlr = nullptr, *dIpn = nullptr, *dIgoal = nullptr, *dIstage = nullptr;
+    const double *iref_rows() const { return dIlr + (size_t)tinympc::INST_LR_PAD * 64; }  // SolveParams::iref_lr on layout A
+    int iref_dirty_lo = 0, iref_dirty_hi = 0;
+    void iref_mark(int lo, int hi) {
+        if (iref_dirty_lo >= iref_dirty_hi) { iref_dirty_lo = lo; iref_dirty_hi = hi; }
+        else { iref_dirty_lo = lo < iref_dirty_lo ? lo : iref_dirty_lo; iref_dirty_hi = hi > iref_dirty_hi ? hi : iref_dirty_hi; }
+    }
     size_t lds_bytes_a = 0;       // layout-A LDS plan (layout B, where it runs, replaces lds_bytes; the families and adaptive rho always use layout A)
     bool tables_in_lds_a = false;
 
@@ -268,6 +292,7 @@ int flush_host_refs(tinympc_solver *s);
 int refresh_derived(tinympc_solver *s);
 FamilyStructure family_structure(const tinympc_solver *s, double *mu = nullptr);
 int refresh_families(tinympc_solver *s);
+int refresh_inst_tables(tinympc_solver *s);  // the per-instance table rows of the instances whose references changed
 void destroy(tinympc_solver *s);
 
 // ---- tinympc_plan.hip: the kernel of a launch, decided in ONE place
@@ -276,6 +301,7 @@ struct LaunchPlan {
     KernelId kernel = KernelId::A;
     char layout = 'A';                       // what tinympc_get_layout reports
     bool families = false, adaptive = false;  // variant bits of the launch
+    bool inst_refs = false;                  // ... per-instance references (layout A's InstRefs variant)
     bool jit = false;                        // a run-time specialisation (tinympc_jit.hip) rather than a compiled-in kernel
     bool host_exchange = false;              // the kernel serves the pinned-host paths (x0 in, solution / completion stamp out)
     int workgroups = 0;

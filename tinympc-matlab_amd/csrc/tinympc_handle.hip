@@ -313,7 +313,21 @@ int refresh_derived(tinympc_solver *s) {
         p.Xref = s->dXref; p.Uref = s->dUref; p.Pinf = s->dPinf; p.ops = s->dops; p.tables = s->dtables;
         HIP_TRY(launch_build_tables(p, s->stream));
         s->tables_dirty = false;
+        if (s->iref()) s->iref_mark(0, s->batch);  // (the per-instance rows use the same shared inputs: dg, Pinf, the shared half)
     }
+    return TINYMPC_OK;
+}
+
+int refresh_inst_tables(tinympc_solver *s) {
+    if (!s->iref() || !s->dIlr || s->iref_dirty_lo >= s->iref_dirty_hi) return TINYMPC_OK;
+    InstTableParams p{};
+    p.nx = s->nx; p.nu = s->nu; p.N = s->N; p.W = s->W; p.KT = s->KT;
+    p.first = s->iref_dirty_lo; p.count = s->iref_dirty_hi - s->iref_dirty_lo;
+    p.Xi = s->iref_x ? s->dXi : nullptr; p.Ui = s->iref_u ? s->dUi : nullptr;
+    p.Xref = s->dXref; p.Uref = s->dUref; p.Pinf = s->dPinf; p.ops = s->dops;
+    p.lr = const_cast<double *>(s->iref_rows()); p.pn = s->dIpn; p.lrg = s->dIgoal;
+    HIP_TRY(launch_build_inst_tables(p, s->stream));
+    s->iref_dirty_lo = s->iref_dirty_hi = 0;
     return TINYMPC_OK;
 }
 

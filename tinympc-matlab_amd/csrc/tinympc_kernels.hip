@@ -575,6 +575,73 @@ hipError_t launch_build_tables(const TableParams &p, hipStream_t stream) {
     return hipGetLastError();
 }
 
+// Per-instance references: instances [first, first+count) of the handle's copy, from host-staged or caller device memory. A source of
+// one column (a goal) is held over every column of the destination; a source stride of 0 gives every instance the same block (the
+// shared reference, when an instance enters per-instance mode).
+__global__ void __launch_bounds__(256) k_store_inst_refs(const InstRefStoreParams p) {
+    const size_t per = (size_t)p.rows * p.cols, total = per * p.count;
+    for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
+        const size_t b = idx / per, e = idx % per;
+        const int k = (int)(e / p.rows), i = (int)(e % p.rows);
+        p.dst[(size_t)(p.first + b) * per + e] = p.src[b * p.src_stride + (size_t)(p.src_cols == 1 ? 0 : k) * p.rows + i];
+    }
+}
+
+hipError_t launch_store_inst_refs(const InstRefStoreParams &p, hipStream_t stream) {
+    const size_t total = (size_t)p.rows * p.cols * p.count;
+    if (total == 0) return hipSuccess;
+    const size_t blocks = (total + 255) / 256;
+    hipLaunchKernelGGL(k_store_inst_refs, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, stream, p);
+    return hipGetLastError();
+}
+
+// The reference-dependent table rows of instances [first, first+count), in the lane order of layout A's solve kernel: lane j*W + r of
+// wavefront g is row r of instance g*(64/W) + j. The expressions and the order of the pNref sum are k_build_tables' (an instance whose
+// references equal the shared ones gets bit-identical values); padding rows and lanes are zero.
+__global__ void __launch_bounds__(256) k_build_inst_tables(const InstTableParams p) {
+    const int nx = p.nx, nu = p.nu, N = p.N, W = p.W, nxu = nx + nu, TR = N + 2;
+    const size_t X = (size_t)nx * N, U = (size_t)nu * (N - 1);
+    const double *dg = p.ops + (size_t)2 * W * p.KT + 2 * W;
+    const size_t per = (size_t)(TR + 1) * W;  // TR linref rows + the pNref row, W lanes each
+    const size_t total = per * p.count;
+    for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
+        const long inst = p.first + (long)(idx / per);
+        const int e = (int)(idx % per), row = e / W, r = e % W;
+        const long grp = inst / (64 / W);
+        const int lane = (int)(inst % (64 / W)) * W + r;
+        const double *Xr = p.Xi ? p.Xi + inst * X : p.Xref;
+        const double *Ur = p.Ui ? p.Ui + inst * U : p.Uref;
+        if (row == TR) {
+            double acc = 0.0;
+            if (r < nx) {
+                for (int k = 0; k < nx; ++k) acc += Xr[k + (size_t)(N - 1) * nx] * p.Pinf[k + (size_t)r * nx];
+                acc = -acc;  // admm.cpp:81
+            }
+            p.pn[(size_t)grp * 64 + lane] = acc;
+        } else {
+            const int kn = row - 1;
+            double ref = 0.0;
+            if (kn < 0 || kn >= N) {
+                // padding row
+            } else if (r < nx) {
+                ref = -(Xr[r + (size_t)kn * nx] * dg[r]);  // admm.cpp:79
+            } else if (r < nxu && kn < N - 1) {
+                ref = -(Ur[(r - nx) + (size_t)kn * nu] * dg[r]);  // admm.cpp:77
+            }
+            p.lr[((size_t)grp * TR + row) * 64 + lane] = ref;
+            if (row == 1) p.lrg[(size_t)grp * 64 + lane] = ref;
+        }
+    }
+}
+
+hipError_t launch_build_inst_tables(const InstTableParams &p, hipStream_t stream) {
+    const size_t total = (size_t)(p.N + 3) * p.W * p.count;
+    if (total == 0) return hipSuccess;
+    const size_t blocks = (total + 255) / 256;
+    hipLaunchKernelGGL(k_build_inst_tables, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, stream, p);
+    return hipGetLastError();
+}
+
 // Adaptive rho (k_admm_solve_adapt, layout D's ADAPT variant): the tables of adapt_doubles(), rebuilt per launch from the current
 // cache, the sensitivities and Xref -- mt | pinf | dpinf | dmf | dmb [W][KT], then dpnref[W].
 __global__ void __launch_bounds__(256) k_build_adapt(const AdaptTableParams p) {

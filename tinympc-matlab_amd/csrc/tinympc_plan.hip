@@ -163,12 +163,20 @@ namespace host {
 //   adaptive rho                       D (run-time specialised, rho per lane)  >  k_admm_solve_adapt on layout A's plan
 //   cone / linear families             D (N <= 22)  >  F (small batches)  >  E (batches)  >  C<FAM> (disjoint cones only)  >  k_admm_solve_fam
 //   box path                           E (only where D has no kernel)  >  D  >  F (on request)  >  C (small batches)  >  B  >  A
+//   per-instance references            A (box path only: with the families, adaptive rho or layout M, launch() refuses)
 LaunchPlan current_plan(const tinympc_solver *s) {
     LaunchPlan pl;
     const bool fam = s->families_active(), adaptive = s->st.adaptive_rho != 0, d = s->use_layout_d();
     pl.families = fam;
     pl.adaptive = adaptive;
-    if (s->layout_m) pl.kernel = KernelId::M;
+    if (s->iref() && !s->layout_m && !fam && !adaptive) {
+        // goals, where the handle runs layout D: its constant-table kernel (compiled in for the 16-lane shapes that are, run-time
+        // specialised otherwise -- wide systems included); trajectories, and goals without such a kernel: layout A
+        const bool goal = s->layout_d && s->iref_goal();
+        pl.kernel = (goal && !s->d_jit && s->W == 16 && solve_d_supported(s->nx, s->nu, s->N, true)) ? KernelId::D_COMPILED
+                    : (goal && s->d_goal == 1) ? KernelId::D_JIT : KernelId::A;
+        pl.inst_refs = true;
+    } else if (s->layout_m) pl.kernel = KernelId::M;
     else if (adaptive) pl.kernel = d ? KernelId::D_JIT : KernelId::ADAPT_A;
     else if (fam)
         pl.kernel = d ? KernelId::D_JIT : s->use_layout_f() ? KernelId::F : s->use_layout_e() ? KernelId::E
@@ -176,7 +184,8 @@ LaunchPlan current_plan(const tinympc_solver *s) {
     else
         pl.kernel = s->use_layout_e() ? KernelId::E : d ? (d_is_jit(s, false, false) ? KernelId::D_JIT : KernelId::D_COMPILED)
                     : s->use_layout_f() ? KernelId::F : s->layout_c ? KernelId::C : s->layout_b ? KernelId::B : KernelId::A;
-    const bool ct = s->tables_const();
+    const bool d_goal = pl.inst_refs && (pl.kernel == KernelId::D_COMPILED || pl.kernel == KernelId::D_JIT);
+    const bool ct = s->tables_const() || d_goal;  // (the goal form: constant tables)
     switch (pl.kernel) {
         case KernelId::M:
             pl.layout = 'M';
@@ -186,12 +195,12 @@ LaunchPlan current_plan(const tinympc_solver *s) {
         case KernelId::D_JIT:
             pl.layout = 'D';
             pl.jit = true;
-            pl.workgroups = solve_jit_workgroups(s->W, s->nx, s->nu, s->N, ct, s->groups, fam, adaptive);
-            pl.lds_bytes = solve_jit_lds_bytes(s->W, s->nx, s->nu, s->N, ct, fam, adaptive);
+            pl.workgroups = solve_jit_workgroups(s->W, s->nx, s->nu, s->N, ct, s->groups, fam, adaptive, pl.inst_refs);
+            pl.lds_bytes = solve_jit_lds_bytes(s->W, s->nx, s->nu, s->N, ct, fam, adaptive, pl.inst_refs);
             break;
         case KernelId::D_COMPILED:
             pl.layout = 'D';
-            pl.host_exchange = s->W == 16;  // (the compiled-in 16-lane shapes have a variant that reads x0 from / writes the first controls to pinned host memory)
+            pl.host_exchange = s->W == 16 && !pl.inst_refs;  // (the compiled-in 16-lane shapes have a variant that reads x0 from / writes the first controls to pinned host memory)
             pl.workgroups = s->W == 64 ? solve_dx_workgroups(s->nu, s->N, s->groups) : s->W == 32 ? solve_dw_workgroups(s->nu, s->N, s->groups)
                                                                                                    : solve_d_workgroups(s->nu, s->N, ct, s->groups);
             pl.lds_bytes = s->W == 64 ? solve_dx_lds_bytes(s->nu, s->N) : s->W == 32 ? solve_dw_lds_bytes(s->nu, s->N) : solve_d_lds_bytes(s->nu, s->N, ct);
@@ -237,6 +246,12 @@ LaunchPlan current_plan(const tinympc_solver *s) {
 
 int resolve_plan(tinympc_solver *s) {
     int rc;
+    if (s->iref()) {  // layout A or D's goal form, or a refusal: only the goal form's specialisation to decide
+        if (s->d_goal < 0 && s->layout_d && s->iref_goal() && !(s->W == 16 && !s->d_jit && solve_d_supported(s->nx, s->nu, s->N, true)) &&
+            !s->families_active() && !s->st.adaptive_rho)
+            s->d_goal = solve_jit_supported(s->W, s->nx, s->nu, s->N, true, false, false, true) ? 1 : 0;
+        return TINYMPC_OK;
+    }
     decide_layout_d_variants(s);
     if ((rc = decide_layout_e(s))) return rc;
     return decide_layout_f(s);
@@ -247,7 +262,7 @@ int resolve_plan(tinympc_solver *s) {
 // with. TINYMPC_REFILL=0 switches it off, =1 takes it for any batch beyond one resident set whatever the tolerances.
 static bool refill_applies(const tinympc_solver *s, const LaunchPlan &pl) {
     const bool jit = pl.kernel == KernelId::D_JIT;
-    if ((pl.kernel != KernelId::D_COMPILED && !jit) || s->W != 16 || pl.adaptive || pl.families || s->zero_copy_tick || s->st.max_iter <= 0 ||
+    if ((pl.kernel != KernelId::D_COMPILED && !jit) || s->W != 16 || pl.adaptive || pl.families || pl.inst_refs || s->zero_copy_tick || s->st.max_iter <= 0 ||
         s->st.check_termination <= 0)
         return false;
     const char *env = getenv("TINYMPC_REFILL");
@@ -274,6 +289,10 @@ int launch(tinympc_solver *s, bool timed) {
     if ((rc = resolve_plan(s))) return rc;
     const LaunchPlan pl = current_plan(s);
     const bool fam = pl.families, adaptive = pl.adaptive;
+    if (s->iref() && !pl.inst_refs)  // never a solve with the shared references in their place
+        return fail(TINYMPC_ERR_UNSUPPORTED, "per-instance references (set_x_ref_batch / set_u_ref_batch) are not supported %s; "
+                    "tinympc_set_x_ref / tinympc_set_u_ref return to shared references",
+                    s->layout_m ? "for systems with nx+nu > 64" : fam ? "with cone / linear constraint families" : "with adaptive rho");
     // k_build_adapt reads the device copy of the references before the solve kernel starts: bring the device copies and the tables up
     // to date the ordinary way (every other kernel of a single-instance handle stages references left in pinned host memory itself)
     if (s->refs_on_host && adaptive) {
@@ -295,6 +314,7 @@ int launch(tinympc_solver *s, bool timed) {
         HIP_TRY(launch_build_adapt(a, s->stream));
     }
     if (fam && (rc = refresh_families(s))) return rc;
+    if (pl.inst_refs && (rc = refresh_inst_tables(s))) return rc;
     SolveParams p{};
     p.nx = s->nx; p.nu = s->nu; p.N = s->N; p.batch = s->batch;
     p.max_iter = s->st.max_iter; p.check_termination = s->st.check_termination;
@@ -319,7 +339,7 @@ int launch(tinympc_solver *s, bool timed) {
     }
 #endif
     p.scratch_stride = state_scratch_doubles(s->nu, s->N, s->W);
-    p.const_tables = s->tables_const() ? 1 : 0;
+    p.const_tables = (s->tables_const() || (pl.inst_refs && pl.kernel != KernelId::A)) ? 1 : 0;
     if (s->zero_copy_tick && pl.host_exchange) {  // set by tinympc_mpc_step_batch for the duration of one launch
         p.x0 = s->h_x0;
         p.x0_mirror = s->dx0;
@@ -342,6 +362,10 @@ int launch(tinympc_solver *s, bool timed) {
         s->refs_on_host = false;  // the kernel brings the tables and the device copies up to date
     }
     p.adapt = s->dadapt; p.rho_inst = s->drho_inst;
+    if (pl.inst_refs) {
+        p.iref_lr = pl.kernel == KernelId::A ? s->iref_rows() : s->dIgoal;
+        p.iref_pn = s->dIpn;
+    }
     p.rho_min = s->st.adaptive_rho_min; p.rho_max = s->st.adaptive_rho_max; p.rho_clip = s->st.adaptive_rho_enable_clipping;
     // a pending cold start: layout D's kernels start from zero registers; every other kernel loads its state from HBM
     // (a solve of zero iterations writes nothing back: the zeros must then be in HBM)
@@ -388,7 +412,8 @@ int launch(tinympc_solver *s, bool timed) {
         case KernelId::A:
         case KernelId::FAM_A:  // (the families and adaptive rho share the persistent state -- G, canonical V, D -- with every other kernel)
         case KernelId::ADAPT_A: {
-            const SolveExt ext = pl.kernel == KernelId::FAM_A ? SolveExt::Families : pl.kernel == KernelId::ADAPT_A ? SolveExt::Adaptive : SolveExt::Box;
+            const SolveExt ext = pl.kernel == KernelId::FAM_A ? SolveExt::Families : pl.kernel == KernelId::ADAPT_A ? SolveExt::Adaptive
+                                 : pl.inst_refs ? SolveExt::InstRefs : SolveExt::Box;
             HIP_TRY(launch_solve_a(p, ext, s->W, s->KT, s->lds_bytes_a, s->stream));
             break;
         }
@@ -437,6 +462,16 @@ int tinympc_get_jit_info(tinympc_solver *s, char *buf, int len) {
     buf[0] = '\0';
     const LaunchPlan pl = current_plan(s);
     const bool ct = s->tables_const();
+    if (pl.inst_refs) {
+        if (pl.kernel == KernelId::D_JIT) {
+            if ((rc = bind_device(s))) return rc;
+            solve_jit_describe(s->W, s->nx, s->nu, s->N, true, false, false, buf, (size_t)len, true);
+            strncat(buf, " per-instance-refs goal", (size_t)len - strlen(buf) - 1);
+        } else {
+            snprintf(buf, (size_t)len, "compiled-in layout=%c per-instance-refs%s", pl.layout, pl.kernel == KernelId::D_COMPILED ? " goal" : "");
+        }
+        return TINYMPC_OK;
+    }
     // a specialisation that was asked for and refused leaves the plan on a generic kernel: say why
     if (!pl.adaptive && !s->f_sig.empty() && !s->f_ok && pl.kernel != KernelId::E && pl.kernel != KernelId::D_JIT && pl.kernel != KernelId::D_COMPILED)
         solve_f_describe(s->nx, s->nu, s->N, ct, pl.families, s->f_fs, buf, (size_t)len);

@@ -1,7 +1,7 @@
 // tinympc_solve.hip -- k_admm_solve: the whole TinyMPC solve() as ONE persistent kernel (gfx950, FP64); layout A's box path.
 // Layout A has two more variants of the same kernel, which share its body (tinympc_solve_a_body.h) and its launcher
 // (tinympc_solve_a.h): k_admm_solve_fam (tinympc_solve_fam.hip, the cone / linear slack families) and k_admm_solve_adapt
-// (tinympc_solve_adapt.hip, adaptive rho).
+// (tinympc_solve_adapt.hip, adaptive rho). A fourth, k_admm_solve_iref (below), carries per-instance references.
 //
 //   M1 solve                 admm.cpp:109-207      F1 forward_pass          admm.cpp:25-35
 //   S1 update_slack          admm.cpp:43-59        D1 update_dual           admm.cpp:65-69
@@ -65,6 +65,18 @@ __global__ void __launch_bounds__(64) k_admm_solve(const SolveParams p) {
 }
 template hipError_t launch_solve_a_e<SolveExt::Box>(const SolveParams &, int, int, size_t, hipStream_t);
 
+// k_admm_solve_iref: the box path for a batched handle whose instances track their OWN references (tinympc_set_x_ref_batch /
+// _u_ref_batch). The only difference is where the reference-dependent operands come from: the backward sweep streams the instance's
+// linref rows -(Xref .* Q) | -(Uref .* R) from SolveParams::iref_lr, one 512-byte line per knot and wavefront (the lanes' order is the
+// kernel's own), and pNref comes from iref_pn. Both are built by k_build_inst_tables with k_build_tables' expressions, so an instance
+// whose references are the shared ones computes exactly what k_admm_solve computes. Bounds stay the shared tables (LDS or L2).
+template <int W, int KT, bool TLDS, bool GMEM>
+__global__ void __launch_bounds__(64) k_admm_solve_iref(const SolveParams p) {
+    constexpr SolveExt E = SolveExt::InstRefs;
+#include "tinympc_solve_a_body.h"
+}
+template hipError_t launch_solve_a_e<SolveExt::InstRefs>(const SolveParams &, int, int, size_t, hipStream_t);
+
 hipError_t launch_solve_a(const SolveParams &p, SolveExt ext, int W, int KT, size_t lds_bytes, hipStream_t stream) {
     switch (ext) {
         case SolveExt::Box: return launch_solve_a_e<SolveExt::Box>(p, W, KT, lds_bytes, stream);
@@ -72,6 +84,9 @@ hipError_t launch_solve_a(const SolveParams &p, SolveExt ext, int W, int KT, siz
         case SolveExt::Adaptive:
             if (!p.adapt || !p.rho_inst) return hipErrorInvalidValue;
             return launch_solve_a_e<SolveExt::Adaptive>(p, W, KT, lds_bytes, stream);
+        case SolveExt::InstRefs:
+            if (!p.iref_lr || !p.iref_pn) return hipErrorInvalidValue;
+            return launch_solve_a_e<SolveExt::InstRefs>(p, W, KT, lds_bytes, stream);
     }
     return hipErrorInvalidValue;
 }

@@ -1,8 +1,12 @@
 // tinympc_solve_a_body.h -- the body of layout A's three solve kernels (k_admm_solve, k_admm_solve_fam, k_admm_solve_adapt;
-// tinympc_solve_a.h). Included INSIDE each kernel, with the kernel's template parameters W, KT, TLDS, GMEM, its parameter
-// p and the variant E (SolveExt) in scope; the families' and adaptive rho's additions are compiled only into their variant.
+// tinympc_solve_a.h; and k_admm_solve_iref). Included INSIDE each kernel, with the kernel's template parameters W, KT, TLDS, GMEM, its
+// parameter p and the variant E (SolveExt) in scope; the families', adaptive rho's and per-instance references' additions are compiled
+// only into their variant.
 // No include guard: it is meant to be included once per kernel.
     constexpr bool FAM = E == SolveExt::Families, ADAPT = E == SolveExt::Adaptive;
+    // per-instance references: this instance's linref rows and pNref from p.iref_lr / iref_pn (HBM / L2, the lane's own 512-byte line
+    // per knot) instead of the shared tables; everything else as on the box path
+    constexpr bool IREF = E == SolveExt::InstRefs;
     extern __shared__ __attribute__((aligned(16))) double smem[];
     refresh_reference_tables(p, W, KT);  // references handed over in pinned host memory (single-instance handles; adaptive rho: never)
     constexpr int IPW = 64 / W;
@@ -140,7 +144,7 @@
 
     const double cf = p.ops[(size_t)2 * W * KT + r];
     const double cb = p.ops[(size_t)2 * W * KT + W + r];
-    double pnref = p.tables[(size_t)3 * TOFF + r];
+    double pnref = IREF ? p.iref_pn[(size_t)grp * 64 + lane] : p.tables[(size_t)3 * TOFF + r];
     double rho = p.rho;
     const double rho0 = p.rho, dgr = ADAPT ? p.ops[2 * M + 2 * W + r] : 0.0;  // Q + rho0 / R + rho0 diagonal of this row (tiny_api.cpp:90-91)
     const double pnref0 = pnref, dpnref = ADAPT ? p.adapt[5 * M + r] : 0.0;
@@ -152,6 +156,14 @@
 #pragma unroll
             for (int k = 0; k < KT; ++k) mt[k] = Mt[k];
         }
+    }
+    // per-instance references: the first four rows the backward sweep reads (knots N-2 .. N-5) stay in registers for the whole solve, so
+    // that no sweep starts waiting for HBM; the ring below keeps the rest of the rows four knots ahead
+    double lr_top[IREF ? 4 : 1];
+    if constexpr (IREF) {
+        const double *t = p.iref_lr + ((size_t)grp * table_rows(N) + (N - 1)) * 64 + lane;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) lr_top[k] = t[-64 * k];
     }
     const double x0v = (inst_ok && is_x) ? p.x0[inst * nx + r] : 0.0;
     if (p.x0_mirror && inst_ok && is_x) p.x0_mirror[inst * nx + r] = x0v;  // zero-copy tick: x0 came from host memory
@@ -433,10 +445,15 @@
             const double *pb = sG + N * 64 + lane;  // knot N-1
             double pcur = pnref_lin - rho_lin * (pb[VOFF] - pb[0]);  // p_{N-1}, admm.cpp:81-82 (state lanes)
             pb -= 64;                                                  // knot N-2
-            const double *pl = t_lr + (N - 1) * W + r;
+            constexpr int LRS = IREF ? 64 : W;  // linref row stride
+            const double *pl = IREF ? p.iref_lr + ((size_t)grp * table_rows(N) + (N - 1)) * 64 + lane : t_lr + (N - 1) * W + r;
             double *pdst = sD + (stb ? (N - 2) * dstride + dIdx : dsize + lane);
             const int ddec = stb ? dstride : 0;
-            BwdOperands A{pb[0], pb[VOFF], pl[0]}, B;
+            BwdOperands A{pb[0], pb[VOFF], IREF ? lr_top[0] : pl[0]}, B;
+            // per-instance rows come from HBM / L2, not LDS: three more rows in flight (rows below row 0 are the previous group's or the
+            // buffer's padding, INST_LR_PAD; never used)
+            double q1 = 0.0, q2 = 0.0, q3 = 0.0;
+            if constexpr (IREF) { q1 = lr_top[1]; q2 = lr_top[2]; q3 = lr_top[3]; }
             const double *px_ = gLX + (N - 1) * 64 + lane;  // families: lx, knot N-1 first
             if constexpr (FAM) {
                 pcur += px_[0];  // p_{N-1} incl. the family terms
@@ -448,8 +465,13 @@
                 if constexpr (FAM) lin += cur.lx;
                 const double w = is_x ? pcur : lin;
                 pb -= 64;
-                pl -= W;
-                nxt.bg = pb[0]; nxt.bv = pb[VOFF]; nxt.blr = pl[0];
+                pl -= LRS;
+                nxt.bg = pb[0]; nxt.bv = pb[VOFF];
+                if constexpr (IREF) {
+                    nxt.blr = q1; q1 = q2; q2 = q3; q3 = pl[-3 * LRS];
+                } else {
+                    nxt.blr = pl[0];
+                }
                 if constexpr (FAM) {
                     px_ -= 64;
                     nxt.lx = px_[0];

@@ -219,9 +219,13 @@ __device__ __forceinline__ bool wave_may_converge_d(unsigned long long bad, unsi
 // arithmetic of an instance is that of the plain kernel (bit-identical results: tests/test_hip_parity.py); what changes is that
 // a wavefront's time is the sum of what its rows worked, not four times its slowest instance.
 template <int NX, int NU, int N, bool CT, int WPG, int VL, bool FAM = false, bool ADAPT = false, bool TWO_PER_SIMD = true, bool HOSTX = false,
-          bool REFILL = false>
+          bool REFILL = false, bool IGOAL = false>
 #else
-template <int NX, int NU, int N, bool CT, int WPG, int VL, bool FAM = false, bool ADAPT = false, bool TWO_PER_SIMD = true, bool HOSTX = false>
+// IGOAL: per-instance references in the goal form (every instance's references constant over the horizon; k_admm_solve_d_goal) --
+// the two reference-dependent constants lr_c and pNref come per lane from SolveParams::iref_lr / iref_pn ([instance][16]) instead of
+// the shared table; nothing else changes.
+template <int NX, int NU, int N, bool CT, int WPG, int VL, bool FAM = false, bool ADAPT = false, bool TWO_PER_SIMD = true, bool HOSTX = false,
+          bool REFILL = false, bool IGOAL = false>
 #endif
 __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double *smem) {
     static_assert(!(FAM && ADAPT), "adaptive rho and the constraint families exclude each other (as in the C ABI)");
@@ -416,7 +420,7 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
 
     const double cf = p.ops[(size_t)2 * W * KT + r];
     const double cb = p.ops[(size_t)2 * W * KT + W + r];
-    const double pnref0 = p.tables[(size_t)3 * TOFF + r];
+    const double pnref0 = IGOAL ? (inst_ok ? p.iref_pn[inst * W + r] : 0.0) : p.tables[(size_t)3 * TOFF + r];
     // (ADAPT: rho, its negative and pNref are lane variables that change every fifth iteration; otherwise they never change and
     // stay in scalar registers)
     const double rho0 = p.rho;
@@ -429,7 +433,8 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
         pnref = fma(rho - rho0, dpnref, pnref0);
     }
     double nrho = -rho;
-    const double lo_c = p.tables[W + r], hi_c = p.tables[(size_t)TOFF + W + r], lr_c = p.tables[(size_t)2 * TOFF + W + r];
+    const double lo_c = p.tables[W + r], hi_c = p.tables[(size_t)TOFF + W + r];
+    const double lr_c = IGOAL ? (inst_ok ? p.iref_lr[inst * W + r] : 0.0) : p.tables[(size_t)2 * TOFF + W + r];
     double rhom = is_x ? nrho : 0.0;
 #if TINY_REFILL
     double x0v = (inst_ok && is_x) ? p.x0[inst * NX + r] : 0.0;
@@ -1008,6 +1013,15 @@ __global__ void __launch_bounds__(64 * WPG) __attribute__((amdgpu_waves_per_eu(2
     k_admm_solve_d_body<NX, NU, N, CT, WPG, VL, false, false, true, HOSTX>(p, smem);
 #endif
 }
+#if !TINY_REFILL
+// Per-instance references, goal form (tinympc_set_x_ref_batch with one goal per instance): the plain constant-table kernel with the
+// instance's lr_c / pNref loaded per lane at kernel start.
+template <int NX, int NU, int N, int WPG, int VL>
+__global__ void __launch_bounds__(64 * WPG) __attribute__((amdgpu_waves_per_eu(2, 2))) k_admm_solve_d_goal(const SolveParams p) {
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    k_admm_solve_d_body<NX, NU, N, true, WPG, VL, false, false, true, false, false, true>(p, smem);
+}
+#endif
 #endif
 
 #ifdef TINY_JIT
@@ -1043,7 +1057,10 @@ tinympc_jit_solve(const tinympc::SolveParams p) {
 #endif
     tinympc::k_admm_solve_d_body<TINY_JIT_NX, TINY_JIT_NU, TINY_JIT_N, CTJ, WPGJ, VLJ, FAMJ, ADJ, TINY_JIT_WPS == 2, false, TINY_JIT_REFILL != 0>(p, smem_jit);
 #else
-    tinympc::k_admm_solve_d_body<TINY_JIT_NX, TINY_JIT_NU, TINY_JIT_N, CTJ, WPGJ, VLJ, FAMJ, ADJ, TINY_JIT_WPS == 2>(p, smem_jit);
+#ifndef TINY_JIT_IGOAL
+#define TINY_JIT_IGOAL 0
+#endif
+    tinympc::k_admm_solve_d_body<TINY_JIT_NX, TINY_JIT_NU, TINY_JIT_N, CTJ, WPGJ, VLJ, FAMJ, ADJ, TINY_JIT_WPS == 2, false, false, TINY_JIT_IGOAL != 0>(p, smem_jit);
 #endif
 }
 namespace tinympc {
@@ -1105,9 +1122,19 @@ static hipError_t launch_d_one(const SolveParams &p, hipStream_t stream) {
         return hipErrorInvalidValue;
     } else {
         constexpr size_t lds = d_lds_bytes(NU, N, CT, WPG, VL);
-        static size_t lds_set[16] = {0}, lds_set_x[16] = {0};
+        static size_t lds_set[16] = {0}, lds_set_x[16] = {0}, lds_set_g[16] = {0};
         const int wgs = (p.groups + WPG - 1) / WPG;
-        if (p.x0_mirror || p.u0_host) {  // (the batched zero-copy tick)
+        if (p.iref_pn) {  // per-instance goals (constant tables only; the plan never combines them with the zero-copy tick)
+            if constexpr (!CT) {
+                return hipErrorInvalidValue;
+            } else {
+                if (p.x0_mirror || p.u0_host) return hipErrorInvalidValue;
+                auto fn = &k_admm_solve_d_goal<NX, NU, N, WPG, VL>;
+                hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void *>(fn), lds, lds_set_g);
+                if (e != hipSuccess) return e;
+                hipLaunchKernelGGL(fn, dim3(wgs), dim3(64 * WPG), lds, stream, p);
+            }
+        } else if (p.x0_mirror || p.u0_host) {  // (the batched zero-copy tick)
             auto fn = &k_admm_solve_d<NX, NU, N, CT, WPG, VL, true>;
             hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void *>(fn), lds, lds_set_x);
             if (e != hipSuccess) return e;

@@ -314,6 +314,35 @@ class TinyMPC:
         assert a.shape[0] == self.nx
         _lib.check(self._L.tinympc_set_x0_batch(self._h, _p(a), first, a.shape[1]))
 
+    def set_x_ref_batch(self, x_refs, first: int = 0):
+        """Per-instance state references for instances first, first+1, ...: a numpy array of shape (nx, count) (one goal per
+        instance, held over the horizon) or (nx, N, count) (a trajectory per instance), or a CUDA torch tensor with the same memory
+        layout, (count, nx) or (count, N, nx) contiguous. set_x_ref() returns every instance to the shared reference."""
+        self._check_setup()
+        self._set_ref_batch(x_refs, first, self.nx, self.N, self._L.tinympc_set_x_ref_batch, self._L.tinympc_set_x_ref_batch_device)
+
+    def set_u_ref_batch(self, u_refs, first: int = 0):
+        """Per-instance input references: (nu, count) or (nu, N-1, count); see set_x_ref_batch."""
+        self._check_setup()
+        self._set_ref_batch(u_refs, first, self.nu, self.N - 1, self._L.tinympc_set_u_ref_batch, self._L.tinympc_set_u_ref_batch_device)
+
+    def _set_ref_batch(self, refs, first, rows, cols_full, f_host, f_device):
+        if hasattr(refs, "data_ptr") and getattr(refs, "is_cuda", False):
+            import torch
+            if refs.dtype != torch.float64 or not refs.is_contiguous() or refs.dim() not in (2, 3) or refs.shape[-1] != rows:
+                raise TinyMPCError(_lib.ERR_INVALID_INPUT, "references on the device must be a contiguous float64 tensor of shape "
+                                   "(count, %d) or (count, %d, %d), got %s %s" % (rows, cols_full, rows, refs.dtype, tuple(refs.shape)))
+            cols = 1 if refs.dim() == 2 else refs.shape[1]  # (the library checks cols, the range and that the memory is on the handle's GPU)
+            torch.cuda.current_stream(refs.device).synchronize()  # (the set_x0_batch contract)
+            _lib.check(f_device(self._h, C.c_void_p(refs.data_ptr()), rows, cols, first, refs.shape[0]))
+            return
+        a = np.asarray(refs, dtype=np.float64)
+        if a.ndim not in (2, 3) or a.shape[0] != rows:
+            raise TinyMPCError(_lib.ERR_INVALID_INPUT, "references must be %d x count or %d x %d x count" % (rows, rows, cols_full))
+        cols = 1 if a.ndim == 2 else a.shape[1]
+        a = _f(a)
+        _lib.check(f_host(self._h, _p(a), rows, cols, first, a.shape[-1]))
+
     def _tick_buffers(self):
         """Persistent buffers of the per-tick verbs (addresses cached: see _lib.fast_tick_functions)."""
         if self._tick is None or self._tick[0].shape != (self.nx, self.batch):
