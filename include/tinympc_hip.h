@@ -202,8 +202,9 @@ int tinympc_get_cache(tinympc_solver *s, double *Kinf, double *Pinf, double *Quu
  * (admm.cpp:93-96). */
 int tinympc_get_residuals(tinympc_solver *s, double residuals[4]);
 
-/* Batched setup: `batch` independent MPC instances sharing (A,B,fdyn,Q,R,rho,bounds,refs,settings),
- * each with its own x0 and its own persistent ADMM state (references per instance: tinympc_set_x_ref_batch below). device < 0 keeps the current HIP device. */
+/* Batched setup: `batch` independent MPC instances sharing (A,B,fdyn,Q,R,rho,settings) and, by default, bounds and refs,
+ * each with its own x0 and its own persistent ADMM state (references per instance: tinympc_set_x_ref_batch below; bounds per
+ * instance: tinympc_set_bound_constraints_batch below). device < 0 keeps the current HIP device. */
 int tinympc_setup_batch(tinympc_solver **out, const double *A, const double *B, const double *fdyn,
                         const double *Q, const double *R, double rho, int nx, int nu, int N,
                         int batch, int device, int verbose);
@@ -233,6 +234,23 @@ int tinympc_set_u_ref_batch(tinympc_solver *s, const double *Urefs, int rows, in
 /* Same, from device memory on the handle's GPU; same contract as tinympc_set_x0_batch_device. */
 int tinympc_set_x_ref_batch_device(tinympc_solver *s, const double *d_Xrefs, int rows, int cols, int first, int count);
 int tinympc_set_u_ref_batch_device(tinympc_solver *s, const double *d_Urefs, int rows, int cols, int first, int count);
+
+/* Per-instance box bounds for instances [first, first+count) of a batched handle.
+ * x_min, x_max: nx x cols x count, column-major, instance b's block at b*nx*cols; u_min, u_max: nu x ucols x count likewise.
+ * cols = N (bounds per knot; then ucols = N-1) or cols = 1 (one box per instance, held over the whole horizon; then ucols = 1).
+ * Instance b then solves exactly what it would solve alone after set_bound_constraints(bounds_b); like that verb, the call enables
+ * both bound families (a later tinympc_update_settings can switch either off again, for every instance). The first call turns
+ * per-instance mode on; instances outside the range keep the handle's shared bounds of that moment. A later
+ * tinympc_set_bound_constraints returns every instance to shared bounds. reset_workspace, update_settings, the reference verbs, the
+ * solve verbs and mpc_step_batch keep them. Boxes (with references constant over the horizon) run on layout D where the handle runs
+ * layout D, everything else on layout A; with the cone / linear families, adaptive rho or nx+nu > 64 a solve returns
+ * TINYMPC_ERR_UNSUPPORTED (never a solve with the shared bounds). Invalid arguments return TINYMPC_ERR_INVALID_INPUT and leave the mode
+ * as it was. Single-instance handles: the same as tinympc_set_bound_constraints. The input has been copied when the call returns. */
+int tinympc_set_bound_constraints_batch(tinympc_solver *s, const double *x_min, const double *x_max,
+                                        const double *u_min, const double *u_max, int cols, int first, int count);
+/* Same, from device memory on the handle's GPU; same contract as tinympc_set_x0_batch_device. */
+int tinympc_set_bound_constraints_batch_device(tinympc_solver *s, const double *d_x_min, const double *d_x_max,
+                                               const double *d_u_min, const double *d_u_max, int cols, int first, int count);
 
 /* Zero the persistent ADMM state (cold start) of every instance and put every instance's rho back to
  * the setup value; x0 is kept. */

@@ -80,6 +80,10 @@ SIGNATURES = {
     "tinympc_set_u_ref_batch": (C.c_int, [Handle, c_double_p, C.c_int, C.c_int, C.c_int, C.c_int]),
     "tinympc_set_x_ref_batch_device": (C.c_int, [Handle, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
     "tinympc_set_u_ref_batch_device": (C.c_int, [Handle, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "tinympc_set_bound_constraints_batch": (C.c_int, [Handle, c_double_p, c_double_p, c_double_p, c_double_p,
+                                                      C.c_int, C.c_int, C.c_int]),
+    "tinympc_set_bound_constraints_batch_device": (C.c_int, [Handle, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                             C.c_int, C.c_int, C.c_int]),
     "tinympc_reset_workspace": (C.c_int, [Handle]),
     "tinympc_get_rho_batch": (C.c_int, [Handle, c_double_p, C.c_int, C.c_int]),
     "tinympc_get_solution_batch": (C.c_int, [Handle, c_double_p, c_double_p, C.c_int, C.c_int]),

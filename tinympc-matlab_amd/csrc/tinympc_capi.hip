@@ -357,6 +357,7 @@ int tinympc_set_bound_constraints(tinympc_solver *s, const double *x_min, const 
     s->st.en_state_bound = 1;  // bindings.cpp:206-207
     s->st.en_input_bound = 1;
     s->tables_dirty = true;
+    s->ibnd = false;  // (per-instance bounds: every instance is on the shared bounds again)
     if (verbose) printf("Bound constraints set\n");
     return TINYMPC_OK;
 }
@@ -1000,6 +1001,19 @@ int tinympc_set_x0_batch_device(tinympc_solver *s, const double *d_x0s, int firs
 
 namespace {
 
+// The per-instance table rows (SolveParams::iref_lr / iref_pn), allocated at the first per-instance verb of a batched handle.
+int alloc_inst_tables(tinympc_solver *s) {
+    int rc;
+    if (s->dIlr) return TINYMPC_OK;
+    if ((rc = dalloc(s, &s->dIlr, inst_lr_doubles(s->groups, s->N)))) return rc;
+    if ((rc = dalloc(s, &s->dIpn, (size_t)s->groups * 64))) return rc;
+    if ((rc = dalloc(s, &s->dIgoal, (size_t)s->groups * 64))) return rc;
+    HIP_TRY(hipMemsetAsync(s->dIlr, 0, sizeof(double) * inst_lr_doubles(s->groups, s->N), s->stream));
+    HIP_TRY(hipMemsetAsync(s->dIpn, 0, sizeof(double) * s->groups * 64, s->stream));
+    HIP_TRY(hipMemsetAsync(s->dIgoal, 0, sizeof(double) * s->groups * 64, s->stream));
+    return TINYMPC_OK;
+}
+
 // tinympc_set_x_ref_batch / _u_ref_batch (+ _device): one half (x or u) of instances [first, first+count). The half enters per-instance
 // mode at its first call (every instance then holds the shared reference of that moment); the table rows of the instances named here
 // are rebuilt at the next launch (refresh_inst_tables). Single-instance handles: the shared verb.
@@ -1040,14 +1054,7 @@ int set_ref_batch(tinympc_solver *s, bool is_x, const double *src, bool on_devic
     }
     double *&dst = is_x ? s->dXi : s->dUi;
     if (!dst && (rc = dalloc(s, &dst, per * s->batch))) return rc;
-    if (!s->dIlr) {
-        if ((rc = dalloc(s, &s->dIlr, inst_lr_doubles(s->groups, s->N)))) return rc;
-        if ((rc = dalloc(s, &s->dIpn, (size_t)s->groups * 64))) return rc;
-        if ((rc = dalloc(s, &s->dIgoal, (size_t)s->groups * 64))) return rc;
-        HIP_TRY(hipMemsetAsync(s->dIlr, 0, sizeof(double) * inst_lr_doubles(s->groups, s->N), s->stream));
-        HIP_TRY(hipMemsetAsync(s->dIpn, 0, sizeof(double) * s->groups * 64, s->stream));
-        HIP_TRY(hipMemsetAsync(s->dIgoal, 0, sizeof(double) * s->groups * 64, s->stream));
-    }
+    if ((rc = alloc_inst_tables(s))) return rc;
     if (!mode) {  // every instance starts from the shared reference of this moment
         InstRefStoreParams b{};
         b.src = is_x ? s->dXref : s->dUref; b.src_stride = 0; b.rows = R; b.src_cols = C; b.cols = C;
@@ -1084,7 +1091,122 @@ int set_ref_batch(tinympc_solver *s, bool is_x, const double *src, bool on_devic
     return TINYMPC_OK;
 }
 
+// tinympc_set_bound_constraints_batch (+ _device): the bounds of instances [first, first+count). The handle enters per-instance mode at
+// the first call (every instance then holds the shared bounds of that moment); the clamp rows of the instances named here are rebuilt at
+// the next launch (refresh_inst_tables). Like the shared verb, the call enables both bound families. Single-instance handles: the shared verb.
+int set_bounds_batch(tinympc_solver *s, const double *const src[4], bool on_device, int cols, int first, int count) {
+    const char *verb = on_device ? "set_bound_constraints_batch_device" : "set_bound_constraints_batch";
+    int rc = check_handle(s);
+    if (rc) return rc;
+    if (!src[0] || !src[1] || !src[2] || !src[3]) return fail(TINYMPC_ERR_INVALID_INPUT, "%s requires x_min, x_max, u_min, u_max", verb);
+    const int N = s->N;
+    if (cols != N && cols != 1)
+        return fail(TINYMPC_ERR_INVALID_INPUT, "%s: cols is %d. Expected %d (bounds per knot) or 1 (one box per instance).", verb, cols, N);
+    if (first < 0 || count < 0 || first + count > s->batch)
+        return fail(TINYMPC_ERR_INVALID_INPUT, "%s: instance range [%d, %d) outside batch of %d", verb, first, first + count, s->batch);
+    const int R[4] = {s->nx, s->nx, s->nu, s->nu}, C[4] = {N, N, N - 1, N - 1};
+    const int in_cols[4] = {cols, cols, cols == 1 ? 1 : N - 1, cols == 1 ? 1 : N - 1};
+    if (on_device && count > 0) {  // device memory of the handle's own GPU (a host pointer or another GPU's memory is refused here)
+        for (int a = 0; a < 4; ++a) {
+            hipPointerAttribute_t attr{};
+            const hipError_t e = hipPointerGetAttributes(&attr, src[a]);
+            (void)hipGetLastError();
+            if (e != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != s->device)
+                return fail(TINYMPC_ERR_INVALID_INPUT, "%s: the bounds are not device memory of the handle's GPU %d", verb, s->device);
+        }
+    }
+    if (s->batch == 1) {  // the shared verb
+        if (count == 0) return TINYMPC_OK;
+        std::vector<double> h[4];
+        if (on_device && (rc = bind_device(s))) return rc;
+        for (int a = 0; a < 4; ++a) {
+            const size_t per = (size_t)R[a] * C[a], in_per = (size_t)R[a] * in_cols[a];
+            std::vector<double> in;
+            const double *p = src[a];
+            if (on_device) {
+                in.resize(in_per);
+                if ((rc = download(s, in.data(), src[a], sizeof(double) * in_per))) return rc;
+                p = in.data();
+            }
+            h[a].resize(per);
+            for (size_t e = 0; e < per; ++e) h[a][e] = p[in_cols[a] == 1 ? e % R[a] : e];
+        }
+        return tinympc_set_bound_constraints(s, h[0].data(), h[1].data(), h[2].data(), h[3].data(), 0);
+    }
+    if ((rc = bind_device(s))) return rc;
+    if (!s->st.en_state_bound || !s->st.en_input_bound) {  // bindings.cpp:206-207
+        s->st.en_state_bound = 1;
+        s->st.en_input_bound = 1;
+        s->tables_dirty = true;  // (the shared tables follow the flags; refresh_derived then marks every instance's rows)
+    }
+    if (s->layout_m) {  // (no kernel carries them: the next launch refuses until the shared verb clears the mode)
+        s->ibnd = true;
+        return TINYMPC_OK;
+    }
+    const size_t X = (size_t)s->batch * s->X(), U = (size_t)s->batch * s->U();
+    if (!s->dBi && (rc = dalloc(s, &s->dBi, 2 * X + 2 * U))) return rc;
+    if ((rc = alloc_inst_tables(s))) return rc;
+    if (!s->dIb) {
+        if ((rc = dalloc(s, &s->dIb, inst_bnd_doubles(s->groups, N)))) return rc;
+        if ((rc = dalloc(s, &s->dIbg, (size_t)2 * s->groups * 64))) return rc;
+        HIP_TRY(hipMemsetAsync(s->dIb, 0, sizeof(double) * inst_bnd_doubles(s->groups, N), s->stream));
+        HIP_TRY(hipMemsetAsync(s->dIbg, 0, sizeof(double) * 2 * s->groups * 64, s->stream));
+    }
+    double *dst[4] = {s->dBi, s->dBi + X, s->dBi + 2 * X, s->dBi + 2 * X + U};
+    const double *shared[4] = {s->dxmin, s->dxmax, s->dumin, s->dumax};
+    if (!s->ibnd) {  // every instance starts from the shared bounds of this moment
+        for (int a = 0; a < 4; ++a) {
+            InstRefStoreParams b{};
+            b.src = shared[a]; b.src_stride = 0; b.rows = R[a]; b.src_cols = C[a]; b.cols = C[a];
+            b.first = 0; b.count = s->batch; b.dst = dst[a];
+            HIP_TRY(launch_store_inst_refs(b, s->stream));
+        }
+        s->ibnd = true;
+        s->ibnd_const = s->xmin_const && s->xmax_const && s->umin_const && s->umax_const;
+        s->iref_mark(0, s->batch);
+    }
+    if (count > 0) {
+        for (int a = 0; a < 4; ++a) {
+            const size_t per = (size_t)R[a] * C[a], in_per = (size_t)R[a] * in_cols[a];
+            if (cols == N) {  // per knot: the caller's layout is the handle's
+                bool constant = !on_device;  // (device input: not looked at)
+                for (int b = 0; constant && b < count; ++b) constant = rows_constant(src[a] + (size_t)b * per, R[a], C[a]);
+                if (!constant) s->ibnd_const = false;
+                HIP_TRY(hipMemcpyAsync(dst[a] + (size_t)first * per, src[a], sizeof(double) * per * count,
+                                       on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s->stream));
+            } else {  // one box: held over the horizon on the device
+                const double *dsrc = src[a];
+                if (!on_device) {
+                    const size_t cap = (size_t)s->batch * (s->nx > s->nu ? s->nx : s->nu);
+                    if (!s->dIstage && (rc = dalloc(s, &s->dIstage, cap))) return rc;
+                    HIP_TRY(hipMemcpyAsync(s->dIstage, src[a], sizeof(double) * in_per * count, hipMemcpyHostToDevice, s->stream));
+                    dsrc = s->dIstage;
+                }
+                InstRefStoreParams b{};
+                b.src = dsrc; b.src_stride = in_per; b.rows = R[a]; b.src_cols = 1; b.cols = C[a];
+                b.first = first; b.count = count; b.dst = dst[a];
+                HIP_TRY(launch_store_inst_refs(b, s->stream));
+            }
+        }
+        s->iref_mark(first, first + count);
+    }
+    // the caller keeps ownership of its buffers: the copies have completed when the call returns (the tinympc_set_x0_batch_device rule)
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return TINYMPC_OK;
+}
+
 }  // namespace
+
+int tinympc_set_bound_constraints_batch(tinympc_solver *s, const double *x_min, const double *x_max, const double *u_min,
+                                        const double *u_max, int cols, int first, int count) {
+    const double *const src[4] = {x_min, x_max, u_min, u_max};
+    return set_bounds_batch(s, src, false, cols, first, count);
+}
+int tinympc_set_bound_constraints_batch_device(tinympc_solver *s, const double *d_x_min, const double *d_x_max, const double *d_u_min,
+                                               const double *d_u_max, int cols, int first, int count) {
+    const double *const src[4] = {d_x_min, d_x_max, d_u_min, d_u_max};
+    return set_bounds_batch(s, src, true, cols, first, count);
+}
 
 int tinympc_set_x_ref_batch(tinympc_solver *s, const double *Xrefs, int rows, int cols, int first, int count) {
     return set_ref_batch(s, true, Xrefs, false, rows, cols, first, count);

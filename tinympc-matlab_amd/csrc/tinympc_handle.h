@@ -200,8 +200,19 @@ struct tinympc_solver {
     int d_goal = -1;  // the run-time specialised goal kernel (16 lanes beyond the compiled-in shapes, 32 / 64 lanes): -1 not asked yet, 0 no, 1 yes
     bool iref() const { return iref_x || iref_u; }
     bool iref_goal() const {
-        return (iref_x ? iref_x_goal : xref_const) && (iref_u ? iref_u_goal : uref_const) && xmin_const && xmax_const && umin_const && umax_const;
+        return (iref_x ? iref_x_goal : xref_const) && (iref_u ? iref_u_goal : uref_const) &&
+               (ibnd ? ibnd_const : xmin_const && xmax_const && umin_const && umax_const);
     }
+    // Per-instance bounds (tinympc_set_bound_constraints_batch; batched handles): in per-instance mode from the first call until the next
+    // tinympc_set_bound_constraints; instances the verb did not name hold the shared bounds of the moment the mode began. dBi: every
+    // instance's x_min | x_max | u_min | u_max, each [batch] column-major nx x N / nu x (N-1) blocks; dIb / dIbg: the clamp rows the solve
+    // kernels read (SolveParams::ibnd: layout A's rows, layout D's knot 0), rebuilt with the reference rows (the same dirty interval).
+    // The mode always runs on the per-instance reference rows as well (dIlr / dIpn / dIgoal, with the shared references where a half is
+    // shared). ibnd_const: every instance's bounds are constant over the horizon (sticky, as iref_x_goal): the goal form on layout D.
+    bool ibnd = false, ibnd_const = false;
+    int d_gbnd = -1;  // the run-time specialised goal kernel with per-instance bounds: -1 not asked yet, 0 no, 1 yes
+    double *dBi = nullptr, *dIb = nullptr, *dIbg = nullptr;
+    bool inst_tables() const { return iref() || ibnd; }  // the per-instance table rows are in use
     double *dXi = nullptr, *dUi = nullptr, *dIlr = nullptr, *dIpn = nullptr, *dIgoal = nullptr, *dIstage = nullptr;
     const double *iref_rows() const { return dIlr + (size_t)tinympc::INST_LR_PAD * 64; }  // SolveParams::iref_lr on layout A
     int iref_dirty_lo = 0, iref_dirty_hi = 0;
@@ -301,7 +312,8 @@ struct LaunchPlan {
     KernelId kernel = KernelId::A;
     char layout = 'A';                       // what tinympc_get_layout reports
     bool families = false, adaptive = false;  // variant bits of the launch
-    bool inst_refs = false;                  // ... per-instance references (layout A's InstRefs variant)
+    bool inst_refs = false;                  // ... per-instance references (layout A's InstRefs variant) or bounds (see inst_bounds)
+    bool inst_bounds = false;                // ... per-instance bounds (layout A's InstBounds variant, layout D's goal form with bounds)
     bool jit = false;                        // a run-time specialisation (tinympc_jit.hip) rather than a compiled-in kernel
     bool host_exchange = false;              // the kernel serves the pinned-host paths (x0 in, solution / completion stamp out)
     int workgroups = 0;

@@ -3,6 +3,7 @@
 //   k_precompute        P1  tiny_precompute_and_set_cache         (reference tiny_api.cpp:124-190)
 //   k_build_operators       fuses the cache into the two 1-step sweep operators used by the solve
 //   k_build_tables          per-knot clamp bounds / linear-cost reference terms
+//   k_build_inst_tables / k_build_inst_bounds   the same rows per instance (per-instance references / bounds of a batched handle)
 //   k_build_adapt           adaptive rho: the sensitivity rows of the sweep operators and [A'; B']
 //
 // The solve kernel itself (M1: F1, S1, D1, L1, R1, C1, B1) is in tinympc_solve.hip.
@@ -639,6 +640,52 @@ hipError_t launch_build_inst_tables(const InstTableParams &p, hipStream_t stream
     if (total == 0) return hipSuccess;
     const size_t blocks = (total + 255) / 256;
     hipLaunchKernelGGL(k_build_inst_tables, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, stream, p);
+    return hipGetLastError();
+}
+
+// Per-instance bounds: the clamp rows of instances [first, first+count), in the same lane order (lane j*W + r of group g is row r of
+// instance g*(64/W) + j) and with k_build_tables' expressions -- an instance whose bounds equal the shared ones gets bit-identical rows;
+// a disabled family is -inf / +inf for every instance. Knot 0's rows also go to knot0 (layout D's goal form).
+__global__ void __launch_bounds__(256) k_build_inst_bounds(const InstBoundParams p) {
+    const int nx = p.nx, nu = p.nu, N = p.N, W = p.W, nxu = nx + nu, TR = N + 2;
+    const size_t X = (size_t)nx * N, U = (size_t)nu * (N - 1);
+    const size_t per = (size_t)TR * W, total = per * p.count, bhi = inst_bnd_hi_offset(p.groups, N);
+    const double inf = __longlong_as_double(0x7FF0000000000000LL);
+    for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
+        const long inst = p.first + (long)(idx / per);
+        const int e = (int)(idx % per), row = e / W, r = e % W, kn = row - 1;
+        const long grp = inst / (64 / W);
+        const int lane = (int)(inst % (64 / W)) * W + r;
+        double l = -inf, h = inf;
+        if (kn < 0 || kn >= N) {
+            // padding row
+        } else if (r < nx) {
+            if (p.en_state_bound) {
+                l = p.x_min[inst * X + r + (size_t)kn * nx];
+                h = p.x_max[inst * X + r + (size_t)kn * nx];
+            }
+        } else if (r < nxu && kn < N - 1) {
+            const int j = r - nx;
+            if (p.en_input_bound) {
+                l = p.u_min[inst * U + j + (size_t)kn * nu];
+                h = p.u_max[inst * U + j + (size_t)kn * nu];
+            }
+        }
+        const size_t o = ((size_t)grp * TR + row) * 64 + lane;
+        p.rows[o] = l;
+        p.rows[bhi + o] = h;
+        if (row == 1) {
+            p.knot0[(size_t)grp * 64 + lane] = l;
+            p.knot0[(size_t)p.groups * 64 + (size_t)grp * 64 + lane] = h;
+        }
+    }
+}
+
+hipError_t launch_build_inst_bounds(const InstBoundParams &p, hipStream_t stream) {
+    const size_t total = (size_t)(p.N + 2) * p.W * p.count;
+    if (total == 0) return hipSuccess;
+    const size_t blocks = (total + 255) / 256;
+    hipLaunchKernelGGL(k_build_inst_bounds, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, stream, p);
     return hipGetLastError();
 }
 

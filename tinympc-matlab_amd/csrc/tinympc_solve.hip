@@ -1,7 +1,8 @@
 // tinympc_solve.hip -- k_admm_solve: the whole TinyMPC solve() as ONE persistent kernel (gfx950, FP64); layout A's box path.
 // Layout A has two more variants of the same kernel, which share its body (tinympc_solve_a_body.h) and its launcher
 // (tinympc_solve_a.h): k_admm_solve_fam (tinympc_solve_fam.hip, the cone / linear slack families) and k_admm_solve_adapt
-// (tinympc_solve_adapt.hip, adaptive rho). A fourth, k_admm_solve_iref (below), carries per-instance references.
+// (tinympc_solve_adapt.hip, adaptive rho). A fourth, k_admm_solve_iref (below), carries per-instance references, and a fifth,
+// k_admm_solve_ibnd, per-instance bounds as well.
 //
 //   M1 solve                 admm.cpp:109-207      F1 forward_pass          admm.cpp:25-35
 //   S1 update_slack          admm.cpp:43-59        D1 update_dual           admm.cpp:65-69
@@ -77,6 +78,17 @@ __global__ void __launch_bounds__(64) k_admm_solve_iref(const SolveParams p) {
 }
 template hipError_t launch_solve_a_e<SolveExt::InstRefs>(const SolveParams &, int, int, size_t, hipStream_t);
 
+// k_admm_solve_ibnd: k_admm_solve_iref for a batched handle whose instances also have their OWN bounds (tinympc_set_bound_constraints_batch).
+// The forward sweep streams the instance's clamp rows lo | hi from SolveParams::ibnd (k_build_inst_bounds, k_build_tables' expressions)
+// four knots ahead, as the backward sweep streams the linref rows; an instance whose bounds and references are the shared ones computes
+// exactly what k_admm_solve computes.
+template <int W, int KT, bool TLDS, bool GMEM>
+__global__ void __launch_bounds__(64) k_admm_solve_ibnd(const SolveParams p) {
+    constexpr SolveExt E = SolveExt::InstBounds;
+#include "tinympc_solve_a_body.h"
+}
+template hipError_t launch_solve_a_e<SolveExt::InstBounds>(const SolveParams &, int, int, size_t, hipStream_t);
+
 hipError_t launch_solve_a(const SolveParams &p, SolveExt ext, int W, int KT, size_t lds_bytes, hipStream_t stream) {
     switch (ext) {
         case SolveExt::Box: return launch_solve_a_e<SolveExt::Box>(p, W, KT, lds_bytes, stream);
@@ -87,6 +99,9 @@ hipError_t launch_solve_a(const SolveParams &p, SolveExt ext, int W, int KT, siz
         case SolveExt::InstRefs:
             if (!p.iref_lr || !p.iref_pn) return hipErrorInvalidValue;
             return launch_solve_a_e<SolveExt::InstRefs>(p, W, KT, lds_bytes, stream);
+        case SolveExt::InstBounds:
+            if (!p.iref_lr || !p.iref_pn || !p.ibnd) return hipErrorInvalidValue;
+            return launch_solve_a_e<SolveExt::InstBounds>(p, W, KT, lds_bytes, stream);
     }
     return hipErrorInvalidValue;
 }

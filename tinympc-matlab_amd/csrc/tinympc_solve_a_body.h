@@ -1,12 +1,14 @@
 // tinympc_solve_a_body.h -- the body of layout A's three solve kernels (k_admm_solve, k_admm_solve_fam, k_admm_solve_adapt;
-// tinympc_solve_a.h; and k_admm_solve_iref). Included INSIDE each kernel, with the kernel's template parameters W, KT, TLDS, GMEM, its
-// parameter p and the variant E (SolveExt) in scope; the families', adaptive rho's and per-instance references' additions are compiled
-// only into their variant.
+// tinympc_solve_a.h; and k_admm_solve_iref, k_admm_solve_ibnd). Included INSIDE each kernel, with the kernel's template parameters W, KT,
+// TLDS, GMEM, its parameter p and the variant E (SolveExt) in scope; the families', adaptive rho's and per-instance references' and
+// bounds' additions are compiled only into their variant.
 // No include guard: it is meant to be included once per kernel.
     constexpr bool FAM = E == SolveExt::Families, ADAPT = E == SolveExt::Adaptive;
     // per-instance references: this instance's linref rows and pNref from p.iref_lr / iref_pn (HBM / L2, the lane's own 512-byte line
     // per knot) instead of the shared tables; everything else as on the box path
-    constexpr bool IREF = E == SolveExt::InstRefs;
+    // per-instance bounds (with the per-instance references' rows): this instance's clamp rows from p.ibnd, streamed like the linref rows
+    constexpr bool IBND = E == SolveExt::InstBounds;
+    constexpr bool IREF = E == SolveExt::InstRefs || IBND;
     extern __shared__ __attribute__((aligned(16))) double smem[];
     refresh_reference_tables(p, W, KT);  // references handed over in pinned host memory (single-instance handles; adaptive rho: never)
     constexpr int IPW = 64 / W;
@@ -165,6 +167,21 @@
 #pragma unroll
         for (int k = 0; k < 4; ++k) lr_top[k] = t[-64 * k];
     }
+    // per-instance bounds: knot 0's rows (the state lanes' x_0 clamp) and the first four rows the forward sweep reads stay in registers
+    // for the whole solve; the ring in the sweep keeps the rest four knots ahead. hi rows lie bhi doubles behind the lo rows.
+    const size_t bhi = IBND ? inst_bnd_hi_offset((int)p.groups, N) : 0;
+    double blo0 = 0.0, bhi0 = 0.0, blo_top[IBND ? 4 : 1], bhi_top[IBND ? 4 : 1];
+    if constexpr (IBND) {
+        const double *t = p.ibnd + ((size_t)grp * table_rows(N) + 1) * 64 + lane;  // row 1 = knot 0
+        blo0 = t[0];
+        bhi0 = t[bhi];
+        t += (is_x ? 1 : 0) * 64;  // (koff, below: the first row a state lane's sweep reads is knot 1's)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            blo_top[k] = t[64 * k];
+            bhi_top[k] = t[bhi + 64 * k];
+        }
+    }
     const double x0v = (inst_ok && is_x) ? p.x0[inst * nx + r] : 0.0;
     if (p.x0_mirror && inst_ok && is_x) p.x0_mirror[inst * nx + r] = x0v;  // zero-copy tick: x0 came from host memory
     const int dIdx = is_u ? (j * nu + (r - nx)) : 0;
@@ -306,7 +323,7 @@
             const bool on = st && is_x;
             const double g = sG[64 + lane], vold = sV[64 + lane];
             const double s = x0v + g;
-            const double snew = fmin(t_lo[TOFF + W + r], fmax(t_lo[W + r], s));
+            const double snew = IBND ? fmin(bhi0, fmax(blo0, s)) : fmin(t_lo[TOFF + W + r], fmax(t_lo[W + r], s));
             pri = is_x ? fabs(x0v - snew) : 0.0;
             dua = is_x ? fabs(vold - snew) : 0.0;
             double gcn, gln, lx;
@@ -322,13 +339,18 @@
         }
         {
             const double *pg = sG + (1 + koff) * 64 + lane;  // this lane's operands of step 0
-            const double *pt = t_lo + (1 + koff) * W + r;
+            constexpr int BRS = IBND ? 64 : W;  // clamp row stride
+            const double *pt = IBND ? p.ibnd + ((size_t)grp * table_rows(N) + 1 + koff) * 64 + lane : t_lo + (1 + koff) * W + r;
             const double *pd = sD + dIdx;
             double *ps = sG + (st ? (1 + koff) * 64 + lane : ldummy);
             double *pgv = gV + (st ? koff * 64 + lane : gdummy);
             const int inc = st ? 64 : 0;
             double xcur = x0v;
-            FwdOperands A{pg[0], pg[VOFF], pt[0], pt[TOFF], pd[0]}, B;
+            FwdOperands A{pg[0], pg[VOFF], IBND ? blo_top[0] : pt[0], IBND ? bhi_top[0] : pt[TOFF], pd[0]}, B;
+            // per-instance rows come from HBM / L2, not LDS: three more rows of each in flight (reads past the last group's rows land in
+            // the hi rows or in the padding behind them, INST_LR_PAD; never used)
+            double l1 = 0.0, l2 = 0.0, l3 = 0.0, h1 = 0.0, h2 = 0.0, h3 = 0.0;
+            if constexpr (IBND) { l1 = blo_top[1]; l2 = blo_top[2]; l3 = blo_top[3]; h1 = bhi_top[1]; h2 = bhi_top[2]; h3 = bhi_top[3]; }
             // families: the duals gc | gl read one step ahead, the new ones and lx written where pgv writes
             const double *pgc = gGC + koff * 64 + lane, *pgl = gGL + koff * 64 + lane;
             double *pwc = gGC + (pgv - gV), *pwl = gGL + (pgv - gV), *pwx = gLX + (pgv - gV);
@@ -337,10 +359,16 @@
             auto fstep = [&](const FwdOperands &cur, FwdOperands &nxt) {
                 const double w = is_x ? xcur : cur.dv;
                 pg += 64;  // operands of the next step, fetched while this step's mat-vec runs
-                pt += W;
+                pt += BRS;
                 pd += dstride;
                 if constexpr (FAM) { pgc += 64; pgl += 64; }
-                nxt.g = pg[0]; nxt.vold = pg[VOFF]; nxt.lo = pt[0]; nxt.hi = pt[TOFF]; nxt.dv = pd[0];
+                if constexpr (IBND) {
+                    nxt.g = pg[0]; nxt.vold = pg[VOFF]; nxt.dv = pd[0];
+                    nxt.lo = l1; l1 = l2; l2 = l3; l3 = pt[3 * BRS];
+                    nxt.hi = h1; h1 = h2; h2 = h3; h3 = pt[bhi + 3 * BRS];
+                } else {
+                    nxt.g = pg[0]; nxt.vold = pg[VOFF]; nxt.lo = pt[0]; nxt.hi = pt[TOFF]; nxt.dv = pd[0];
+                }
                 if constexpr (FAM) { nxt.gc = pgc[0]; nxt.gl = pgl[0]; }
                 const double out = group_matvec<W, KT>(mf, w, cf);  // state lanes: x_{i+1}; input lanes: u_i
                 double gnew, snew;

@@ -343,6 +343,45 @@ class TinyMPC:
         a = _f(a)
         _lib.check(f_host(self._h, _p(a), rows, cols, first, a.shape[-1]))
 
+    def set_bound_constraints_batch(self, x_min, x_max, u_min, u_max, first: int = 0):
+        """Per-instance box bounds for instances first, first+1, ...: numpy arrays of shape (nx, count) / (nu, count) (one box per
+        instance, held over the horizon) or (nx, N, count) / (nu, N-1, count) (bounds per knot), or CUDA torch tensors with the same
+        memory layout, (count, nx) / (count, nu) or (count, N, nx) / (count, N-1, nu) contiguous float64. All four in the same form.
+        Enables both bound families, as set_bound_constraints does; set_bound_constraints() returns every instance to shared bounds."""
+        self._check_setup()
+        arrays = (x_min, x_max, u_min, u_max)
+        rows = (self.nx, self.nx, self.nu, self.nu)
+        full = (self.N, self.N, self.N - 1, self.N - 1)
+        on_device = [hasattr(a, "data_ptr") and getattr(a, "is_cuda", False) for a in arrays]
+        if any(on_device):
+            import torch
+            if not all(on_device):
+                raise TinyMPCError(_lib.ERR_INVALID_INPUT, "bounds: all four must be CUDA tensors, or none")
+            for a, r, c in zip(arrays, rows, full):
+                if a.dtype != torch.float64 or not a.is_contiguous() or a.dim() not in (2, 3) or a.shape[-1] != r or \
+                        (a.dim() == 3 and a.shape[1] != c):
+                    raise TinyMPCError(_lib.ERR_INVALID_INPUT, "bounds on the device must be contiguous float64 tensors of shape "
+                                       "(count, %d) or (count, %d, %d), got %s %s" % (r, c, r, a.dtype, tuple(a.shape)))
+            if len({(a.dim(), a.shape[0]) for a in arrays}) != 1:
+                raise TinyMPCError(_lib.ERR_INVALID_INPUT, "bounds: all four must have the same form and count")
+            cols = 1 if x_min.dim() == 2 else self.N
+            torch.cuda.current_stream(x_min.device).synchronize()  # (the set_x0_batch contract)
+            _lib.check(self._L.tinympc_set_bound_constraints_batch_device(
+                self._h, *[C.c_void_p(a.data_ptr()) for a in arrays], cols, first, x_min.shape[0]))
+        else:
+            arrs = [np.asarray(a, dtype=np.float64) for a in arrays]
+            for a, r, c in zip(arrs, rows, full):
+                if a.ndim not in (2, 3) or a.shape[0] != r or (a.ndim == 3 and a.shape[1] != c):
+                    raise TinyMPCError(_lib.ERR_INVALID_INPUT, "bounds must be %d x count or %d x %d x count, got %s"
+                                       % (r, r, c, a.shape))
+            if len({(a.ndim, a.shape[-1]) for a in arrs}) != 1:
+                raise TinyMPCError(_lib.ERR_INVALID_INPUT, "bounds: all four must have the same form and count")
+            cols = 1 if arrs[0].ndim == 2 else self.N
+            arrs = [_f(a) for a in arrs]
+            _lib.check(self._L.tinympc_set_bound_constraints_batch(self._h, *[_p(a) for a in arrs], cols, first, arrs[0].shape[-1]))
+        self.settings["en_state_bound"] = True
+        self.settings["en_input_bound"] = True
+
     def _tick_buffers(self):
         """Persistent buffers of the per-tick verbs (addresses cached: see _lib.fast_tick_functions)."""
         if self._tick is None or self._tick[0].shape != (self.nx, self.batch):
