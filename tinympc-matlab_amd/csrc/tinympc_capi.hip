@@ -286,7 +286,7 @@ int tinympc_set_x_ref(tinympc_solver *s, const double *Xref, int rows, int cols,
     // the workspace shape under the solver; rejected here.
     if (rows != s->nx || cols != s->N)
         return fail(TINYMPC_ERR_INVALID_INPUT, "State reference trajectory (x_ref) is %d x %d. Expected %d x %d.", rows, cols, s->nx, s->N);
-    s->iref_x = false;  // (per-instance references: this half is shared again, for every instance)
+    s->inst.x = false;  // (per-instance references: this half is shared again, for every instance)
     s->xref_const = rows_constant(Xref, s->nx, s->N);
     if (s->host_path()) {  // no device call: the next launch reads the pinned copy and rebuilds the table rows itself
         if (s->host_sol_state == 1 && (rc = tinympc_synchronize(s))) return rc;  // a launch in flight may be reading it
@@ -316,7 +316,7 @@ int tinympc_set_u_ref(tinympc_solver *s, const double *Uref, int rows, int cols,
     if (!Uref) return fail(TINYMPC_ERR_INVALID_INPUT, "set_u_ref: Uref is NULL");
     if (rows != s->nu || cols != s->N - 1)
         return fail(TINYMPC_ERR_INVALID_INPUT, "Control/input reference trajectory (u_ref) is %d x %d. Expected %d x %d.", rows, cols, s->nu, s->N - 1);
-    s->iref_u = false;
+    s->inst.u = false;
     s->uref_const = rows_constant(Uref, s->nu, s->N - 1);
     if (s->host_path()) {
         if (s->host_sol_state == 1 && (rc = tinympc_synchronize(s))) return rc;
@@ -357,7 +357,7 @@ int tinympc_set_bound_constraints(tinympc_solver *s, const double *x_min, const 
     s->st.en_state_bound = 1;  // bindings.cpp:206-207
     s->st.en_input_bound = 1;
     s->tables_dirty = true;
-    s->ibnd = false;  // (per-instance bounds: every instance is on the shared bounds again)
+    s->inst.bounds = false;  // (per-instance bounds: every instance is on the shared bounds again)
     if (verbose) printf("Bound constraints set\n");
     return TINYMPC_OK;
 }
@@ -1001,22 +1001,130 @@ int tinympc_set_x0_batch_device(tinympc_solver *s, const double *d_x0s, int firs
 
 namespace {
 
-// The per-instance table rows (SolveParams::iref_lr / iref_pn), allocated at the first per-instance verb of a batched handle.
-int alloc_inst_tables(tinympc_solver *s) {
+// One array of a per-instance verb: the handle's rows x cols block per instance, and where it goes.
+struct InstArray {
+    const double *src;      // the caller's blocks, one per instance: rows x cols, or rows x 1 (one column held over the horizon)
+    int rows, cols;
+    double **store;         // the per-instance store [batch][cols][rows] (InstState; alloc_inst_state)
+    const double *shared;   // what every instance holds when the mode begins ...
+    bool shared_const;      // ... and whether that is constant over the horizon
+    bool *constant;         // the mode's "constant over the horizon" flag
+};
+
+// The per-instance stores of `a`, the table rows (SolveParams::iref_lr / iref_pn / ibnd) and, for the bounds, layout A's clamp rows:
+// allocated at the first per-instance verb that needs them.
+int alloc_inst_state(tinympc_solver *s, const InstArray *a, int n, bool bounds) {
+    InstState &in = s->inst;
     int rc;
-    if (s->dIlr) return TINYMPC_OK;
-    if ((rc = dalloc(s, &s->dIlr, inst_lr_doubles(s->groups, s->N)))) return rc;
-    if ((rc = dalloc(s, &s->dIpn, (size_t)s->groups * 64))) return rc;
-    if ((rc = dalloc(s, &s->dIgoal, (size_t)s->groups * 64))) return rc;
-    HIP_TRY(hipMemsetAsync(s->dIlr, 0, sizeof(double) * inst_lr_doubles(s->groups, s->N), s->stream));
-    HIP_TRY(hipMemsetAsync(s->dIpn, 0, sizeof(double) * s->groups * 64, s->stream));
-    HIP_TRY(hipMemsetAsync(s->dIgoal, 0, sizeof(double) * s->groups * 64, s->stream));
+    for (int i = 0; i < n; ++i)
+        if (!*a[i].store && (rc = dalloc(s, a[i].store, (size_t)a[i].rows * a[i].cols * s->batch))) return rc;
+    const size_t lr = inst_lr_doubles(s->groups, s->N), row = (size_t)s->groups * 64, bnd = inst_bnd_doubles(s->groups, s->N);
+    if (!in.lr) {
+        if ((rc = dalloc(s, &in.lr, lr)) || (rc = dalloc(s, &in.pn, row)) || (rc = dalloc(s, &in.lrg, row)) || (rc = dalloc(s, &in.bndg, 2 * row)))
+            return rc;
+        HIP_TRY(hipMemsetAsync(in.lr, 0, sizeof(double) * lr, s->stream));
+        HIP_TRY(hipMemsetAsync(in.pn, 0, sizeof(double) * row, s->stream));
+        HIP_TRY(hipMemsetAsync(in.lrg, 0, sizeof(double) * row, s->stream));
+        HIP_TRY(hipMemsetAsync(in.bndg, 0, sizeof(double) * 2 * row, s->stream));
+    }
+    if (bounds && !in.bnd) {
+        if ((rc = dalloc(s, &in.bnd, bnd))) return rc;
+        HIP_TRY(hipMemsetAsync(in.bnd, 0, sizeof(double) * bnd, s->stream));
+    }
     return TINYMPC_OK;
 }
 
-// tinympc_set_x_ref_batch / _u_ref_batch (+ _device): one half (x or u) of instances [first, first+count). The half enters per-instance
-// mode at its first call (every instance then holds the shared reference of that moment); the table rows of the instances named here
-// are rebuilt at the next launch (refresh_inst_tables). Single-instance handles: the shared verb.
+// The one upload path of the per-instance verbs: arrays a[0, n) of instances [first, first+count), per knot or one column each
+// (one_col). The mode enters at its first call (every instance then holds the shared value of that moment); the table rows of the
+// instances named here are rebuilt at the next launch (refresh_inst_tables). Single-instance handles: `shared_verb`, handed the arrays
+// expanded to rows x cols. `verb` names the range error, `dev_verb` / `noun` the device-memory one.
+int set_inst_batch(tinympc_solver *s, const char *verb, const char *dev_verb, const char *noun, const InstArray *a, int n, bool &mode,
+                   bool bounds, bool on_device, bool one_col, int first, int count, int (*shared_verb)(tinympc_solver *, const double *const *)) {
+    int rc;
+    if (first < 0 || count < 0 || first + count > s->batch)
+        return fail(TINYMPC_ERR_INVALID_INPUT, "%s: instance range [%d, %d) outside batch of %d", verb, first, first + count, s->batch);
+    for (int i = 0; on_device && count > 0 && i < n; ++i) {  // device memory of the handle's own GPU (a host pointer or another GPU's memory is refused here)
+        hipPointerAttribute_t attr{};
+        const hipError_t e = hipPointerGetAttributes(&attr, a[i].src);
+        (void)hipGetLastError();
+        if (e != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != s->device)
+            return fail(TINYMPC_ERR_INVALID_INPUT, "%s: the %s are not device memory of the handle's GPU %d", dev_verb, noun, s->device);
+    }
+    if (s->batch == 1) {  // the shared verb, pinned-host path included
+        if (count == 0) return TINYMPC_OK;
+        if (on_device && (rc = bind_device(s))) return rc;
+        std::vector<double> h[4];
+        const double *hp[4];
+        for (int i = 0; i < n; ++i) {
+            const size_t per = (size_t)a[i].rows * a[i].cols, in_per = one_col ? (size_t)a[i].rows : per;
+            std::vector<double> in;
+            const double *src = a[i].src;
+            if (on_device) {
+                in.resize(in_per);
+                if ((rc = download(s, in.data(), src, sizeof(double) * in_per))) return rc;
+                src = in.data();
+            }
+            h[i].resize(per);
+            for (size_t e = 0; e < per; ++e) h[i][e] = src[one_col ? e % a[i].rows : e];
+            hp[i] = h[i].data();
+        }
+        return shared_verb(s, hp);
+    }
+    if ((rc = bind_device(s))) return rc;
+    if (bounds && (!s->st.en_state_bound || !s->st.en_input_bound)) {  // like the shared verb, bindings.cpp:206-207
+        s->st.en_state_bound = 1;
+        s->st.en_input_bound = 1;
+        s->tables_dirty = true;  // (the shared tables follow the flags; refresh_derived then marks every instance's rows)
+    }
+    if (s->layout_m) {  // (no kernel carries them: the next launch refuses until the shared verb clears the mode)
+        mode = true;
+        return TINYMPC_OK;
+    }
+    if ((rc = alloc_inst_state(s, a, n, bounds))) return rc;
+    if (!mode) {  // every instance starts from the shared value of this moment
+        for (int i = 0; i < n; ++i) *a[i].constant = true;
+        for (int i = 0; i < n; ++i) {
+            InstRefStoreParams b{};
+            b.src = a[i].shared; b.src_stride = 0; b.rows = a[i].rows; b.src_cols = a[i].cols; b.cols = a[i].cols;
+            b.first = 0; b.count = s->batch; b.dst = *a[i].store;
+            HIP_TRY(launch_store_inst_refs(b, s->stream));
+            *a[i].constant = *a[i].constant && a[i].shared_const;
+        }
+        mode = true;
+        s->inst.mark(0, s->batch);
+    }
+    if (count > 0) {
+        for (int i = 0; i < n; ++i) {
+            const int R = a[i].rows, C = a[i].cols;
+            const size_t per = (size_t)R * C;
+            if (!one_col) {  // per knot: the caller's layout is the handle's
+                bool constant = !on_device;  // (device input: not looked at)
+                for (int b = 0; constant && b < count; ++b) constant = rows_constant(a[i].src + (size_t)b * per, R, C);
+                if (!constant) *a[i].constant = false;
+                HIP_TRY(hipMemcpyAsync(*a[i].store + (size_t)first * per, a[i].src, sizeof(double) * per * count,
+                                       on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s->stream));
+            } else {  // one column: held over the horizon on the device
+                const double *dsrc = a[i].src;
+                if (!on_device) {
+                    const size_t cap = (size_t)s->batch * (s->nx > s->nu ? s->nx : s->nu);
+                    if (!s->inst.stage && (rc = dalloc(s, &s->inst.stage, cap))) return rc;
+                    HIP_TRY(hipMemcpyAsync(s->inst.stage, a[i].src, sizeof(double) * R * count, hipMemcpyHostToDevice, s->stream));
+                    dsrc = s->inst.stage;
+                }
+                InstRefStoreParams b{};
+                b.src = dsrc; b.src_stride = R; b.rows = R; b.src_cols = 1; b.cols = C;
+                b.first = first; b.count = count; b.dst = *a[i].store;
+                HIP_TRY(launch_store_inst_refs(b, s->stream));
+            }
+        }
+        s->inst.mark(first, first + count);
+    }
+    // the caller keeps ownership of its buffers: the copies have completed when the call returns (the tinympc_set_x0_batch_device rule)
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return TINYMPC_OK;
+}
+
+// tinympc_set_x_ref_batch / _u_ref_batch (+ _device): one half (x or u) of the references, a goal (cols = 1) or a trajectory per instance.
 int set_ref_batch(tinympc_solver *s, bool is_x, const double *src, bool on_device, int rows, int cols, int first, int count) {
     const char *verb = is_x ? "set_x_ref_batch" : "set_u_ref_batch";
     int rc = check_handle(s);
@@ -1025,75 +1133,17 @@ int set_ref_batch(tinympc_solver *s, bool is_x, const double *src, bool on_devic
     const int R = is_x ? s->nx : s->nu, C = is_x ? s->N : s->N - 1;
     if (rows != R || (cols != C && cols != 1))
         return fail(TINYMPC_ERR_INVALID_INPUT, "%s: the references are %d x %d per instance. Expected %d x %d or %d x 1.", verb, rows, cols, R, C, R);
-    if (first < 0 || count < 0 || first + count > s->batch)
-        return fail(TINYMPC_ERR_INVALID_INPUT, "%s: instance range [%d, %d) outside batch of %d", verb, first, first + count, s->batch);
-    const size_t per = (size_t)R * C, in_per = (size_t)R * cols;
-    if (on_device && count > 0) {  // device memory of the handle's own GPU (a host pointer or another GPU's memory is refused here)
-        hipPointerAttribute_t attr{};
-        const hipError_t e = hipPointerGetAttributes(&attr, src);
-        (void)hipGetLastError();
-        if (e != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != s->device)
-            return fail(TINYMPC_ERR_INVALID_INPUT, "%s_device: the references are not device memory of the handle's GPU %d", verb, s->device);
-    }
-    if (s->batch == 1) {  // the shared verb, pinned-host path included
-        if (count == 0) return TINYMPC_OK;
-        std::vector<double> h(per);
-        if (on_device) {
-            if ((rc = bind_device(s))) return rc;
-            if ((rc = download(s, h.data(), src, sizeof(double) * in_per))) return rc;
-            src = h.data();
-        }
-        for (size_t e = 0; e < per; ++e) h[e] = src[cols == 1 ? e % R : e];
-        return is_x ? tinympc_set_x_ref(s, h.data(), R, C, 0) : tinympc_set_u_ref(s, h.data(), R, C, 0);
-    }
-    if ((rc = bind_device(s))) return rc;
-    bool &mode = is_x ? s->iref_x : s->iref_u;
-    if (s->layout_m) {  // (no kernel carries them: the next launch refuses until the shared verb clears the mode)
-        mode = true;
-        return TINYMPC_OK;
-    }
-    double *&dst = is_x ? s->dXi : s->dUi;
-    if (!dst && (rc = dalloc(s, &dst, per * s->batch))) return rc;
-    if ((rc = alloc_inst_tables(s))) return rc;
-    if (!mode) {  // every instance starts from the shared reference of this moment
-        InstRefStoreParams b{};
-        b.src = is_x ? s->dXref : s->dUref; b.src_stride = 0; b.rows = R; b.src_cols = C; b.cols = C;
-        b.first = 0; b.count = s->batch; b.dst = dst;
-        HIP_TRY(launch_store_inst_refs(b, s->stream));
-        mode = true;
-        (is_x ? s->iref_x_goal : s->iref_u_goal) = is_x ? s->xref_const : s->uref_const;
-        s->iref_mark(0, s->batch);
-    }
-    if (count > 0) {
-        if (cols == C) {  // trajectories: the caller's layout is the handle's
-            bool goal = !on_device;  // (device input: not looked at)
-            for (int b = 0; goal && b < count; ++b) goal = rows_constant(src + (size_t)b * per, R, C);
-            if (!goal) (is_x ? s->iref_x_goal : s->iref_u_goal) = false;
-            HIP_TRY(hipMemcpyAsync(dst + (size_t)first * per, src, sizeof(double) * per * count,
-                                   on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s->stream));
-        } else {  // goals: held over the horizon on the device
-            const double *dsrc = src;
-            if (!on_device) {
-                const size_t cap = (size_t)s->batch * (s->nx > s->nu ? s->nx : s->nu);
-                if (!s->dIstage && (rc = dalloc(s, &s->dIstage, cap))) return rc;
-                HIP_TRY(hipMemcpyAsync(s->dIstage, src, sizeof(double) * in_per * count, hipMemcpyHostToDevice, s->stream));
-                dsrc = s->dIstage;
-            }
-            InstRefStoreParams b{};
-            b.src = dsrc; b.src_stride = in_per; b.rows = R; b.src_cols = 1; b.cols = C;
-            b.first = first; b.count = count; b.dst = dst;
-            HIP_TRY(launch_store_inst_refs(b, s->stream));
-        }
-        s->iref_mark(first, first + count);
-    }
-    // the caller keeps ownership of its buffer: the copies have completed when the call returns (the tinympc_set_x0_batch_device rule)
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    return TINYMPC_OK;
+    InstState &in = s->inst;
+    const InstArray a = {src, R, C, is_x ? &in.Xi : &in.Ui, is_x ? s->dXref : s->dUref, is_x ? s->xref_const : s->uref_const,
+                         is_x ? &in.x_const : &in.u_const};
+    auto shared = is_x ? +[](tinympc_solver *q, const double *const *h) { return tinympc_set_x_ref(q, h[0], q->nx, q->N, 0); }
+                       : +[](tinympc_solver *q, const double *const *h) { return tinympc_set_u_ref(q, h[0], q->nu, q->N - 1, 0); };
+    return set_inst_batch(s, verb, is_x ? "set_x_ref_batch_device" : "set_u_ref_batch_device", "references", &a, 1, is_x ? in.x : in.u,
+                          false, on_device, cols != C, first, count, shared);
 }
 
-// tinympc_set_bound_constraints_batch (+ _device): the bounds of instances [first, first+count). The handle enters per-instance mode at
-// the first call (every instance then holds the shared bounds of that moment); the clamp rows of the instances named here are rebuilt at
-// the next launch (refresh_inst_tables). Like the shared verb, the call enables both bound families. Single-instance handles: the shared verb.
+// tinympc_set_bound_constraints_batch (+ _device): one box (cols = 1) or bounds per knot (cols = N) per instance. Like the shared verb,
+// the call enables both bound families.
 int set_bounds_batch(tinympc_solver *s, const double *const src[4], bool on_device, int cols, int first, int count) {
     const char *verb = on_device ? "set_bound_constraints_batch_device" : "set_bound_constraints_batch";
     int rc = check_handle(s);
@@ -1102,97 +1152,13 @@ int set_bounds_batch(tinympc_solver *s, const double *const src[4], bool on_devi
     const int N = s->N;
     if (cols != N && cols != 1)
         return fail(TINYMPC_ERR_INVALID_INPUT, "%s: cols is %d. Expected %d (bounds per knot) or 1 (one box per instance).", verb, cols, N);
-    if (first < 0 || count < 0 || first + count > s->batch)
-        return fail(TINYMPC_ERR_INVALID_INPUT, "%s: instance range [%d, %d) outside batch of %d", verb, first, first + count, s->batch);
-    const int R[4] = {s->nx, s->nx, s->nu, s->nu}, C[4] = {N, N, N - 1, N - 1};
-    const int in_cols[4] = {cols, cols, cols == 1 ? 1 : N - 1, cols == 1 ? 1 : N - 1};
-    if (on_device && count > 0) {  // device memory of the handle's own GPU (a host pointer or another GPU's memory is refused here)
-        for (int a = 0; a < 4; ++a) {
-            hipPointerAttribute_t attr{};
-            const hipError_t e = hipPointerGetAttributes(&attr, src[a]);
-            (void)hipGetLastError();
-            if (e != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != s->device)
-                return fail(TINYMPC_ERR_INVALID_INPUT, "%s: the bounds are not device memory of the handle's GPU %d", verb, s->device);
-        }
-    }
-    if (s->batch == 1) {  // the shared verb
-        if (count == 0) return TINYMPC_OK;
-        std::vector<double> h[4];
-        if (on_device && (rc = bind_device(s))) return rc;
-        for (int a = 0; a < 4; ++a) {
-            const size_t per = (size_t)R[a] * C[a], in_per = (size_t)R[a] * in_cols[a];
-            std::vector<double> in;
-            const double *p = src[a];
-            if (on_device) {
-                in.resize(in_per);
-                if ((rc = download(s, in.data(), src[a], sizeof(double) * in_per))) return rc;
-                p = in.data();
-            }
-            h[a].resize(per);
-            for (size_t e = 0; e < per; ++e) h[a][e] = p[in_cols[a] == 1 ? e % R[a] : e];
-        }
-        return tinympc_set_bound_constraints(s, h[0].data(), h[1].data(), h[2].data(), h[3].data(), 0);
-    }
-    if ((rc = bind_device(s))) return rc;
-    if (!s->st.en_state_bound || !s->st.en_input_bound) {  // bindings.cpp:206-207
-        s->st.en_state_bound = 1;
-        s->st.en_input_bound = 1;
-        s->tables_dirty = true;  // (the shared tables follow the flags; refresh_derived then marks every instance's rows)
-    }
-    if (s->layout_m) {  // (no kernel carries them: the next launch refuses until the shared verb clears the mode)
-        s->ibnd = true;
-        return TINYMPC_OK;
-    }
-    const size_t X = (size_t)s->batch * s->X(), U = (size_t)s->batch * s->U();
-    if (!s->dBi && (rc = dalloc(s, &s->dBi, 2 * X + 2 * U))) return rc;
-    if ((rc = alloc_inst_tables(s))) return rc;
-    if (!s->dIb) {
-        if ((rc = dalloc(s, &s->dIb, inst_bnd_doubles(s->groups, N)))) return rc;
-        if ((rc = dalloc(s, &s->dIbg, (size_t)2 * s->groups * 64))) return rc;
-        HIP_TRY(hipMemsetAsync(s->dIb, 0, sizeof(double) * inst_bnd_doubles(s->groups, N), s->stream));
-        HIP_TRY(hipMemsetAsync(s->dIbg, 0, sizeof(double) * 2 * s->groups * 64, s->stream));
-    }
-    double *dst[4] = {s->dBi, s->dBi + X, s->dBi + 2 * X, s->dBi + 2 * X + U};
-    const double *shared[4] = {s->dxmin, s->dxmax, s->dumin, s->dumax};
-    if (!s->ibnd) {  // every instance starts from the shared bounds of this moment
-        for (int a = 0; a < 4; ++a) {
-            InstRefStoreParams b{};
-            b.src = shared[a]; b.src_stride = 0; b.rows = R[a]; b.src_cols = C[a]; b.cols = C[a];
-            b.first = 0; b.count = s->batch; b.dst = dst[a];
-            HIP_TRY(launch_store_inst_refs(b, s->stream));
-        }
-        s->ibnd = true;
-        s->ibnd_const = s->xmin_const && s->xmax_const && s->umin_const && s->umax_const;
-        s->iref_mark(0, s->batch);
-    }
-    if (count > 0) {
-        for (int a = 0; a < 4; ++a) {
-            const size_t per = (size_t)R[a] * C[a], in_per = (size_t)R[a] * in_cols[a];
-            if (cols == N) {  // per knot: the caller's layout is the handle's
-                bool constant = !on_device;  // (device input: not looked at)
-                for (int b = 0; constant && b < count; ++b) constant = rows_constant(src[a] + (size_t)b * per, R[a], C[a]);
-                if (!constant) s->ibnd_const = false;
-                HIP_TRY(hipMemcpyAsync(dst[a] + (size_t)first * per, src[a], sizeof(double) * per * count,
-                                       on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s->stream));
-            } else {  // one box: held over the horizon on the device
-                const double *dsrc = src[a];
-                if (!on_device) {
-                    const size_t cap = (size_t)s->batch * (s->nx > s->nu ? s->nx : s->nu);
-                    if (!s->dIstage && (rc = dalloc(s, &s->dIstage, cap))) return rc;
-                    HIP_TRY(hipMemcpyAsync(s->dIstage, src[a], sizeof(double) * in_per * count, hipMemcpyHostToDevice, s->stream));
-                    dsrc = s->dIstage;
-                }
-                InstRefStoreParams b{};
-                b.src = dsrc; b.src_stride = in_per; b.rows = R[a]; b.src_cols = 1; b.cols = C[a];
-                b.first = first; b.count = count; b.dst = dst[a];
-                HIP_TRY(launch_store_inst_refs(b, s->stream));
-            }
-        }
-        s->iref_mark(first, first + count);
-    }
-    // the caller keeps ownership of its buffers: the copies have completed when the call returns (the tinympc_set_x0_batch_device rule)
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    return TINYMPC_OK;
+    InstState &in = s->inst;
+    const InstArray a[4] = {{src[0], s->nx, N, &in.xmin, s->dxmin, s->xmin_const, &in.bounds_const},
+                            {src[1], s->nx, N, &in.xmax, s->dxmax, s->xmax_const, &in.bounds_const},
+                            {src[2], s->nu, N - 1, &in.umin, s->dumin, s->umin_const, &in.bounds_const},
+                            {src[3], s->nu, N - 1, &in.umax, s->dumax, s->umax_const, &in.bounds_const}};
+    auto shared = +[](tinympc_solver *q, const double *const *h) { return tinympc_set_bound_constraints(q, h[0], h[1], h[2], h[3], 0); };
+    return set_inst_batch(s, verb, verb, "bounds", a, 4, in.bounds, true, on_device, cols != N, first, count, shared);
 }
 
 }  // namespace

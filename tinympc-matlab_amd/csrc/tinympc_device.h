@@ -233,17 +233,18 @@ struct SolveParams {
     // Per-instance references (tinympc_set_x_ref_batch / _u_ref_batch; layout A's InstRefs variant, which reads neither ctab nor ftab): the
     // reference-dependent table rows of every instance, in the solve kernel's lane order (k_build_inst_tables) -- iref_lr
     // [groups][N+2][64] (row k+1 = knot k, the same padding rows as the shared tables), iref_pn [groups][64] = [instance][W].
-    // Layout D's goal form (k_admm_solve_d_goal): iref_lr is knot 0's linref, [instance][16]. NULL otherwise.
+    // Layout D's goal form (k_admm_solve_d_gbnd, -DTINY_JIT_IGOAL=1): iref_lr is knot 0's linref, [instance][W]. NULL otherwise.
     union { const double *ftab; const double *iref_pn; };
-    // Per-instance bounds (tinympc_set_bound_constraints_batch; always together with iref_lr / iref_pn, which then hold every instance's
-    // rows whether its references are its own or the shared ones): ibnd (in the mail slot above) holds every instance's clamp rows, built
-    // by k_build_inst_bounds with k_build_tables' expressions. Layout A's InstBounds variant: lo [groups][N+2][64] | hi [groups][N+2][64]
-    // (row k+1 = knot k, hi at inst_bnd_hi_offset()), followed by INST_LR_PAD padding rows (the forward sweep reads that many knots
-    // ahead). Layout D's goal form with bounds: knot 0's rows lo [instance][W] | hi [instance][W], hi at groups*64.
+    // Per-instance clamp rows (ibnd, in the mail slot above), built by k_build_inst_tables with k_build_tables' expressions -- from every
+    // instance's own bounds (tinympc_set_bound_constraints_batch) or from the shared ones. Layout A's InstBounds variant (per-instance
+    // bounds only): lo [groups][N+2][64] | hi [groups][N+2][64] (row k+1 = knot k, hi at inst_bnd_hi_offset()), followed by INST_LR_PAD
+    // padding rows (the forward sweep reads that many knots ahead). Layout D's goal form (always): knot 0's rows lo [instance][W] |
+    // hi [instance][W], hi at groups*64.
 };
 
-// Per-instance references of a batched handle (k_store_inst_refs, k_build_inst_tables; tinympc_kernels.hip). The references of instance b
-// are column-major nx x N / nu x (N-1) blocks at b*nx*N / b*nu*(N-1); the table rows are laid out as SolveParams::iref_lr / iref_pn say.
+// Per-instance references and bounds of a batched handle (k_store_inst_refs, k_build_inst_tables; tinympc_kernels.hip). The references
+// of instance b are column-major nx x N / nu x (N-1) blocks at b*nx*N / b*nu*(N-1), its bounds the same per array; the table rows are laid
+// out as SolveParams::iref_lr / iref_pn / ibnd say.
 // (iref_lr points INST_LR_PAD rows into its block: layout A prefetches the rows of the backward sweep that many knots ahead)
 constexpr int INST_LR_PAD = 4;
 __host__ __device__ inline size_t inst_lr_doubles(int groups, int N) { return ((size_t)groups * table_rows(N) + INST_LR_PAD) * 64; }
@@ -257,24 +258,20 @@ struct InstRefStoreParams {
     double *dst;        // [batch][cols][rows]
 };
 struct InstTableParams {
-    int nx, nu, N, W, KT;
+    int nx, nu, N, W, KT, groups;
+    int en_state_bound, en_input_bound;
     int first, count;                 // instances whose rows are rebuilt
     const double *Xi, *Ui;            // per-instance references, or NULL: that half is the shared one
     const double *Xref, *Uref, *Pinf;  // shared references, Pinf for pNref
     const double *ops;                // for dg[]
-    double *lr, *pn;                  // rows (layout A), pNref [instance][W]
-    double *lrg;                      // knot 0's linref [instance][W] (layout D's goal form: the references are constant over the horizon)
-};
-// Per-instance bounds: every instance's x_min | x_max | u_min | u_max, each [batch][cols][rows] column-major (InstRefStoreParams::dst
-// layout), into the clamp rows of SolveParams::ibnd for instances [first, first+count). The enable flags act as in k_build_tables.
-struct InstBoundParams {
-    int nx, nu, N, W;
-    int en_state_bound, en_input_bound;
-    int first, count;
-    const double *x_min, *x_max, *u_min, *u_max;  // [batch][N][nx] / [batch][N-1][nu]
-    double *rows;                                 // layout A's lo | hi rows (inst_bnd_doubles)
-    double *knot0;                                // layout D's goal form: knot 0's lo [instance][W] | hi at +groups*64
-    int groups;
+    // bounds: the per-instance store (x_min | x_max | u_min | u_max, each [batch][N][nx] / [batch][N-1][nu]; bnd_inst = 1) or the
+    // shared bounds (bnd_inst = 0: instance stride 0). The enable flags act as in k_build_tables.
+    const double *x_min, *x_max, *u_min, *u_max;
+    int bnd_inst;
+    double *lr, *pn;                  // linref rows (layout A), pNref [instance][W]
+    double *lrg;                      // knot 0's linref [instance][W] (layout D's goal form)
+    double *bndg;                     // knot 0's lo [instance][W] | hi at +groups*64 (layout D's goal form)
+    double *bnd;                      // layout A's lo | hi rows (inst_bnd_doubles; per-instance bounds only), or NULL
 };
 
 struct ChunkTableParams {
@@ -390,7 +387,7 @@ bool solve_jit_enabled();  // TINYMPC_JIT is not 0
 bool solve_e_supported(int nx, int nu, int N, bool const_tables, bool families, const FamilyStructure &fs);  // plans AND compiles
 hipError_t launch_solve_e(const SolveParams &p, const FamilyStructure &fs, hipStream_t stream);
 void solve_e_describe(int nx, int nu, int N, bool const_tables, bool families, const FamilyStructure &fs, char *buf, size_t len);
-void solve_jit_describe(int W, int nx, int nu, int N, bool const_tables, bool families, bool adaptive, char *buf, size_t len, int goal = 0);
+void solve_jit_describe(int W, int nx, int nu, int N, bool const_tables, bool families, bool adaptive, char *buf, size_t len, bool goal = false);
 // Layout F (tinympc_solve_f.hip, run-time specialised only): the latency kernel with compile-time shape and structure
 bool solve_f_plan(int nx, int nu, int N, bool const_tables, bool families, const FamilyStructure &fs, int *chunk_len, int *chunks, int *wpg, size_t *lds_bytes);
 bool solve_f_supported(int nx, int nu, int N, bool const_tables, bool families, const FamilyStructure &fs);  // plans AND compiles
@@ -433,7 +430,6 @@ hipError_t launch_build_operators(const OperatorParams &p, hipStream_t stream);
 hipError_t launch_build_tables(const TableParams &p, hipStream_t stream);
 hipError_t launch_store_inst_refs(const InstRefStoreParams &p, hipStream_t stream);
 hipError_t launch_build_inst_tables(const InstTableParams &p, hipStream_t stream);
-hipError_t launch_build_inst_bounds(const InstBoundParams &p, hipStream_t stream);
 // Layout A: one wavefront per workgroup, all ADMM state in LDS (lowest latency, 2 waves per CU). One kernel body, three
 // variants: the box path (k_admm_solve), plus the cone / linear slack families (k_admm_solve_fam: extra duals and the extra
 // linear-cost term in HBM), plus adaptive rho (k_admm_solve_adapt: per-instance rho, Taylor-updated operators; needs
@@ -508,13 +504,13 @@ int solve_m_fam_fast_rows();  // up to this many linear rows per side the descri
 hipError_t launch_solve_m(const SolveParams &p, hipStream_t stream);
 // Run-time specialisation of layout D (tinympc_jit.hip): any (nx, nu, N) that fits the register / LDS plan, compiled with
 // hiprtc from the very sources of the compiled-in instantiations on first use and cached (memory + disk).
-// goal: the per-instance goal form (-DTINY_JIT_IGOAL=1; constant tables, box path); 2: with per-instance bounds too (-DTINY_JIT_IBND=1)
-bool solve_jit_supported(int W, int nx, int nu, int N, bool const_tables, bool families = false, bool adaptive = false, int goal = 0);
+// goal: the per-instance goal form (-DTINY_JIT_IGOAL=1; constant tables, box path)
+bool solve_jit_supported(int W, int nx, int nu, int N, bool const_tables, bool families = false, bool adaptive = false, bool goal = false);
 hipError_t launch_solve_jit(const SolveParams &p, int W, hipStream_t stream);
 bool solve_jit_refill_supported(int W, int nx, int nu, int N, bool const_tables);   // (compiles the slot-refill variant on first use)
 int solve_jit_resident_wavefronts(int W, int nx, int nu, int N, bool const_tables);  // wavefronts of the shape's plan the device holds at once
-int solve_jit_workgroups(int W, int nx, int nu, int N, bool const_tables, int groups, bool families = false, bool adaptive = false, int goal = 0);
-size_t solve_jit_lds_bytes(int W, int nx, int nu, int N, bool const_tables, bool families = false, bool adaptive = false, int goal = 0);  // per workgroup, from the plan  // 8 wavefronts per workgroup, 4 on the long-horizon plan
+int solve_jit_workgroups(int W, int nx, int nu, int N, bool const_tables, int groups, bool families = false, bool adaptive = false, bool goal = false);
+size_t solve_jit_lds_bytes(int W, int nx, int nu, int N, bool const_tables, bool families = false, bool adaptive = false, bool goal = false);  // per workgroup, from the plan  // 8 wavefronts per workgroup, 4 on the long-horizon plan
 #endif  // !__HIPCC_RTC__
 
 // Doubles of working state per group in layout A (G and V with N+2 rows, D with 64 dummy slots).

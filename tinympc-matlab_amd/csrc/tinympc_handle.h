@@ -50,6 +50,33 @@ constexpr int kLayoutCBatchMax = 768;  // above this the batch-oriented layouts 
 
 }  // namespace tinympc
 
+// Per-instance references and bounds of a batched handle. Each mode -- the x half of the references, the u half, the bounds -- is on from
+// its first per-instance verb until the shared verb (tinympc_set_x_ref / _set_u_ref / _set_bound_constraints); instances the verbs did
+// not name hold the shared value of the moment the mode began. The rows the solve kernels read (SolveParams::iref_lr / iref_pn / ibnd)
+// are rebuilt at the next launch for the instances in [dirty_lo, dirty_hi) -- all of them when the shared tables were rebuilt (new
+// references, bounds or cache). One interval: two small updates far apart rebuild the instances between them too (a rebuild is one
+// element-wise kernel over the interval). A mode's rows hold the shared values where it is off.
+struct InstState {
+    bool x = false, u = false, bounds = false;
+    // ... every instance's value of that mode is constant over the horizon. Sticky until the mode ends: a trajectory that is later
+    // replaced by goals keeps the handle on layout A (nothing looks at the whole batch's data again)
+    bool x_const = false, u_const = false, bounds_const = false;
+    int d_goal = -1;  // the run-time specialised goal kernel (16 lanes beyond the compiled-in shapes, 32 / 64 lanes): -1 not asked yet, 0 no, 1 yes
+    // every instance's value, column-major [batch] blocks of nx x N (Xi, xmin, xmax) / nu x (N-1) (Ui, umin, umax)
+    double *Xi = nullptr, *Ui = nullptr, *xmin = nullptr, *xmax = nullptr, *umin = nullptr, *umax = nullptr;
+    double *lr = nullptr, *pn = nullptr;     // linref rows (inst_lr_doubles), pNref [instance][W]
+    double *lrg = nullptr, *bndg = nullptr;  // knot 0's linref [instance][W] and lo | hi rows (layout D's goal form)
+    double *bnd = nullptr;                   // layout A's lo | hi rows (inst_bnd_doubles; bounds mode)
+    double *stage = nullptr;                 // device staging of one-column host input
+    int dirty_lo = 0, dirty_hi = 0;
+    bool refs() const { return x || u; }
+    const double *lr_rows() const { return lr + (size_t)tinympc::INST_LR_PAD * 64; }  // SolveParams::iref_lr on layout A
+    void mark(int lo, int hi) {
+        if (dirty_lo >= dirty_hi) { dirty_lo = lo; dirty_hi = hi; }
+        else { dirty_lo = lo < dirty_lo ? lo : dirty_lo; dirty_hi = hi > dirty_hi ? hi : dirty_hi; }
+    }
+};
+
 struct tinympc_solver {
     int nx = 0, nu = 0, N = 0, batch = 0, device = 0;
     int W = 0, KT = 0, IPW = 0, groups = 0;
@@ -185,40 +212,14 @@ struct tinympc_solver {
     bool state_in_global = false;             // horizon too long for LDS: layout-A kernels work on dscratch
     double *dscratch_state = nullptr;
     bool fam_dirty = true;
-    // Per-instance references (tinympc_set_x_ref_batch / _u_ref_batch; batched handles). Each half (x, u) is in per-instance mode from its
-    // first per-instance verb until the next tinympc_set_x_ref / _set_u_ref; instances the verbs did not name hold the shared reference
-    // of the moment the mode began. dXi / dUi: every instance's reference, column-major nx x N / nu x (N-1) blocks; dIlr / dIpn: the
-    // table rows the solve kernel reads (SolveParams::iref_lr / iref_pn), rebuilt at the next launch for the instances in
-    // [iref_dirty_lo, iref_dirty_hi) -- all of them when the shared tables were rebuilt (new references, bounds or cache). One interval:
-    // two small updates far apart rebuild the instances between them too (a rebuild is one element-wise kernel over the interval).
-    // Goal form (every instance's references constant over the horizon, bounds too): layout D's constant-table kernel carries it
-    // (k_admm_solve_d_goal, compiled-in 16-lane shapes) with knot 0's linref per instance in dIgoal; everything else runs on layout A.
-    bool iref_x = false, iref_u = false;
-    // ... every per-instance reference of that half is constant over the horizon. Sticky until the half returns to shared mode: a
-    // trajectory that is later replaced by goals keeps the handle on layout A (nothing looks at the whole batch's data again)
-    bool iref_x_goal = false, iref_u_goal = false;
-    int d_goal = -1;  // the run-time specialised goal kernel (16 lanes beyond the compiled-in shapes, 32 / 64 lanes): -1 not asked yet, 0 no, 1 yes
-    bool iref() const { return iref_x || iref_u; }
+    // Per-instance references and bounds (tinympc_set_x_ref_batch / _u_ref_batch / _bound_constraints_batch; batched handles): InstState.
+    InstState inst;
+    bool inst_tables() const { return inst.refs() || inst.bounds; }  // the per-instance table rows are in use
+    // Goal form (every instance's references AND bounds constant over the horizon): layout D's constant-table kernel carries it, with
+    // knot 0's rows per instance; everything else runs on layout A.
     bool iref_goal() const {
-        return (iref_x ? iref_x_goal : xref_const) && (iref_u ? iref_u_goal : uref_const) &&
-               (ibnd ? ibnd_const : xmin_const && xmax_const && umin_const && umax_const);
-    }
-    // Per-instance bounds (tinympc_set_bound_constraints_batch; batched handles): in per-instance mode from the first call until the next
-    // tinympc_set_bound_constraints; instances the verb did not name hold the shared bounds of the moment the mode began. dBi: every
-    // instance's x_min | x_max | u_min | u_max, each [batch] column-major nx x N / nu x (N-1) blocks; dIb / dIbg: the clamp rows the solve
-    // kernels read (SolveParams::ibnd: layout A's rows, layout D's knot 0), rebuilt with the reference rows (the same dirty interval).
-    // The mode always runs on the per-instance reference rows as well (dIlr / dIpn / dIgoal, with the shared references where a half is
-    // shared). ibnd_const: every instance's bounds are constant over the horizon (sticky, as iref_x_goal): the goal form on layout D.
-    bool ibnd = false, ibnd_const = false;
-    int d_gbnd = -1;  // the run-time specialised goal kernel with per-instance bounds: -1 not asked yet, 0 no, 1 yes
-    double *dBi = nullptr, *dIb = nullptr, *dIbg = nullptr;
-    bool inst_tables() const { return iref() || ibnd; }  // the per-instance table rows are in use
-    double *dXi = nullptr, *dUi = nullptr, *dIlr = nullptr, *dIpn = nullptr, *dIgoal = nullptr, *dIstage = nullptr;
-    const double *iref_rows() const { return dIlr + (size_t)tinympc::INST_LR_PAD * 64; }  // SolveParams::iref_lr on layout A
-    int iref_dirty_lo = 0, iref_dirty_hi = 0;
-    void iref_mark(int lo, int hi) {
-        if (iref_dirty_lo >= iref_dirty_hi) { iref_dirty_lo = lo; iref_dirty_hi = hi; }
-        else { iref_dirty_lo = lo < iref_dirty_lo ? lo : iref_dirty_lo; iref_dirty_hi = hi > iref_dirty_hi ? hi : iref_dirty_hi; }
+        return (inst.x ? inst.x_const : xref_const) && (inst.u ? inst.u_const : uref_const) &&
+               (inst.bounds ? inst.bounds_const : xmin_const && xmax_const && umin_const && umax_const);
     }
     size_t lds_bytes_a = 0;       // layout-A LDS plan (layout B, where it runs, replaces lds_bytes; the families and adaptive rho always use layout A)
     bool tables_in_lds_a = false;
@@ -303,7 +304,7 @@ int flush_host_refs(tinympc_solver *s);
 int refresh_derived(tinympc_solver *s);
 FamilyStructure family_structure(const tinympc_solver *s, double *mu = nullptr);
 int refresh_families(tinympc_solver *s);
-int refresh_inst_tables(tinympc_solver *s);  // the per-instance table rows of the instances whose references changed
+int refresh_inst_tables(tinympc_solver *s);  // the per-instance table rows of the instances whose references / bounds changed
 void destroy(tinympc_solver *s);
 
 // ---- tinympc_plan.hip: the kernel of a launch, decided in ONE place
@@ -313,7 +314,7 @@ struct LaunchPlan {
     char layout = 'A';                       // what tinympc_get_layout reports
     bool families = false, adaptive = false;  // variant bits of the launch
     bool inst_refs = false;                  // ... per-instance references (layout A's InstRefs variant) or bounds (see inst_bounds)
-    bool inst_bounds = false;                // ... per-instance bounds (layout A's InstBounds variant, layout D's goal form with bounds)
+    bool inst_bounds = false;                // ... per-instance bounds (layout A's InstBounds variant)
     bool jit = false;                        // a run-time specialisation (tinympc_jit.hip) rather than a compiled-in kernel
     bool host_exchange = false;              // the kernel serves the pinned-host paths (x0 in, solution / completion stamp out)
     int workgroups = 0;

@@ -313,31 +313,27 @@ int refresh_derived(tinympc_solver *s) {
         p.Xref = s->dXref; p.Uref = s->dUref; p.Pinf = s->dPinf; p.ops = s->dops; p.tables = s->dtables;
         HIP_TRY(launch_build_tables(p, s->stream));
         s->tables_dirty = false;
-        if (s->inst_tables()) s->iref_mark(0, s->batch);  // (the per-instance rows use the same shared inputs: dg, Pinf, the shared half, the enable flags)
+        if (s->inst_tables()) s->inst.mark(0, s->batch);  // (the per-instance rows use the same shared inputs: dg, Pinf, the shared half, the enable flags)
     }
     return TINYMPC_OK;
 }
 
 int refresh_inst_tables(tinympc_solver *s) {
-    if (!s->inst_tables() || !s->dIlr || s->iref_dirty_lo >= s->iref_dirty_hi) return TINYMPC_OK;
+    InstState &in = s->inst;
+    if (!s->inst_tables() || !in.lr || in.dirty_lo >= in.dirty_hi) return TINYMPC_OK;
     InstTableParams p{};
-    p.nx = s->nx; p.nu = s->nu; p.N = s->N; p.W = s->W; p.KT = s->KT;
-    p.first = s->iref_dirty_lo; p.count = s->iref_dirty_hi - s->iref_dirty_lo;
-    p.Xi = s->iref_x ? s->dXi : nullptr; p.Ui = s->iref_u ? s->dUi : nullptr;
+    p.nx = s->nx; p.nu = s->nu; p.N = s->N; p.W = s->W; p.KT = s->KT; p.groups = s->groups;
+    p.en_state_bound = s->st.en_state_bound; p.en_input_bound = s->st.en_input_bound;
+    p.first = in.dirty_lo; p.count = in.dirty_hi - in.dirty_lo;
+    p.Xi = in.x ? in.Xi : nullptr; p.Ui = in.u ? in.Ui : nullptr;
     p.Xref = s->dXref; p.Uref = s->dUref; p.Pinf = s->dPinf; p.ops = s->dops;
-    p.lr = const_cast<double *>(s->iref_rows()); p.pn = s->dIpn; p.lrg = s->dIgoal;
+    p.bnd_inst = in.bounds;
+    p.x_min = in.bounds ? in.xmin : s->dxmin; p.x_max = in.bounds ? in.xmax : s->dxmax;
+    p.u_min = in.bounds ? in.umin : s->dumin; p.u_max = in.bounds ? in.umax : s->dumax;
+    p.lr = const_cast<double *>(in.lr_rows()); p.pn = in.pn; p.lrg = in.lrg; p.bndg = in.bndg;
+    p.bnd = in.bounds ? in.bnd : nullptr;
     HIP_TRY(launch_build_inst_tables(p, s->stream));
-    if (s->ibnd && s->dIb) {
-        InstBoundParams b{};
-        b.nx = s->nx; b.nu = s->nu; b.N = s->N; b.W = s->W; b.groups = s->groups;
-        b.en_state_bound = s->st.en_state_bound; b.en_input_bound = s->st.en_input_bound;
-        b.first = p.first; b.count = p.count;
-        const size_t X = (size_t)s->batch * s->X(), U = (size_t)s->batch * s->U();
-        b.x_min = s->dBi; b.x_max = s->dBi + X; b.u_min = s->dBi + 2 * X; b.u_max = s->dBi + 2 * X + U;
-        b.rows = s->dIb; b.knot0 = s->dIbg;
-        HIP_TRY(launch_build_inst_bounds(b, s->stream));
-    }
-    s->iref_dirty_lo = s->iref_dirty_hi = 0;
+    in.dirty_lo = in.dirty_hi = 0;
     return TINYMPC_OK;
 }
 

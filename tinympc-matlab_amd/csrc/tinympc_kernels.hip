@@ -3,7 +3,7 @@
 //   k_precompute        P1  tiny_precompute_and_set_cache         (reference tiny_api.cpp:124-190)
 //   k_build_operators       fuses the cache into the two 1-step sweep operators used by the solve
 //   k_build_tables          per-knot clamp bounds / linear-cost reference terms
-//   k_build_inst_tables / k_build_inst_bounds   the same rows per instance (per-instance references / bounds of a batched handle)
+//   k_build_inst_tables     the same rows per instance (per-instance references / bounds of a batched handle)
 //   k_build_adapt           adaptive rho: the sensitivity rows of the sweep operators and [A'; B']
 //
 // The solve kernel itself (M1: F1, S1, D1, L1, R1, C1, B1) is in tinympc_solve.hip.
@@ -596,14 +596,18 @@ hipError_t launch_store_inst_refs(const InstRefStoreParams &p, hipStream_t strea
     return hipGetLastError();
 }
 
-// The reference-dependent table rows of instances [first, first+count), in the lane order of layout A's solve kernel: lane j*W + r of
-// wavefront g is row r of instance g*(64/W) + j. The expressions and the order of the pNref sum are k_build_tables' (an instance whose
-// references equal the shared ones gets bit-identical values); padding rows and lanes are zero.
+// The table rows of instances [first, first+count), in the lane order of layout A's solve kernel: lane j*W + r of wavefront g is row r
+// of instance g*(64/W) + j. The expressions and the order of the pNref sum are k_build_tables' (an instance whose references and bounds
+// equal the shared ones gets bit-identical values; a disabled bound family is -inf / +inf for every instance); padding rows and lanes of
+// the linref rows are zero. Knot 0's linref and clamp rows also go to lrg / bndg (layout D's goal form); layout A's clamp rows only
+// where bnd is set.
 __global__ void __launch_bounds__(256) k_build_inst_tables(const InstTableParams p) {
     const int nx = p.nx, nu = p.nu, N = p.N, W = p.W, nxu = nx + nu, TR = N + 2;
     const size_t X = (size_t)nx * N, U = (size_t)nu * (N - 1);
     const double *dg = p.ops + (size_t)2 * W * p.KT + 2 * W;
-    const size_t per = (size_t)(TR + 1) * W;  // TR linref rows + the pNref row, W lanes each
+    const double inf = __longlong_as_double(0x7FF0000000000000LL);
+    const size_t bhi = inst_bnd_hi_offset(p.groups, N);
+    const size_t per = (size_t)(TR + 1) * W;  // TR table rows + the pNref row, W lanes each
     const size_t total = per * p.count;
     for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
         const long inst = p.first + (long)(idx / per);
@@ -620,17 +624,36 @@ __global__ void __launch_bounds__(256) k_build_inst_tables(const InstTableParams
             }
             p.pn[(size_t)grp * 64 + lane] = acc;
         } else {
+            const size_t bx = p.bnd_inst ? inst * X : 0, bu = p.bnd_inst ? inst * U : 0;
             const int kn = row - 1;
-            double ref = 0.0;
+            double ref = 0.0, l = -inf, h = inf;
             if (kn < 0 || kn >= N) {
                 // padding row
             } else if (r < nx) {
+                if (p.en_state_bound) {
+                    l = p.x_min[bx + r + (size_t)kn * nx];
+                    h = p.x_max[bx + r + (size_t)kn * nx];
+                }
                 ref = -(Xr[r + (size_t)kn * nx] * dg[r]);  // admm.cpp:79
             } else if (r < nxu && kn < N - 1) {
-                ref = -(Ur[(r - nx) + (size_t)kn * nu] * dg[r]);  // admm.cpp:77
+                const int j = r - nx;
+                if (p.en_input_bound) {
+                    l = p.u_min[bu + j + (size_t)kn * nu];
+                    h = p.u_max[bu + j + (size_t)kn * nu];
+                }
+                ref = -(Ur[j + (size_t)kn * nu] * dg[r]);  // admm.cpp:77
             }
-            p.lr[((size_t)grp * TR + row) * 64 + lane] = ref;
-            if (row == 1) p.lrg[(size_t)grp * 64 + lane] = ref;
+            const size_t o = ((size_t)grp * TR + row) * 64 + lane;
+            p.lr[o] = ref;
+            if (p.bnd) {
+                p.bnd[o] = l;
+                p.bnd[bhi + o] = h;
+            }
+            if (row == 1) {
+                p.lrg[(size_t)grp * 64 + lane] = ref;
+                p.bndg[(size_t)grp * 64 + lane] = l;
+                p.bndg[(size_t)p.groups * 64 + (size_t)grp * 64 + lane] = h;
+            }
         }
     }
 }
@@ -640,52 +663,6 @@ hipError_t launch_build_inst_tables(const InstTableParams &p, hipStream_t stream
     if (total == 0) return hipSuccess;
     const size_t blocks = (total + 255) / 256;
     hipLaunchKernelGGL(k_build_inst_tables, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, stream, p);
-    return hipGetLastError();
-}
-
-// Per-instance bounds: the clamp rows of instances [first, first+count), in the same lane order (lane j*W + r of group g is row r of
-// instance g*(64/W) + j) and with k_build_tables' expressions -- an instance whose bounds equal the shared ones gets bit-identical rows;
-// a disabled family is -inf / +inf for every instance. Knot 0's rows also go to knot0 (layout D's goal form).
-__global__ void __launch_bounds__(256) k_build_inst_bounds(const InstBoundParams p) {
-    const int nx = p.nx, nu = p.nu, N = p.N, W = p.W, nxu = nx + nu, TR = N + 2;
-    const size_t X = (size_t)nx * N, U = (size_t)nu * (N - 1);
-    const size_t per = (size_t)TR * W, total = per * p.count, bhi = inst_bnd_hi_offset(p.groups, N);
-    const double inf = __longlong_as_double(0x7FF0000000000000LL);
-    for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
-        const long inst = p.first + (long)(idx / per);
-        const int e = (int)(idx % per), row = e / W, r = e % W, kn = row - 1;
-        const long grp = inst / (64 / W);
-        const int lane = (int)(inst % (64 / W)) * W + r;
-        double l = -inf, h = inf;
-        if (kn < 0 || kn >= N) {
-            // padding row
-        } else if (r < nx) {
-            if (p.en_state_bound) {
-                l = p.x_min[inst * X + r + (size_t)kn * nx];
-                h = p.x_max[inst * X + r + (size_t)kn * nx];
-            }
-        } else if (r < nxu && kn < N - 1) {
-            const int j = r - nx;
-            if (p.en_input_bound) {
-                l = p.u_min[inst * U + j + (size_t)kn * nu];
-                h = p.u_max[inst * U + j + (size_t)kn * nu];
-            }
-        }
-        const size_t o = ((size_t)grp * TR + row) * 64 + lane;
-        p.rows[o] = l;
-        p.rows[bhi + o] = h;
-        if (row == 1) {
-            p.knot0[(size_t)grp * 64 + lane] = l;
-            p.knot0[(size_t)p.groups * 64 + (size_t)grp * 64 + lane] = h;
-        }
-    }
-}
-
-hipError_t launch_build_inst_bounds(const InstBoundParams &p, hipStream_t stream) {
-    const size_t total = (size_t)(p.N + 2) * p.W * p.count;
-    if (total == 0) return hipSuccess;
-    const size_t blocks = (total + 255) / 256;
-    hipLaunchKernelGGL(k_build_inst_bounds, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, stream, p);
     return hipGetLastError();
 }
 

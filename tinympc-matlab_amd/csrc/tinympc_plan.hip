@@ -171,13 +171,13 @@ LaunchPlan current_plan(const tinympc_solver *s) {
     pl.adaptive = adaptive;
     if (s->inst_tables() && !s->layout_m && !fam && !adaptive) {
         // goals, where the handle runs layout D: its constant-table kernel (compiled in for the 16-lane shapes that are, run-time
-        // specialised otherwise -- wide systems included); trajectories, and goals without such a kernel: layout A. Per-instance
-        // bounds: the same, with "goal" meaning that references AND bounds are constant over the horizon
+        // specialised otherwise -- wide systems included); trajectories, and goals without such a kernel: layout A. "Goal" means that
+        // references AND bounds are constant over the horizon, each per instance or shared
         const bool goal = s->layout_d && s->iref_goal();
         pl.kernel = (goal && !s->d_jit && s->W == 16 && solve_d_supported(s->nx, s->nu, s->N, true)) ? KernelId::D_COMPILED
-                    : (goal && (s->ibnd ? s->d_gbnd : s->d_goal) == 1) ? KernelId::D_JIT : KernelId::A;
+                    : (goal && s->inst.d_goal == 1) ? KernelId::D_JIT : KernelId::A;
         pl.inst_refs = true;
-        pl.inst_bounds = s->ibnd;
+        pl.inst_bounds = s->inst.bounds;
     } else if (s->layout_m) pl.kernel = KernelId::M;
     else if (adaptive) pl.kernel = d ? KernelId::D_JIT : KernelId::ADAPT_A;
     else if (fam)
@@ -188,7 +188,6 @@ LaunchPlan current_plan(const tinympc_solver *s) {
                     : s->use_layout_f() ? KernelId::F : s->layout_c ? KernelId::C : s->layout_b ? KernelId::B : KernelId::A;
     const bool d_goal = pl.inst_refs && (pl.kernel == KernelId::D_COMPILED || pl.kernel == KernelId::D_JIT);
     const bool ct = s->tables_const() || d_goal;  // (the goal form: constant tables)
-    const int jgoal = pl.inst_refs ? (pl.inst_bounds ? 2 : 1) : 0;  // (the run-time specialisation's goal form, see solve_jit_supported)
     switch (pl.kernel) {
         case KernelId::M:
             pl.layout = 'M';
@@ -198,8 +197,8 @@ LaunchPlan current_plan(const tinympc_solver *s) {
         case KernelId::D_JIT:
             pl.layout = 'D';
             pl.jit = true;
-            pl.workgroups = solve_jit_workgroups(s->W, s->nx, s->nu, s->N, ct, s->groups, fam, adaptive, jgoal);
-            pl.lds_bytes = solve_jit_lds_bytes(s->W, s->nx, s->nu, s->N, ct, fam, adaptive, jgoal);
+            pl.workgroups = solve_jit_workgroups(s->W, s->nx, s->nu, s->N, ct, s->groups, fam, adaptive, pl.inst_refs);
+            pl.lds_bytes = solve_jit_lds_bytes(s->W, s->nx, s->nu, s->N, ct, fam, adaptive, pl.inst_refs);
             break;
         case KernelId::D_COMPILED:
             pl.layout = 'D';
@@ -250,10 +249,10 @@ LaunchPlan current_plan(const tinympc_solver *s) {
 int resolve_plan(tinympc_solver *s) {
     int rc;
     if (s->inst_tables()) {  // layout A or D's goal form, or a refusal: only the goal form's specialisation to decide
-        int &known = s->ibnd ? s->d_gbnd : s->d_goal;
+        int &known = s->inst.d_goal;
         if (known < 0 && s->layout_d && s->iref_goal() && !(s->W == 16 && !s->d_jit && solve_d_supported(s->nx, s->nu, s->N, true)) &&
             !s->families_active() && !s->st.adaptive_rho)
-            known = solve_jit_supported(s->W, s->nx, s->nu, s->N, true, false, false, s->ibnd ? 2 : 1) ? 1 : 0;
+            known = solve_jit_supported(s->W, s->nx, s->nu, s->N, true, false, false, true) ? 1 : 0;
         return TINYMPC_OK;
     }
     decide_layout_d_variants(s);
@@ -293,14 +292,14 @@ int launch(tinympc_solver *s, bool timed) {
     if ((rc = resolve_plan(s))) return rc;
     const LaunchPlan pl = current_plan(s);
     const bool fam = pl.families, adaptive = pl.adaptive;
-    if (s->iref() && !pl.inst_refs)  // never a solve with the shared references in their place
-        return fail(TINYMPC_ERR_UNSUPPORTED, "per-instance references (set_x_ref_batch / set_u_ref_batch) are not supported %s; "
-                    "tinympc_set_x_ref / tinympc_set_u_ref return to shared references",
-                    s->layout_m ? "for systems with nx+nu > 64" : fam ? "with cone / linear constraint families" : "with adaptive rho");
-    if (s->ibnd && !pl.inst_refs)  // never a solve with the shared bounds in their place
-        return fail(TINYMPC_ERR_UNSUPPORTED, "per-instance bounds (set_bound_constraints_batch) are not supported %s; "
-                    "tinympc_set_bound_constraints returns to shared bounds",
-                    s->layout_m ? "for systems with nx+nu > 64" : fam ? "with cone / linear constraint families" : "with adaptive rho");
+    if (s->inst_tables() && !pl.inst_refs) {  // never a solve with the shared references / bounds in their place
+        const bool r = s->inst.refs(), b = s->inst.bounds;
+        return fail(TINYMPC_ERR_UNSUPPORTED, "%s%s%s are not supported %s; %s%s%s", r ? "per-instance references (set_x_ref_batch / set_u_ref_batch)" : "",
+                    r && b ? " and " : "", b ? "per-instance bounds (set_bound_constraints_batch)" : "",
+                    s->layout_m ? "for systems with nx+nu > 64" : fam ? "with cone / linear constraint families" : "with adaptive rho",
+                    r ? "tinympc_set_x_ref / tinympc_set_u_ref return to shared references" : "", r && b ? ", " : "",
+                    b ? "tinympc_set_bound_constraints returns to shared bounds" : "");
+    }
     // k_build_adapt reads the device copy of the references before the solve kernel starts: bring the device copies and the tables up
     // to date the ordinary way (every other kernel of a single-instance handle stages references left in pinned host memory itself)
     if (s->refs_on_host && adaptive) {
@@ -371,9 +370,10 @@ int launch(tinympc_solver *s, bool timed) {
     }
     p.adapt = s->dadapt; p.rho_inst = s->drho_inst;
     if (pl.inst_refs) {
-        p.iref_lr = pl.kernel == KernelId::A ? s->iref_rows() : s->dIgoal;
-        p.iref_pn = s->dIpn;
-        if (pl.inst_bounds) p.ibnd = pl.kernel == KernelId::A ? s->dIb : s->dIbg;
+        p.iref_lr = pl.kernel == KernelId::A ? s->inst.lr_rows() : s->inst.lrg;
+        p.iref_pn = s->inst.pn;
+        if (pl.kernel != KernelId::A) p.ibnd = s->inst.bndg;  // (the goal form: always per lane)
+        else if (pl.inst_bounds) p.ibnd = s->inst.bnd;
     }
     p.rho_min = s->st.adaptive_rho_min; p.rho_max = s->st.adaptive_rho_max; p.rho_clip = s->st.adaptive_rho_enable_clipping;
     // a pending cold start: layout D's kernels start from zero registers; every other kernel loads its state from HBM
@@ -473,10 +473,10 @@ int tinympc_get_jit_info(tinympc_solver *s, char *buf, int len) {
     const bool ct = s->tables_const();
     if (pl.inst_refs) {
         // (per-instance-refs only when references are per instance; per-instance-bounds only when bounds are)
-        const char *words = !pl.inst_bounds ? " per-instance-refs" : s->iref() ? " per-instance-refs per-instance-bounds" : " per-instance-bounds";
+        const char *words = !pl.inst_bounds ? " per-instance-refs" : s->inst.refs() ? " per-instance-refs per-instance-bounds" : " per-instance-bounds";
         if (pl.kernel == KernelId::D_JIT) {
             if ((rc = bind_device(s))) return rc;
-            solve_jit_describe(s->W, s->nx, s->nu, s->N, true, false, false, buf, (size_t)len, pl.inst_bounds ? 2 : 1);
+            solve_jit_describe(s->W, s->nx, s->nu, s->N, true, false, false, buf, (size_t)len, true);
             strncat(buf, words, (size_t)len - strlen(buf) - 1);
             strncat(buf, " goal", (size_t)len - strlen(buf) - 1);
         } else {

@@ -79,7 +79,7 @@ __global__ void __launch_bounds__(64) k_admm_solve_iref(const SolveParams p) {
 template hipError_t launch_solve_a_e<SolveExt::InstRefs>(const SolveParams &, int, int, size_t, hipStream_t);
 
 // k_admm_solve_ibnd: k_admm_solve_iref for a batched handle whose instances also have their OWN bounds (tinympc_set_bound_constraints_batch).
-// The forward sweep streams the instance's clamp rows lo | hi from SolveParams::ibnd (k_build_inst_bounds, k_build_tables' expressions)
+// The forward sweep streams the instance's clamp rows lo | hi from SolveParams::ibnd (k_build_inst_tables, k_build_tables' expressions)
 // four knots ahead, as the backward sweep streams the linref rows; an instance whose bounds and references are the shared ones computes
 // exactly what k_admm_solve computes.
 template <int W, int KT, bool TLDS, bool GMEM>

@@ -219,15 +219,13 @@ __device__ __forceinline__ bool wave_may_converge_d(unsigned long long bad, unsi
 // arithmetic of an instance is that of the plain kernel (bit-identical results: tests/test_hip_parity.py); what changes is that
 // a wavefront's time is the sum of what its rows worked, not four times its slowest instance.
 template <int NX, int NU, int N, bool CT, int WPG, int VL, bool FAM = false, bool ADAPT = false, bool TWO_PER_SIMD = true, bool HOSTX = false,
-          bool REFILL = false, bool IGOAL = false, bool IBND = false>
+          bool REFILL = false, bool IGOAL = false>
 #else
-// IGOAL: per-instance references in the goal form (every instance's references constant over the horizon; k_admm_solve_d_goal) --
-// the two reference-dependent constants lr_c and pNref come per lane from SolveParams::iref_lr / iref_pn ([instance][16]) instead of
-// the shared table; nothing else changes.
-// IBND (with IGOAL; k_admm_solve_d_gbnd): per-instance bounds, constant over the horizon -- the two clamp constants lo_c and hi_c come
-// per lane from SolveParams::ibnd ([instance][16], hi at groups*64) as well. The same registers, loaded from elsewhere.
+// IGOAL: the per-instance goal form (every instance's references and bounds constant over the horizon; k_admm_solve_d_gbnd) -- the
+// four table constants lr_c, pNref, lo_c and hi_c come per lane from SolveParams::iref_lr / iref_pn / ibnd ([instance][16], ibnd's hi
+// at groups*64) instead of the shared table. The same registers, loaded from elsewhere; nothing else changes.
 template <int NX, int NU, int N, bool CT, int WPG, int VL, bool FAM = false, bool ADAPT = false, bool TWO_PER_SIMD = true, bool HOSTX = false,
-          bool REFILL = false, bool IGOAL = false, bool IBND = false>
+          bool REFILL = false, bool IGOAL = false>
 #endif
 __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double *smem) {
     static_assert(!(FAM && ADAPT), "adaptive rho and the constraint families exclude each other (as in the C ABI)");
@@ -435,8 +433,8 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
         pnref = fma(rho - rho0, dpnref, pnref0);
     }
     double nrho = -rho;
-    const double lo_c = IBND ? (inst_ok ? p.ibnd[inst * W + r] : 0.0) : p.tables[W + r];
-    const double hi_c = IBND ? (inst_ok ? p.ibnd[(size_t)p.groups * 64 + inst * W + r] : 0.0) : p.tables[(size_t)TOFF + W + r];
+    const double lo_c = IGOAL ? (inst_ok ? p.ibnd[inst * W + r] : 0.0) : p.tables[W + r];
+    const double hi_c = IGOAL ? (inst_ok ? p.ibnd[(size_t)p.groups * 64 + inst * W + r] : 0.0) : p.tables[(size_t)TOFF + W + r];
     const double lr_c = IGOAL ? (inst_ok ? p.iref_lr[inst * W + r] : 0.0) : p.tables[(size_t)2 * TOFF + W + r];
     double rhom = is_x ? nrho : 0.0;
 #if TINY_REFILL
@@ -1017,18 +1015,13 @@ __global__ void __launch_bounds__(64 * WPG) __attribute__((amdgpu_waves_per_eu(2
 #endif
 }
 #if !TINY_REFILL
-// Per-instance references, goal form (tinympc_set_x_ref_batch with one goal per instance): the plain constant-table kernel with the
-// instance's lr_c / pNref loaded per lane at kernel start.
-template <int NX, int NU, int N, int WPG, int VL>
-__global__ void __launch_bounds__(64 * WPG) __attribute__((amdgpu_waves_per_eu(2, 2))) k_admm_solve_d_goal(const SolveParams p) {
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    k_admm_solve_d_body<NX, NU, N, true, WPG, VL, false, false, true, false, false, true>(p, smem);
-}
-// ... with per-instance bounds too (tinympc_set_bound_constraints_batch with one box per instance): lo_c / hi_c per lane as well.
+// The per-instance goal form (one goal per instance from tinympc_set_x_ref_batch and / or one box per instance from
+// tinympc_set_bound_constraints_batch; shared references and bounds that are constant over the horizon fill the rest): the plain
+// constant-table kernel with the instance's lr_c / pNref / lo_c / hi_c loaded per lane at kernel start.
 template <int NX, int NU, int N, int WPG, int VL>
 __global__ void __launch_bounds__(64 * WPG) __attribute__((amdgpu_waves_per_eu(2, 2))) k_admm_solve_d_gbnd(const SolveParams p) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
-    k_admm_solve_d_body<NX, NU, N, true, WPG, VL, false, false, true, false, false, true, true>(p, smem);
+    k_admm_solve_d_body<NX, NU, N, true, WPG, VL, false, false, true, false, false, true>(p, smem);
 }
 #endif
 #endif
@@ -1069,11 +1062,8 @@ tinympc_jit_solve(const tinympc::SolveParams p) {
 #ifndef TINY_JIT_IGOAL
 #define TINY_JIT_IGOAL 0
 #endif
-#ifndef TINY_JIT_IBND
-#define TINY_JIT_IBND 0
-#endif
-    tinympc::k_admm_solve_d_body<TINY_JIT_NX, TINY_JIT_NU, TINY_JIT_N, CTJ, WPGJ, VLJ, FAMJ, ADJ, TINY_JIT_WPS == 2, false, false, TINY_JIT_IGOAL != 0,
-                                 TINY_JIT_IBND != 0>(p, smem_jit);
+    tinympc::k_admm_solve_d_body<TINY_JIT_NX, TINY_JIT_NU, TINY_JIT_N, CTJ, WPGJ, VLJ, FAMJ, ADJ, TINY_JIT_WPS == 2, false, false, TINY_JIT_IGOAL != 0>(
+        p, smem_jit);
 #endif
 }
 namespace tinympc {
@@ -1135,16 +1125,15 @@ static hipError_t launch_d_one(const SolveParams &p, hipStream_t stream) {
         return hipErrorInvalidValue;
     } else {
         constexpr size_t lds = d_lds_bytes(NU, N, CT, WPG, VL);
-        static size_t lds_set[16] = {0}, lds_set_x[16] = {0}, lds_set_g[16] = {0}, lds_set_b[16] = {0};
+        static size_t lds_set[16] = {0}, lds_set_x[16] = {0}, lds_set_goal[16] = {0};
         const int wgs = (p.groups + WPG - 1) / WPG;
         if (p.iref_pn) {  // per-instance goals (constant tables only; the plan never combines them with the zero-copy tick)
             if constexpr (!CT) {
                 return hipErrorInvalidValue;
             } else {
-                if (p.x0_mirror || p.u0_host) return hipErrorInvalidValue;
-                // (p.ibnd: per-instance boxes as well)
-                auto fn = p.ibnd ? &k_admm_solve_d_gbnd<NX, NU, N, WPG, VL> : &k_admm_solve_d_goal<NX, NU, N, WPG, VL>;
-                hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void *>(fn), lds, p.ibnd ? lds_set_b : lds_set_g);
+                if (p.x0_mirror || p.u0_host || !p.iref_lr || !p.ibnd) return hipErrorInvalidValue;
+                auto fn = &k_admm_solve_d_gbnd<NX, NU, N, WPG, VL>;
+                hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void *>(fn), lds, lds_set_goal);
                 if (e != hipSuccess) return e;
                 hipLaunchKernelGGL(fn, dim3(wgs), dim3(64 * WPG), lds, stream, p);
             }

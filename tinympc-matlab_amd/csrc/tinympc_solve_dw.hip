@@ -91,11 +91,8 @@ tinympc_jit_solve(const tinympc::SolveParams p) {
 #ifndef TINY_JIT_IGOAL
 #define TINY_JIT_IGOAL 0
 #endif
-#ifndef TINY_JIT_IBND
-#define TINY_JIT_IBND 0
-#endif
-    tinympc::k_admm_solve_wide_body<32, TINY_JIT_NX, TINY_JIT_NU, TINY_JIT_N, CTJ, WPGJ, VLJ, TINY_JIT_FAM != 0, TINY_JIT_IGOAL != 0,
-                                    TINY_JIT_IBND != 0>(p, smem_jit);  // (FAM: the streamed families, tinympc_solve_dwide.h)
+    tinympc::k_admm_solve_wide_body<32, TINY_JIT_NX, TINY_JIT_NU, TINY_JIT_N, CTJ, WPGJ, VLJ, TINY_JIT_FAM != 0, TINY_JIT_IGOAL != 0>(
+        p, smem_jit);  // (FAM: the streamed families, tinympc_solve_dwide.h)
 }
 #else
 template <int NX, int NU, int N, int WPG, int VL>

@@ -128,11 +128,10 @@ __device__ __forceinline__ bool wave_may_converge_w(unsigned long long bad, unsi
 }
 }  // namespace
 
-// IGOAL: per-instance references in the goal form (tinympc_set_x_ref_batch, constant over the horizon): lr_c and pNref per lane from
-// SolveParams::iref_lr / iref_pn ([instance][W]) instead of the shared table (run-time specialised only, -DTINY_JIT_IGOAL=1).
-// IBND (with IGOAL): per-instance bounds, constant over the horizon -- lo_c and hi_c per lane from SolveParams::ibnd ([instance][W], hi at
-// groups*64) as well (-DTINY_JIT_IBND=1).
-template <int W, int NX, int NU, int N, bool CT, int WPG, int VL, bool FAM = false, bool IGOAL = false, bool IBND = false>
+// IGOAL: the per-instance goal form (references and bounds constant over the horizon): lr_c, pNref, lo_c and hi_c per lane from
+// SolveParams::iref_lr / iref_pn / ibnd ([instance][W], ibnd's hi at groups*64) instead of the shared table (run-time specialised
+// only, -DTINY_JIT_IGOAL=1).
+template <int W, int NX, int NU, int N, bool CT, int WPG, int VL, bool FAM = false, bool IGOAL = false>
 __device__ __forceinline__ void k_admm_solve_wide_body(const SolveParams &p, double *smem) {
     constexpr int IPW = 64 / W, NXU = NX + NU, NS = N - 1, DS = IPW * NU, NVR = NS - VL;
     constexpr int KT = W;  // row stride of p.ops (choose_geometry)
@@ -202,8 +201,8 @@ __device__ __forceinline__ void k_admm_solve_wide_body(const SolveParams &p, dou
     const double cb = p.ops[(size_t)2 * W * KT + W + r];
     const double pnref = IGOAL ? (inst_ok ? p.iref_pn[inst * W + r] : 0.0) : p.tables[(size_t)3 * TOFF + r];
     const double rho = p.rho, nrho = -p.rho;
-    const double lo_c = IBND ? (inst_ok ? p.ibnd[inst * W + r] : 0.0) : p.tables[W + r];
-    const double hi_c = IBND ? (inst_ok ? p.ibnd[(size_t)p.groups * 64 + inst * W + r] : 0.0) : p.tables[(size_t)TOFF + W + r];
+    const double lo_c = IGOAL ? (inst_ok ? p.ibnd[inst * W + r] : 0.0) : p.tables[W + r];
+    const double hi_c = IGOAL ? (inst_ok ? p.ibnd[(size_t)p.groups * 64 + inst * W + r] : 0.0) : p.tables[(size_t)TOFF + W + r];
     const double lr_c = IGOAL ? (inst_ok ? p.iref_lr[inst * W + r] : 0.0) : p.tables[(size_t)2 * TOFF + W + r];
     const double rhom = is_x ? nrho : 0.0;
     const double x0v = (inst_ok && is_x) ? p.x0[inst * NX + r] : 0.0;

@@ -319,29 +319,14 @@ class TinyMPC:
         instance, held over the horizon) or (nx, N, count) (a trajectory per instance), or a CUDA torch tensor with the same memory
         layout, (count, nx) or (count, N, nx) contiguous. set_x_ref() returns every instance to the shared reference."""
         self._check_setup()
-        self._set_ref_batch(x_refs, first, self.nx, self.N, self._L.tinympc_set_x_ref_batch, self._L.tinympc_set_x_ref_batch_device)
+        self._set_batch("references", (x_refs,), (self.nx,), (self.N,), self._L.tinympc_set_x_ref_batch,
+                        self._L.tinympc_set_x_ref_batch_device, first, self.nx)
 
     def set_u_ref_batch(self, u_refs, first: int = 0):
         """Per-instance input references: (nu, count) or (nu, N-1, count); see set_x_ref_batch."""
         self._check_setup()
-        self._set_ref_batch(u_refs, first, self.nu, self.N - 1, self._L.tinympc_set_u_ref_batch, self._L.tinympc_set_u_ref_batch_device)
-
-    def _set_ref_batch(self, refs, first, rows, cols_full, f_host, f_device):
-        if hasattr(refs, "data_ptr") and getattr(refs, "is_cuda", False):
-            import torch
-            if refs.dtype != torch.float64 or not refs.is_contiguous() or refs.dim() not in (2, 3) or refs.shape[-1] != rows:
-                raise TinyMPCError(_lib.ERR_INVALID_INPUT, "references on the device must be a contiguous float64 tensor of shape "
-                                   "(count, %d) or (count, %d, %d), got %s %s" % (rows, cols_full, rows, refs.dtype, tuple(refs.shape)))
-            cols = 1 if refs.dim() == 2 else refs.shape[1]  # (the library checks cols, the range and that the memory is on the handle's GPU)
-            torch.cuda.current_stream(refs.device).synchronize()  # (the set_x0_batch contract)
-            _lib.check(f_device(self._h, C.c_void_p(refs.data_ptr()), rows, cols, first, refs.shape[0]))
-            return
-        a = np.asarray(refs, dtype=np.float64)
-        if a.ndim not in (2, 3) or a.shape[0] != rows:
-            raise TinyMPCError(_lib.ERR_INVALID_INPUT, "references must be %d x count or %d x %d x count" % (rows, rows, cols_full))
-        cols = 1 if a.ndim == 2 else a.shape[1]
-        a = _f(a)
-        _lib.check(f_host(self._h, _p(a), rows, cols, first, a.shape[-1]))
+        self._set_batch("references", (u_refs,), (self.nu,), (self.N - 1,), self._L.tinympc_set_u_ref_batch,
+                        self._L.tinympc_set_u_ref_batch_device, first, self.nu)
 
     def set_bound_constraints_batch(self, x_min, x_max, u_min, u_max, first: int = 0):
         """Per-instance box bounds for instances first, first+1, ...: numpy arrays of shape (nx, count) / (nu, count) (one box per
@@ -349,38 +334,42 @@ class TinyMPC:
         memory layout, (count, nx) / (count, nu) or (count, N, nx) / (count, N-1, nu) contiguous float64. All four in the same form.
         Enables both bound families, as set_bound_constraints does; set_bound_constraints() returns every instance to shared bounds."""
         self._check_setup()
-        arrays = (x_min, x_max, u_min, u_max)
-        rows = (self.nx, self.nx, self.nu, self.nu)
-        full = (self.N, self.N, self.N - 1, self.N - 1)
+        self._set_batch("bounds", (x_min, x_max, u_min, u_max), (self.nx, self.nx, self.nu, self.nu), (self.N, self.N, self.N - 1, self.N - 1),
+                        self._L.tinympc_set_bound_constraints_batch, self._L.tinympc_set_bound_constraints_batch_device, first)
+        self.settings["en_state_bound"] = True
+        self.settings["en_input_bound"] = True
+
+    def _set_batch(self, what, arrays, rows, full, f_host, f_device, first, *extra):
+        """The per-instance verbs: numpy arrays of shape (rows, count) / (rows, cols, count), or contiguous float64 CUDA tensors with the
+        same memory layout, (count, rows) / (count, cols, rows) -- one column held over the horizon, or cols = full. All arrays in the
+        same form; f(handle, *arrays, *extra, cols, first, count) with cols = 1 or the first array's full column count."""
         on_device = [hasattr(a, "data_ptr") and getattr(a, "is_cuda", False) for a in arrays]
         if any(on_device):
             import torch
             if not all(on_device):
-                raise TinyMPCError(_lib.ERR_INVALID_INPUT, "bounds: all four must be CUDA tensors, or none")
+                raise TinyMPCError(_lib.ERR_INVALID_INPUT, "%s: all must be CUDA tensors, or none" % what)
             for a, r, c in zip(arrays, rows, full):
                 if a.dtype != torch.float64 or not a.is_contiguous() or a.dim() not in (2, 3) or a.shape[-1] != r or \
                         (a.dim() == 3 and a.shape[1] != c):
-                    raise TinyMPCError(_lib.ERR_INVALID_INPUT, "bounds on the device must be contiguous float64 tensors of shape "
-                                       "(count, %d) or (count, %d, %d), got %s %s" % (r, c, r, a.dtype, tuple(a.shape)))
-            if len({(a.dim(), a.shape[0]) for a in arrays}) != 1:
-                raise TinyMPCError(_lib.ERR_INVALID_INPUT, "bounds: all four must have the same form and count")
-            cols = 1 if x_min.dim() == 2 else self.N
-            torch.cuda.current_stream(x_min.device).synchronize()  # (the set_x0_batch contract)
-            _lib.check(self._L.tinympc_set_bound_constraints_batch_device(
-                self._h, *[C.c_void_p(a.data_ptr()) for a in arrays], cols, first, x_min.shape[0]))
+                    raise TinyMPCError(_lib.ERR_INVALID_INPUT, "%s on the device must be contiguous float64 tensors of shape "
+                                       "(count, %d) or (count, %d, %d), got %s %s" % (what, r, c, r, a.dtype, tuple(a.shape)))
+            forms = {(a.dim(), a.shape[0]) for a in arrays}
+            ptrs = [C.c_void_p(a.data_ptr()) for a in arrays]
         else:
-            arrs = [np.asarray(a, dtype=np.float64) for a in arrays]
-            for a, r, c in zip(arrs, rows, full):
+            arrays = [np.asarray(a, dtype=np.float64) for a in arrays]
+            for a, r, c in zip(arrays, rows, full):
                 if a.ndim not in (2, 3) or a.shape[0] != r or (a.ndim == 3 and a.shape[1] != c):
-                    raise TinyMPCError(_lib.ERR_INVALID_INPUT, "bounds must be %d x count or %d x %d x count, got %s"
-                                       % (r, r, c, a.shape))
-            if len({(a.ndim, a.shape[-1]) for a in arrs}) != 1:
-                raise TinyMPCError(_lib.ERR_INVALID_INPUT, "bounds: all four must have the same form and count")
-            cols = 1 if arrs[0].ndim == 2 else self.N
-            arrs = [_f(a) for a in arrs]
-            _lib.check(self._L.tinympc_set_bound_constraints_batch(self._h, *[_p(a) for a in arrs], cols, first, arrs[0].shape[-1]))
-        self.settings["en_state_bound"] = True
-        self.settings["en_input_bound"] = True
+                    raise TinyMPCError(_lib.ERR_INVALID_INPUT, "%s must be %d x count or %d x %d x count, got %s" % (what, r, r, c, a.shape))
+            forms = {(a.ndim, a.shape[-1]) for a in arrays}
+            arrays = [_f(a) for a in arrays]
+            ptrs = [_p(a) for a in arrays]
+        if len(forms) != 1:
+            raise TinyMPCError(_lib.ERR_INVALID_INPUT, "%s: all must have the same form and count" % what)
+        (ndim, count), = forms
+        cols = 1 if ndim == 2 else full[0]  # (the library checks the range and that device memory is on the handle's GPU)
+        if on_device[0]:
+            torch.cuda.current_stream(arrays[0].device).synchronize()  # (the set_x0_batch contract)
+        _lib.check((f_device if on_device[0] else f_host)(self._h, *ptrs, *extra, cols, first, count))
 
     def _tick_buffers(self):
         """Persistent buffers of the per-tick verbs (addresses cached: see _lib.fast_tick_functions)."""

@@ -1,7 +1,7 @@
 """Per-instance bounds at bench size: kernel milliseconds (HIP events, tinympc_solve_timed) of the same forced-iteration solve with
   shared       one constant box for every instance (what bench.py times: layout D where the shape is compiled in)
-  box          one box per instance (set_bound_constraints_batch, (nx, count) / (nu, count)): layout D's k_admm_solve_d_gbnd where the
-               shape is compiled in -- the same kernel body as `shared`, with lo / hi loaded per lane
+  box          one box per instance (set_bound_constraints_batch, (nx, count) / (nu, count)): layout D's goal form (k_admm_solve_d_gbnd
+               where the shape is compiled in) -- the same kernel body as `shared`, with lr / pNref / lo / hi loaded per lane
   shared-A-knot  shared per-knot bounds on layout A (TINYMPC_LAYOUT=A; the per-knot variant's own layout)
   knot         bounds per knot per instance (set_bound_constraints_batch, (nx, N, count)): layout A's k_admm_solve_ibnd
 The variants run interleaved, `--rounds` times; the median of `--reps` launches per round is reported, one JSON line per variant.

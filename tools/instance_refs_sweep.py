@@ -2,7 +2,7 @@
   shared      one constant reference for every instance (what bench.py times: layout D where the shape is compiled in)
   shared-A    the same on layout A (TINYMPC_LAYOUT=A; the per-instance kernels' own layout)
   shared-A-knot  a shared per-knot reference on layout A (TINYMPC_LAYOUT=A)
-  goal        one goal per instance (set_x_ref_batch, (nx, count)): layout D's k_admm_solve_d_goal where the shape is compiled in
+  goal        one goal per instance (set_x_ref_batch, (nx, count)): layout D's goal form (k_admm_solve_d_gbnd where the shape is compiled in)
   trajectory  a trajectory per instance (set_x_ref_batch, (nx, N, count)): layout A's k_admm_solve_iref
 The variants run interleaved, `--rounds` times; the median of `--reps` launches per round is reported, one JSON line per variant.
     python tools/instance_refs_sweep.py [--batch 8192] [--N 50] [--iters 200] [--rounds 2] [--reps 5] [--only goal]
