@@ -1,9 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- ADMM iterations/s of the batched quadrotor solve (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
     (N > 1: launched by the driver as `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`;
      run directly with --gpus N > 1 it re-launches itself that way before touching the GPU.)
+
+A plain run does what the headline needs and nothing else: setup, the timed steps, the outputs of --dump-outputs, the JSON line.
+`--full` adds everything else the benchmark measures or checks: `parity_check`, the CPU baseline and, with N = 1, every other
+leg (config 5 on one GPU, single instances, other systems and shapes, latency, setup and batched ticks; tools/bench_legs.py).
 
 One "step" = one cold-started batched solve on every rank: reset the persistent ADMM state, then ONE
 launch of k_admm_solve running 200 forced ADMM iterations (tolerances 0, check_termination 1, so the
@@ -20,7 +24,7 @@ live with HIP events on the kernel's stream / 78.6 TFLOP/s. The ADMM state stays
 streaming-bytes figure of SURVEY.md section 8d (8*(11U+9X) per instance-iteration against 8 TB/s) exceeds 1 and is
 kept only as the secondary block `roofline.hbm_algorithmic`; `roofline.traffic` is the PMC-measured HBM bytes per
 launch, reported only when profiles/traffic_latest.json was collected with the library that is running now.
-`parity_check` compares instances 0..63 of the timed workload with tests/golden/quadrotor_batch64.npz (the reference
+With --full: `parity_check` compares instances 0..63 of the timed workload with tests/golden/quadrotor_batch64.npz (the reference
 core's own output) after the timed region and fails the run beyond 1e-6. `cpu_baseline` times the reference's own compiled
 core (oracle/_ref, kind "reference") -- or this repo's C restatement (kind "port") where that binary is
 absent -- on the host cores, on a bounded sample of the same workload.
@@ -51,12 +55,15 @@ def parse_args():
                     help="fixed TOTAL number of instances split over the GPUs (strong scaling); overrides --batch-per-gpu")
     ap.add_argument("--iters", type=int, default=200, help="forced ADMM iterations per solve")
     ap.add_argument("--horizon", type=int, default=50)
-    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="time budget of the CPU baseline sample")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run what it does not need: parity_check, the CPU baseline and every other leg "
+                         "(the --no-* options below leave parts of it out)")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="time budget of the CPU baseline sample (--full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-settle", action="store_true", help="time the K steps right behind the W warm-up steps (the GPU's clock is then still ramping up)")
     ap.add_argument("--sync-steps", action="store_true", help="wait for every timed step before launching the next (default: the K steps are queued and waited for once)")
-    ap.add_argument("--no-single", action="store_true", help="skip the B=1 latency measurement")
-    ap.add_argument("--no-config5", action="store_true", help="skip the 65,536-instance single-GPU leg")
+    ap.add_argument("--no-single", action="store_true", help="--full without the single-instance, shape and latency legs")
+    ap.add_argument("--no-config5", action="store_true", help="--full without the 65,536-instance single-GPU leg")
     ap.add_argument("--dist-backend", choices=("nccl", "gloo"), default=os.environ.get("TINYMPC_BENCH_DIST_BACKEND", "nccl"),
                     help="process-group backend of the N > 1 run: nccl (= RCCL over xGMI, one GPU per rank; the default and what the driver "
                          "runs) or gloo (host-side collectives: the only backend that lets several ranks share one device)")
@@ -70,7 +77,7 @@ def parse_args():
     ap.add_argument("--cpu-worker-latency", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--cpu-worker-ticks", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--worker-count", type=int, default=0, help=argparse.SUPPRESS)
-    ap.add_argument("--no-round5-legs", action="store_true", help="skip the setup and batched_tick legs")
+    ap.add_argument("--no-round5-legs", action="store_true", help="--full without the setup and batched_tick legs")
     ap.add_argument("--dump-outputs", default="", metavar="DIR",
                     help="after the timed steps, write what the last timed step computed (rank 0's shard) as DIR/<name>.npy, float64")
     return ap.parse_args()
@@ -420,10 +427,10 @@ def main() -> int:
         return relaunch_under_torchrun(args)  # nothing has touched the GPU yet
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
-    # CPU baseline first (rank 0, single-GPU runs only): child processes, started before this process
+    # CPU baseline first (--full, rank 0, single-GPU runs only): child processes, started before this process
     # has initialised the GPU, so the host cores are not shared with the timed GPU region either.
     cpu = None
-    if world == 1 and rank == 0 and not args.no_cpu_baseline:
+    if args.full and world == 1 and rank == 0 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args.iters, args.horizon, args.cpu_seconds, round5=not args.no_round5_legs)
 
     import numpy as np
@@ -433,8 +440,6 @@ def main() -> int:
     sys.path.insert(0, ROOT)
     import __graft_entry__ as ge
 
-    from tools.bench_legs import (LegContext, batched_tick_leg, config5_legs, instance_and_family_legs, setup_leg, shape_and_latency_legs,
-                                  stats_us)
     pkg = ge.load_package()
     P = pkg.problems
     # The interpreter's cyclic collector: a full pass over torch's ~170,000 import-time objects takes 40-80 ms and lands wherever the
@@ -520,8 +525,8 @@ def main() -> int:
         barrier()
         return time.perf_counter() - t0, kms
 
-    # (1) AS ASKED: exactly the driver's W warm-up steps, then the K timed steps. This process has just spent ~30 s on the CPU
-    # baseline with the GPU idle, and the first launches after that run at a lower shader clock (2.0 ms per launch in the first
+    # (1) AS ASKED: exactly the driver's W warm-up steps, then the K timed steps. The GPU has been idle until now (with --full for
+    # the ~30 s of the CPU baseline), and the first launches run at a lower shader clock (2.0 ms per launch in the first
     # ten, 1.67 from about the 50th on; in-kernel stamps: tools/clock_check.py), so W = 5 ends inside that ramp.
     # (2) SETTLED: the step is repeated, untimed, until 0.4 s have passed, then W warm-up + K timed steps again -- the
     # steady state a throughput job lives in. `value` is (2); (1) is printed beside it as `value_as_asked`; `--no-settle` runs (1)
@@ -587,10 +592,10 @@ def main() -> int:
     achieved_tflops = alg_flops_per_launch / kernel_s / 1e12
 
     # Parity of the timed workload itself: instances 0..63 of rank 0 are the x0 of tests/golden/quadrotor_batch64.npz
-    # (200 forced iterations of the reference's own core). The last timed step's solutions are still on the device.
+    # (200 forced iterations of the reference's own core). The last timed step's solutions are still on the device. (--full)
     parity = None
     gpath = os.path.join(ROOT, "tests", "golden", "quadrotor_batch64.npz")
-    if rank == 0 and os.path.exists(gpath) and args.iters == 200 and args.horizon == 50 and count >= 64:
+    if args.full and rank == 0 and os.path.exists(gpath) and args.iters == 200 and args.horizon == 50 and count >= 64:
         g = np.load(gpath)
         if np.array_equal(g["x0s"], x0_host[:, :64]):
             sol = solver.get_solution_batch(0, 64)
@@ -627,7 +632,8 @@ def main() -> int:
             "value_as_asked": inst_iters_per_step * args.steps / elapsed_asked, "ms_per_step_as_asked": 1e3 * elapsed_asked / args.steps,
             "value_note": ("value = value_as_asked: --no-settle" if args.no_settle else
                            "value: W warm-up + K timed steps after 0.4 s of untimed repetitions (steady-state clock); value_as_asked: the W warm-up + "
-                           "K timed steps run first, right behind the CPU baseline's ~30 s of GPU idling (clock still ramping up)"),
+                           "K timed steps run first, right behind %s (clock still ramping up)"
+                           % ("the CPU baseline's ~30 s of GPU idling" if cpu is not None else "the setup")),
             "ms_per_step": 1e3 * elapsed / args.steps, "steps_queued": not args.sync_steps, "higher_is_better": True, "scaling": "strong" if strong else "weak",
             "vs_baseline": None, "vs_baseline_note": "BASELINE.md section 1: the reference publishes no number for this metric",
             "dtype": "f64", "data": "synthetic",
@@ -637,8 +643,9 @@ def main() -> int:
                        "batch_per_gpu": B, "global_batch": total_instances, "iters_per_solve": args.iters,
                        "parallelism": "independent instances sharded x%d, no data-path collective" % world},
             "solves_per_s": value / args.iters,
-            "settle": dict(settle, note="untimed repetitions of the step before the W warm-up steps, until 0.4 s have passed: the GPU idles during the "
-                                        "CPU baseline and its first launches run at a lower clock; first / last = mean kernel time of the first / last ten"),
+            "settle": dict(settle, note="untimed repetitions of the step before the W warm-up steps, until 0.4 s have passed: the GPU idles until the "
+                                        "first timed steps (with --full during the CPU baseline) and its first launches run at a lower clock; first / last = "
+                                        "mean kernel time of the first / last ten"),
             "roofline": {"bound": "fp64_vector", "achieved": achieved_tflops, "peak": PEAK_FP64_TFLOPS, "unit": "TFLOP/s",
                          "frac": achieved_tflops / PEAK_FP64_TFLOPS, "traffic": traffic, "traffic_note": traffic_note,
                          "frac_as_asked": alg_flops_per_launch / (kernel_ms_asked_avg * 1e-3) / 1e12 / PEAK_FP64_TFLOPS,
@@ -661,23 +668,26 @@ def main() -> int:
                                "ranks_per_device": ("%d ranks share device(s) %s (rehearsal of the N > 1 path on fewer GPUs than ranks: the rates are "
                                                     "not a scaling measurement)" % (world, sorted({p_["device"] for p_ in per_rank}))
                                                     if len({p_["device"] for p_ in per_rank}) < world else 1)} if use_dist else None),
-            "legs_run_on": ("rank 0 of a single-rank job only: with n_gpus > 1 the line carries the headline, per_rank, summary and parity_check; "
-                            "cpu_baseline, config5_single_gpu, converging_batch and every latency / shape leg are skipped on every rank"),
+            "legs_run_on": ("rank 0 of a single-rank job run with --full only: cpu_baseline, config5_single_gpu, converging_batch and every latency / "
+                            "shape leg are skipped otherwise; a plain run's line carries the headline, per_rank and summary, --full adds "
+                            "parity_check at every n_gpus"),
             "per_rank": per_rank,
             "launch": info,
             "summary": summary,
         }
-        ctx = LegContext(pkg=pkg, prob=prob, args=args, cpu=cpu, dev_index=dev_index, dev=dev, torch=torch, np=np, out=out, flops_iter=flops_iter,
-                         bytes_iter=bytes_iter, sol=(sol if parity else None), parity=parity, leg_counters=leg_counters)
         # (the legs of rounds 1-4 live in tools/bench_legs.py since round 5: this file keeps the headline, the contract and the flat `legs`)
-        if world == 1 and not args.no_config5:
-            config5_legs(ctx)
-        if world == 1 and not args.no_single:
-            instance_and_family_legs(ctx)
-            shape_and_latency_legs(ctx)
-        if world == 1 and not args.no_round5_legs:
-            out["setup"] = setup_leg(pkg, cpu)
-            out["batched_tick"] = batched_tick_leg(pkg, cpu, dev_index)
+        if args.full and world == 1:
+            from tools.bench_legs import LegContext, batched_tick_leg, config5_legs, instance_and_family_legs, setup_leg, shape_and_latency_legs
+            ctx = LegContext(pkg=pkg, prob=prob, args=args, cpu=cpu, dev_index=dev_index, dev=dev, torch=torch, np=np, out=out, flops_iter=flops_iter,
+                             bytes_iter=bytes_iter, sol=(sol if parity else None), parity=parity, leg_counters=leg_counters)
+            if not args.no_config5:
+                config5_legs(ctx)
+            if not args.no_single:
+                instance_and_family_legs(ctx)
+                shape_and_latency_legs(ctx)
+            if not args.no_round5_legs:
+                out["setup"] = setup_leg(pkg, cpu)
+                out["batched_tick"] = batched_tick_leg(pkg, cpu, dev_index)
         if cpu is not None:
             out["cpu_baseline"] = cpu
             out["gpu_over_cpu"] = value / cpu["value"]

@@ -43,7 +43,7 @@ def _launch(world: int, extra: list[str], timeout: int = 900):
     env.pop("TINYMPC_LAYOUT", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=%d" % world, "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "2", "--warmup", "1",
-           "--iters", str(ITERS), "--no-cpu-baseline", "--no-single", "--no-config5"] + extra
+           "--iters", str(ITERS), "--full", "--no-cpu-baseline", "--no-single", "--no-config5"] + extra
     # fresh child processes (torchrun starts one per rank); nothing is exec'ed over a process that has touched the GPU
     return subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=timeout)
 

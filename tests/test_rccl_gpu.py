@@ -30,7 +30,7 @@ def test_bench_under_torchrun_uses_rccl_and_reduces_the_summary(pkg):
     env.pop("TINYMPC_LAYOUT", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-           "--batch-per-gpu", str(batch), "--iters", str(iters), "--no-cpu-baseline", "--no-single", "--no-config5"]
+           "--batch-per-gpu", str(batch), "--iters", str(iters), "--full", "--no-cpu-baseline", "--no-single", "--no-config5"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)  # a child process: nothing is exec'ed over this one
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]

@@ -1,6 +1,6 @@
 #!/bin/bash
 # tools/gpu_profile.sh <tag> -- run ON THE GPU BOX (through gpurun) from the repo root:
-#   bench.py (the driver's command), then the same workload under rocprofv3: kernel trace + stats, and the HBM byte
+#   bench.py --full (the headline and every leg), then the headline workload under rocprofv3: kernel trace + stats, and the HBM byte
 #   counters FETCH_SIZE / WRITE_SIZE in two separate --pmc passes (MI355X_MICROARCH.md: they do not fit one pass; a --pmc pass
 #   carries --kernel-trace only -- never --sys-trace / --runtime-trace / the hip, hsa, memory-copy or marker domains, which
 #   gpurun refuses next to counters). Everything lands in gpurun_out/; afterwards
@@ -10,7 +10,7 @@ TAG=${1:?tag}
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out
 mkdir -p "$O"
-python3 "$R/bench.py" > "$O/bench_$TAG.json" 2> "$O/bench_$TAG.err"
+python3 "$R/bench.py" --full > "$O/bench_$TAG.json" 2> "$O/bench_$TAG.err"
 tail -c 600 "$O/bench_$TAG.json"
 cd /tmp && export TMPDIR=/tmp
 WL="--no-cpu-baseline --no-single --no-config5 --no-round5-legs --steps 20 --warmup 3"  # (the headline workload only: every launch of k_admm_solve_d in the trace is the SAME 8,192 x 200 solve)
