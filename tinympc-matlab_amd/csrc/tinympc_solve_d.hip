@@ -16,8 +16,9 @@
 //              spread over the CUs wavefront by wavefront (d_wpg below).
 //
 // Per sweep step the instruction stream is one asm block (tinympc_solve_d_chain.h): mov + (nx+nu) fused DPP FMAs +
-// the 8-instruction row-local block going forward, (nx+nu) FMAs + 3 going backward; no address arithmetic (LDS
-// immediate offsets), no selects:
+// the 8-instruction row-local block going forward, (nx+nu) FMAs + 3 going backward (FMAs + 2 where references and bounds are
+// constant over the horizon: FOLD in the body; forward step 0 has only its nu input columns: K0); no address arithmetic (LDS immediate
+// offsets), no selects:
 //   * the chain's columns k < nx read the state operand register, columns k >= nx the input-row operand register
 //     (two different DPP sources), so [x_i; d_i] / [p_{i+1}; r_i] are never merged into one register;
 //   * going backward every lane uses the SAME slot: slot s holds knot s+1 on state lanes and knot s on input lanes,
@@ -239,6 +240,13 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
     constexpr int TOFF = (N + 2) * W;
     static_assert(NS >= 3 && VL >= 0 && VL <= NS, "layout D: N >= 4");
     using Step = DStep<NX, NU>;
+    // Work that does not change within a launch, taken out of the sweeps (box path only: the families' and adaptive rho's code is
+    // untouched). K0: x_0 is fixed, so the state columns of forward step 0 are summed once into its accumulator start c0 (not in the
+    // slot-refill variant: it sits at 256 registers with its rare paths in scratch, and the two registers of a live c0 moved a reload
+    // into a sweep). FOLD (references constant over the horizon as well): the backward step's input-row operand r_s = -rho * t + lr_c
+    // is not formed; the operator's input columns carry -rho and the accumulator starts carry Mb[:, nx:] * lr_c instead (Step::bwd_fold).
+    constexpr bool K0 = !FAM && !ADAPT && !REFILL;
+    constexpr bool FOLD = !FAM && !ADAPT && CT;
 
 #ifdef TINY_CLOCK_STAMP
     const unsigned long long ck_entry = __builtin_amdgcn_s_memrealtime();
@@ -264,7 +272,8 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
     // ---- workgroup-shared: the two sweep operators, transposed to [k][r] (conflict-free row reads), and the tables
     for (int i = threadIdx.x; i < D_OPS_DOUBLES; i += 64 * WPG) {
         const int which = i >> 8, k = (i >> 4) & 15, rr = i & 15;
-        sOps[i] = (k < KT) ? p.ops[(size_t)which * W * KT + (size_t)rr * KT + k] : 0.0;
+        const double v = (k < KT) ? p.ops[(size_t)which * W * KT + (size_t)rr * KT + k] : 0.0;
+        sOps[i] = (FOLD && which == 1 && k >= NX) ? -p.rho * v : v;  // (FOLD: -rho * Mb[:, nx:])
     }
     if constexpr (!CT)
         for (int i = threadIdx.x; i < d_tab_doubles(N); i += 64 * WPG) sT[i] = p.tables[i];
@@ -452,6 +461,21 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
     const double *const sMf = sOps + r, *const sMb = sOps + 256 + r;
     const unsigned aV = lds_addr(sVl), aD = lds_addr(sDr), aT = lds_addr(sTl);
     const int ct = p.check_termination;
+    // K0: c0 = cf + Mf[:, :nx] * x_0 -- the chain's state columns, its FMAs in its order, so forward step 0 (the input columns behind
+    // c0) is bit-identical to the full chain.
+    double c0 = 0.0;
+    if constexpr (K0) {
+        c0 = cf;
+        static_for<0, NX>([&](auto K) { c0 = fma(__shfl(x0v, (lane & 48) + K.value), sMf[K.value * 16], c0); });
+    }
+    // FOLD: the accumulator start of a backward step, lr_c + cb on state lanes and cb on input lanes, plus Mb[:, nx:] * lr_c (the input
+    // lanes' lr_c, the unscaled operator); the same expression in the shared-table and the per-instance goal kernels
+    double lrmc_f = 0.0;
+    if constexpr (FOLD) {
+        double mb[16];
+        static_for<0, 16>([&](auto K) { mb[K.value] = (K.value >= NX && K.value < NXU) ? p.ops[(size_t)W * KT + (size_t)r * KT + K.value] : 0.0; });
+        lrmc_f = Step::acc_inputs(is_x ? lr_c + cb : cb, lr_c, mb);
+    }
 
     // Control: an instance that converges stops being `active` but its lanes keep iterating as a zombie (the sweeps are
     // unconditional for all 64 lanes -- no EXEC-masked region around the unrolled body). Its state is written back at
@@ -728,11 +752,13 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
             const double xprev = xcur;
             double snew_q;
             if constexpr (q >= VL) {
-                xcur = Step::fwd_reg(xcur, dcur, m, cf, locur, hicur, G[q], Vr[q - VL], pri, dua);
+                if constexpr (K0 && q == 0) xcur = Step::fwd_reg0(dcur, m, c0, locur, hicur, G[q], Vr[q - VL], pri, dua);
+                else xcur = Step::fwd_reg(xcur, dcur, m, cf, locur, hicur, G[q], Vr[q - VL], pri, dua);
                 snew_q = Vr[q - VL];
             } else {
                 double vnew;
-                xcur = Step::fwd_lds(xcur, dcur, m, cf, locur, hicur, G[q], vcur, vnew, pri, dua);
+                if constexpr (K0 && q == 0) xcur = Step::fwd_lds0(dcur, m, c0, locur, hicur, G[q], vcur, vnew, pri, dua);
+                else xcur = Step::fwd_lds(xcur, dcur, m, cf, locur, hicur, G[q], vcur, vnew, pri, dua);
                 lds_write_async<q * 512>(aV, vnew);
                 snew_q = vnew;
             }
@@ -899,6 +925,14 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
                         : [t] "=&v"(t), [px] "=&v"(px), [acc] "=&v"(acc), [rn] "=&v"(rnext)
                         : [v1] "v"(v1), [g1] "v"(G[NS - 1]), [v2] "v"(v2), [g2] "v"(G[NS - 2]), [nrho] "v"(nrho_lin), [lrT] "v"(lrT),
                           [rhom] "v"(rhom_lin), [lrmc] "v"(lrmc2), [lr] "v"(lr2));
+                } else if constexpr (FOLD) {  // (input lanes: px = 1 * t + 0 = t exactly, the r_{N-2} of the folded operator; rn = t)
+                    asm("v_add_f64 %[t], %[v1], -%[g1]\n\t"
+                        "v_fma_f64 %[px], %[sc], %[t], %[lrT]\n\t"
+                        "v_add_f64 %[rn], %[v2], -%[g2]\n\t"
+                        "v_fma_f64 %[acc], %[rhom], %[rn], %[lrmc]"
+                        : [t] "=&v"(t), [px] "=&v"(px), [acc] "=&v"(acc), [rn] "=&v"(rnext)
+                        : [v1] "v"(v1), [g1] "v"(G[NS - 1]), [v2] "v"(v2), [g2] "v"(G[NS - 2]), [sc] "v"(is_x ? nrho : 1.0),
+                          [lrT] "v"(is_x ? pnref : 0.0), [rhom] "v"(rhom), [lrmc] "v"(lrmc_f));
                 } else {
                     asm("v_add_f64 %[t], %[v1], -%[g1]\n\t"
                         "v_fma_f64 %[px], %[nrho], %[t], %[lrT]\n\t"
@@ -930,6 +964,7 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
                 const double lrmc2 = is_x ? lr2 + cb : cb;
                 double a = acc, an, rn;
                 if constexpr (ADAPT) Step::bwd_v(a, px, rcur, m, v2cur, G[s2], rhom_lin, lrmc2, nrho_lin, lr2, an, rn);
+                else if constexpr (FOLD) Step::bwd_fold(a, px, rcur, m, v2cur, G[s2], rhom, lrmc_f, an, rn);
                 else Step::bwd(a, px, rcur, m, v2cur, G[s2], rhom, lrmc2, nrho, lr2, an, rn);
                 lds_write_masked<s * DS * 8>(aD, a, wr_d);  // d_s
                 px = a;

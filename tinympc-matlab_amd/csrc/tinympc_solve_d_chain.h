@@ -18,7 +18,7 @@
 //
 // DPP hazard (a VGPR written by VALU must not be read through DPP within 2 wait states; nothing guards it inside
 // inline asm): `x` is the `a` the previous block's chain wrote; forward blocks end with >= 8 non-DPP instructions
-// after that write, backward blocks with 3. tests/test_isa_hazards.py checks the generated code.
+// after that write, backward blocks with 3 (2 in the folded form, bwd_fold). tests/test_isa_hazards.py checks the generated code.
 #if !defined(D_NX) || !defined(D_NU)
 #error "define D_NX and D_NU before including tinympc_solve_d_chain.h"
 #endif
@@ -310,6 +310,27 @@ struct DStep<D_NX, D_NU> {
         lds_reads_landed();
         return a;
     }
+    // Forward step 0 of a sweep whose x_0 does not change within the launch: the state columns are folded into the accumulator start,
+    // c0 = cf + Mf[:, :nx] * x_0 (the same FMAs in the same order, computed once -- tinympc_solve_d.hip), so only the input columns
+    // remain; slack in a register / in LDS as fwd_reg / fwd_lds
+    static __device__ __forceinline__ double fwd_reg0(double d, const double (&m)[16], double c0, double lo, double hi, double &g, double &v,
+                                                      double &pri, double &dua) {
+        double a, s, t, sn;
+        asm volatile("v_mov_b64 %[a], %[cf]\n\t" D_HAZ D_CHAIN_IN D_PROJECT "v_mov_b64 %[v], %[sn]\n\t"
+                     : [a] "=&v"(a), [s] "=&v"(s), [t] "=&v"(t), [sn] "=&v"(sn), [g] "+v"(g), [v] "+v"(v), [pri] "+v"(pri), [dua] "+v"(dua)
+                     : [d] "v"(d), [cf] "v"(c0), [lo] "v"(lo), [hi] "v"(hi), D_MOPS);
+        lds_reads_landed();
+        return a;
+    }
+    static __device__ __forceinline__ double fwd_lds0(double d, const double (&m)[16], double c0, double lo, double hi, double &g, double v,
+                                                      double &vnew, double &pri, double &dua) {
+        double a, s, t;
+        asm volatile(D_MOV64 " %[a], %[cf]\n\t" D_HAZ D_CHAIN_IN D_PROJECT
+                     : [a] "=&v"(a), [s] "=&v"(s), [t] "=&v"(t), [sn] "=&v"(vnew), [g] "+v"(g), [pri] "+v"(pri), [dua] "+v"(dua)
+                     : [d] "v"(d), [cf] "v"(c0), [lo] "v"(lo), [hi] "v"(hi), [v] "v"(v), D_MOPS);
+        lds_reads_landed();
+        return a;
+    }
     // Forward step with the row-local block of the PREVIOUS step woven into its chain (layout E): returns a = cf + Mf * [x; d];
     // (ap, g, v, lo, hi) belong to the previous step's slot: ap its element (the `a` that step returned -- usually `x` itself, but
     // the caller decides), g and v are updated in place.
@@ -355,6 +376,19 @@ struct DStep<D_NX, D_NU> {
                      "v_fma_f64 %[rn], %[nrho], %[t], %[lr]\n\t"
                      : [a] "+v"(a), [an] "=&v"(an), [rn] "=&v"(rn), [t] "=&v"(t)
                      : [x] "v"(x), [d] "v"(d), [v2] "v"(v2), [g2] "v"(g2), [rhom] "v"(rhom), [lrmc] "v"(lrmc), [nrho] "s"(nrho), [lr] "v"(lr), D_MOPS);
+        lds_reads_landed();
+    }
+    // ... the same step with the input rows folded into the operator (layout D, references constant over the horizon): the input
+    // columns of m carry -rho * Mb and the accumulator starts carry Mb[:, nx:] * lr, so r_s = -rho * t + lr never has to be formed --
+    // the input-row operand of step s-2 is t itself. Two instructions of tail:
+    //     t = v2 - g2 ;  an = rhom * t + lrmc ;  rn = t
+    static __device__ __forceinline__ void bwd_fold(double &a, double x, double d, const double (&m)[16], double v2, double g2,
+                                                    double rhom, double lrmc, double &an, double &rn) {
+        asm volatile(D_HAZ D_CHAIN
+                     "v_add_f64 %[t], %[v2], -%[g2]\n\t"
+                     "v_fma_f64 %[an], %[rhom], %[t], %[lrmc]\n\t"
+                     : [a] "+v"(a), [an] "=&v"(an), [t] "=&v"(rn)
+                     : [x] "v"(x), [d] "v"(d), [v2] "v"(v2), [g2] "v"(g2), [rhom] "v"(rhom), [lrmc] "v"(lrmc), D_MOPS);
         lds_reads_landed();
     }
     // ... the same step with its tail woven into the chain (layout E)

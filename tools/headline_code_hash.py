@@ -3,8 +3,10 @@ build produced it: sha256 over its instructions (labels renumbered, comments and
 The kernel's speed depends on details of the generated code that no source-level reasoning predicts (+-2.5 % between builds with the
 same instruction mix: profiles/r03_dgroup_ab.txt), so a change of this hash means: run tools/headline_ab.py against the previous
 build on ONE box before believing any number, then record the new hash.
+Each measured state has a record of its own under tests/golden/ (headline_kernel_code*.json); RECORD names the current one. A record
+is never rewritten: a change that moves the headline's code adds a new file, points RECORD at it and records there.
     python tools/headline_code_hash.py            print the hash of the current build
-    python tools/headline_code_hash.py --record   write tests/golden/headline_kernel_code.json (after the A/B)"""
+    python tools/headline_code_hash.py --record   write RECORD (after the A/B)"""
 import hashlib
 import json
 import os
@@ -14,7 +16,9 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KERNEL = "_ZN7tinympc14k_admm_solve_dILi12ELi4ELi50ELb1ELi4ELi25ELb0EEEvNS_11SolveParamsE"
-RECORD = os.path.join(ROOT, "tests", "golden", "headline_kernel_code.json")
+# the current record (the earlier ones stay as the history of measured states: headline_kernel_code.json, the build before knot 0
+# and the backward tail were folded out of the sweeps)
+RECORD = os.path.join(ROOT, "tests", "golden", "headline_kernel_code_d_fold.json")
 
 
 def compiler_version() -> str:
@@ -53,9 +57,9 @@ if __name__ == "__main__":
         sys.exit("no build assembly: run __graft_entry__.build() first")
     print(json.dumps(h, indent=1))
     if "--record" in sys.argv:
-        h["measured"] = ("kernel 1.68-1.69 ms (8,192 x 200 iterations, bench.py on MI355X; profiles/r05_kernel_stats.csv); tools/headline_ab.py, one box, against the "
-                         "build before the sweeps' LDS reads and waits became compiler-tracked (4,349 instructions, asm-issued reads): 1.6872 vs 1.6820 ms "
-                         "(+0.3 %, three interleaved rounds each), profiles/r05_tracked_reads_headline_ab.txt")
+        h["measured"] = ("kernel 1.647 ms avg (8,192 x 200 iterations, bench.py on MI355X; profiles/d_fold_kernel_stats.csv); tools/headline_ab.py, one box, "
+                         "against the build before knot 0 and the backward tail were folded (4,257 instructions): 1.6350 vs 1.6733 ms (-2.3 %), and "
+                         "1.6391 vs 1.6752 ms at TINY_D_PAD=1, four interleaved rounds each, ranges disjoint; profiles/d_fold_headline_ab.txt")
         with open(RECORD, "w") as f:
             json.dump(h, f, indent=1)
             f.write("\n")
