@@ -449,6 +449,7 @@ constexpr int WAVES_PER_GROUP_B = 4;
 bool solve_d_supported(int nx, int nu, int N, bool const_tables);
 hipError_t launch_solve_d(const SolveParams &p, hipStream_t stream);
 hipError_t launch_solve_d_refill(const SolveParams &p, hipStream_t stream);  // tinympc_solve_dr.hip (SolveParams::refill_next set)
+hipError_t launch_solve_d_lean(const SolveParams &p, hipStream_t stream);    // tinympc_lean_d.hip (the plan's lean_applies)
 int solve_d_workgroups(int nu, int N, bool const_tables, int groups);
 size_t solve_d_lds_bytes(int nu, int N, bool const_tables);  // per workgroup
 int solve_d_resident_workgroups(int wpg);  // workgroups of `wpg` wavefronts the device holds at two wavefronts per SIMD (slot refill)

@@ -286,6 +286,23 @@ static bool refill_applies(const tinympc_solver *s, const LaunchPlan &pl) {
     return !jit || solve_jit_refill_supported(s->W, s->nx, s->nu, s->N, ct);  // (run-time specialised shapes: built on first use)
 }
 
+// Lean sweeps (tinympc_lean_d.hip, TINY_LEAN): layout D's compiled-in 16-lane kernels (box path; shared tables or the per-instance
+// goal form), whenever some iteration's residuals cannot be read -- a check interval other than 1 (0: no check at all), or
+// tolerances nothing can meet (forced iteration counts: only the last check of a launch reaches the statistics). With a check in
+// every iteration and reachable tolerances every sweep needs its residuals and the plain kernel stays. Results are bit-identical.
+// TINYMPC_LEAN=0 forces the plain kernel, =1 the lean one wherever it exists.
+static bool lean_applies(const tinympc_solver *s, const LaunchPlan &pl) {
+    if (pl.kernel != KernelId::D_COMPILED || s->W != 16 || pl.adaptive || pl.families || s->zero_copy_tick || s->st.max_iter <= 0)
+        return false;
+    if (refill_applies(s, pl)) return false;
+    const char *env = getenv("TINYMPC_LEAN");
+    const int mode = env ? atoi(env) : -1;
+    if (mode == 0) return false;
+    if (mode == 1) return true;
+    const bool reachable = s->st.abs_pri_tol > 0.0 && s->st.abs_dua_tol > 0.0;
+    return s->st.check_termination != 1 || !reachable;
+}
+
 int launch(tinympc_solver *s, bool timed) {
     int rc;
     s->flag_pending = false;
@@ -399,7 +416,8 @@ int launch(tinympc_solver *s, bool timed) {
             HIP_TRY(launch_solve_jit(p, s->W, s->stream));
             break;
         case KernelId::D_COMPILED:
-            HIP_TRY(s->W == 64 ? launch_solve_dx(p, s->stream) : s->W == 32 ? launch_solve_dw(p, s->stream) : launch_solve_d(p, s->stream));
+            if (lean_applies(s, pl) && !p.x0_mirror && !p.u0_host && !p.refill_next) HIP_TRY(launch_solve_d_lean(p, s->stream));
+            else HIP_TRY(s->W == 64 ? launch_solve_dx(p, s->stream) : s->W == 32 ? launch_solve_dw(p, s->stream) : launch_solve_d(p, s->stream));
             break;
         case KernelId::E:
             p.ctab = s->dctab_e; p.chunk_len = s->e_chunk_len; p.chunk_count = s->e_wpg; p.chunk_levels = 1;
@@ -480,7 +498,8 @@ int tinympc_get_jit_info(tinympc_solver *s, char *buf, int len) {
             strncat(buf, words, (size_t)len - strlen(buf) - 1);
             strncat(buf, " goal", (size_t)len - strlen(buf) - 1);
         } else {
-            snprintf(buf, (size_t)len, "compiled-in layout=%c%s%s", pl.layout, words, pl.kernel == KernelId::D_COMPILED ? " goal" : "");
+            snprintf(buf, (size_t)len, "compiled-in layout=%c%s%s%s", pl.layout, words, pl.kernel == KernelId::D_COMPILED ? " goal" : "",
+                     lean_applies(s, pl) ? " lean" : "");
         }
         return TINYMPC_OK;
     }
@@ -495,7 +514,7 @@ int tinympc_get_jit_info(tinympc_solver *s, char *buf, int len) {
         if ((rc = bind_device(s))) return rc;
         solve_jit_describe(s->W, s->nx, s->nu, s->N, ct, pl.families && !pl.adaptive, pl.adaptive && !pl.families, buf, (size_t)len);
         if (pl.kernel == KernelId::D_JIT && refill_applies(s, pl)) strncat(buf, " slot-refill", (size_t)len - strlen(buf) - 1);
-    } else snprintf(buf, (size_t)len, "compiled-in layout=%c%s", pl.layout, refill_applies(s, pl) ? " slot-refill" : "");
+    } else snprintf(buf, (size_t)len, "compiled-in layout=%c%s%s", pl.layout, refill_applies(s, pl) ? " slot-refill" : "", lean_applies(s, pl) ? " lean" : "");
     return TINYMPC_OK;
 }
 

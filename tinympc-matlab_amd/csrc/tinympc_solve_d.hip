@@ -57,6 +57,21 @@
 #endif
 #endif
 
+// Lean sweeps are a textual variant in the same way (TINY_LEAN: tinympc_lean_d.hip includes this file): an iteration whose
+// residuals nothing can read -- no termination check falls on it, or the tolerances cannot be met and a later check overwrites its
+// snapshot -- runs a forward sweep without the residual maxima (Step::fwd_*_nores), without the "can this sweep still converge" tests
+// and without R1. With reachable = both tolerances > 0 (a launch constant),
+//     need_res(it1) = check(it1) && (reachable || it1 + check_termination > max_iter)
+// and only the iterations with need_res run the sweep of the plain kernel. The lean iteration is an innermost loop of its own (one
+// forward, one backward sweep: what the register allocator sees in the plain kernel, less the residuals' registers); the iteration
+// with residuals follows it in the enclosing loop. Box path only; results are bit-identical to the plain kernel's.
+#ifndef TINY_LEAN
+#define TINY_LEAN 0
+#endif
+#if TINY_LEAN && (TINY_REFILL || defined(TINY_JIT))
+#error "TINY_LEAN: compiled-in plain kernels only"
+#endif
+
 #define TINY_STR2(x) #x
 #define TINY_STR(x) TINY_STR2(x)
 namespace tinympc {
@@ -515,11 +530,20 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
     asm volatile(".p2align " TINY_STR(TINY_D_LOOP_ALIGN) ::: "memory");
 #endif
     const int max_iter = p.max_iter;
+#if TINY_LEAN
+    // One round of the loop below, in two forms: LEAN_ = true without residuals, false the plain kernel's. Returns true when the solve
+    // is over. (Each form is called from one place and inlined there.)
+    auto iteration = [&](auto LEAN_, const int it) __attribute__((always_inline)) -> bool {
+        constexpr bool LEANI = decltype(LEAN_)::value;
+#else
     for (int it = 0; max_iter > 0; ++it) {  // admm.cpp:129
+#endif
         // (readfirstlane: keeps the loop counter and everything derived from it in SGPRs, so that the branches below
         // are scalar branches and not EXEC-masked regions)
         const int it0 = __builtin_amdgcn_readfirstlane(it);
-#if TINY_REFILL
+#if TINY_LEAN
+        const bool final_round = !LEANI && it0 >= max_iter;  // (a lean round is never the last: see the loop behind this lambda)
+#elif TINY_REFILL
         const bool final_round = REFILL ? false : it0 >= max_iter;  // (REFILL: every row has its own count, `fin` below)
 #else
         const bool final_round = it0 >= max_iter;
@@ -666,9 +690,16 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
             }
             pending = false;
         }
+#if TINY_LEAN
+        if (final_round || __ballot(active) == 0ull) return true;
+#else
         if (final_round || __ballot(active) == 0ull) break;
+#endif
         const int it1 = it0 + 1;
-#if TINY_REFILL
+#if TINY_LEAN
+        // (a lean round: no check falls on it, or none that anything can read)
+        const bool check = !LEANI && __builtin_amdgcn_readfirstlane((int)((ct > 0) && ((it1 % ct) == 0))) != 0;
+#elif TINY_REFILL
         // admm.cpp:91 (iter already incremented, :143). REFILL: every row checks by its own count; `check` = some live row does.
         bool chk = true, check_r = false;
         if constexpr (REFILL) {
@@ -732,7 +763,12 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
         // PREVIOUS step's block and retired by the wait behind that block (lds_reads_landed, inside the Step functions).
         double xcur = x0v;
         double dcur = lds_read_async<0>(aD), vcur = 0.0;
+#if TINY_LEAN
+        // (a lean step does not read vold: the read is not issued -- an issued asynchronous read must be consumed behind its wait)
+        if constexpr (VL > 0 && !LEANI) vcur = lds_read_async<0>(aV);
+#else
         if constexpr (VL > 0) vcur = lds_read_async<0>(aV);
+#endif
         // (!CT: bounds that vary over the horizon come from the workgroup's LDS copy of the tables, one step ahead like d)
         double locur = lo_c, hicur = hi_c;
         if constexpr (!CT) {
@@ -744,13 +780,32 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
             constexpr int q = decltype(S)::value;
             double dn = 0.0, vn = 0.0, lon = lo_c, hin = hi_c;
             if constexpr (q + 1 < NS) dn = lds_read_async<(q + 1) * DS * 8>(aD);
+#if TINY_LEAN
+            if constexpr (q + 1 < VL && !LEANI) vn = lds_read_async<(q + 1) * 512>(aV);
+#else
             if constexpr (q + 1 < VL) vn = lds_read_async<(q + 1) * 512>(aV);
+#endif
             if constexpr (!CT && q + 1 < NS) {
                 lon = lds_read_async<(q + 2) * W * 8>(aT);
                 hin = lds_read_async<(TOFF + (q + 2) * W) * 8>(aT);
             }
             const double xprev = xcur;
             double snew_q;
+#if TINY_LEAN
+            if constexpr (LEANI) {  // S1 + D1 without R1's maxima: the clamp goes straight into the slot
+                if constexpr (q >= VL) {
+                    if constexpr (K0 && q == 0) xcur = Step::fwd_reg0_nores(dcur, m, c0, locur, hicur, G[q], Vr[q - VL]);
+                    else xcur = Step::fwd_reg_nores(xcur, dcur, m, cf, locur, hicur, G[q], Vr[q - VL]);
+                    snew_q = Vr[q - VL];
+                } else {
+                    double vnew;
+                    if constexpr (K0 && q == 0) xcur = Step::fwd_lds0_nores(dcur, m, c0, locur, hicur, G[q], vnew);
+                    else xcur = Step::fwd_lds_nores(xcur, dcur, m, cf, locur, hicur, G[q], vnew);
+                    lds_write_async<q * 512>(aV, vnew);
+                    snew_q = vnew;
+                }
+            } else
+#endif
             if constexpr (q >= VL) {
                 if constexpr (K0 && q == 0) xcur = Step::fwd_reg0(dcur, m, c0, locur, hicur, G[q], Vr[q - VL], pri, dua);
                 else xcur = Step::fwd_reg(xcur, dcur, m, cf, locur, hicur, G[q], Vr[q - VL], pri, dua);
@@ -979,7 +1034,31 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
                 lds_write_masked<0>(aD, a, wr_d);  // d_0
             }
         }
+#if TINY_LEAN
+        return false;
+    };
+    // admm.cpp:129. `nres`: the next iteration, counted from 1, whose residuals something reads (need_res, see the top of the file);
+    // the rounds before it are lean, and so is everything behind the last one. All of it scalar.
+    const bool reachable = p.abs_pri_tol > 0.0 && p.abs_dua_tol > 0.0;
+    const int last_check = ct > 0 ? (max_iter / ct) * ct : 0;
+    for (int it = 0; max_iter > 0;) {
+        int nres = max_iter + 1;
+        if (ct > 0 && reachable) nres = (it / ct + 1) * ct;
+        else if (last_check > it) nres = last_check;
+        const int lean_end = __builtin_amdgcn_readfirstlane(nres - 1 < max_iter ? nres - 1 : max_iter);
+        bool over = false;
+        for (; it < lean_end; ++it) {
+            if (iteration(std::true_type{}, it)) {
+                over = true;
+                break;
+            }
+        }
+        if (over || iteration(std::false_type{}, it)) break;
+        ++it;
     }
+#else
+    }
+#endif
     lds_wait();
 #ifdef TINY_CLOCK_STAMP
     // Delta s_memtime (shader cycles) and Delta s_memrealtime (a constant 100 MHz) around the iteration loop, one pair per
@@ -1034,6 +1113,60 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
     }
 }
 
+#if TINY_LEAN
+// (the lean translation unit, tinympc_lean_d.hip: the plain kernel and its per-instance goal form with lean sweeps; tinympc_plan.hip
+// decides when -- lean_applies)
+template <int NX, int NU, int N, bool CT, int WPG, int VL>
+__global__ void __launch_bounds__(64 * WPG) __attribute__((amdgpu_waves_per_eu(2, 2))) k_admm_solve_d_lean(const SolveParams p) {
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    k_admm_solve_d_body<NX, NU, N, CT, WPG, VL>(p, smem);
+}
+template <int NX, int NU, int N, int WPG, int VL>
+__global__ void __launch_bounds__(64 * WPG) __attribute__((amdgpu_waves_per_eu(2, 2))) k_admm_solve_d_gbnd_lean(const SolveParams p) {
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    k_admm_solve_d_body<NX, NU, N, true, WPG, VL, false, false, true, false, false, true>(p, smem);
+}
+
+__host__ __device__ constexpr int d_wpg(int nu, int N, bool ct) { return d_vl(nu, N, ct, 4) >= 0 ? 4 : 8; }  // (as in the plain translation unit)
+
+template <int NX, int NU, int N, bool CT>
+static hipError_t launch_d_one(const SolveParams &p, hipStream_t stream) {
+    constexpr int WPG = d_wpg(NU, N, CT);
+    constexpr int VL = d_vl(NU, N, CT, WPG);
+    if constexpr (VL < 0) {
+        return hipErrorInvalidValue;
+    } else {
+        constexpr size_t lds = d_lds_bytes(NU, N, CT, WPG, VL);
+        static size_t lds_set_l[16] = {0}, lds_set_lgoal[16] = {0};
+        const int wgs = (p.groups + WPG - 1) / WPG;
+        if (p.x0_mirror || p.u0_host || p.refill_next) return hipErrorInvalidValue;  // (the plan keeps those on their own kernels)
+        if (p.iref_pn) {  // per-instance goals (constant tables only)
+            if constexpr (!CT) {
+                return hipErrorInvalidValue;
+            } else {
+                if (!p.iref_lr || !p.ibnd) return hipErrorInvalidValue;
+                auto fn = &k_admm_solve_d_gbnd_lean<NX, NU, N, WPG, VL>;
+                hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void *>(fn), lds, lds_set_lgoal);
+                if (e != hipSuccess) return e;
+                hipLaunchKernelGGL(fn, dim3(wgs), dim3(64 * WPG), lds, stream, p);
+            }
+        } else {
+            auto fn = &k_admm_solve_d_lean<NX, NU, N, CT, WPG, VL>;
+            hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void *>(fn), lds, lds_set_l);
+            if (e != hipSuccess) return e;
+            hipLaunchKernelGGL(fn, dim3(wgs), dim3(64 * WPG), lds, stream, p);
+        }
+        return hipGetLastError();
+    }
+}
+
+hipError_t launch_solve_d_lean(const SolveParams &p, hipStream_t stream) {  // (the shapes of TINY_D_SHAPES in the plain translation unit)
+    if (p.nx == 12 && p.nu == 4 && p.N == 50) return p.const_tables ? launch_d_one<12, 4, 50, true>(p, stream) : launch_d_one<12, 4, 50, false>(p, stream);
+    if (p.nx == 4 && p.nu == 1 && p.N == 20) return p.const_tables ? launch_d_one<4, 1, 20, true>(p, stream) : launch_d_one<4, 1, 20, false>(p, stream);
+    if (p.nx == 4 && p.nu == 1 && p.N == 10) return p.const_tables ? launch_d_one<4, 1, 10, true>(p, stream) : launch_d_one<4, 1, 10, false>(p, stream);
+    return hipErrorInvalidValue;
+}
+#else  // the plain and the slot-refill kernels, their launchers, the run-time specialised entry point
 #ifndef TINY_JIT
 #if TINY_REFILL
 template <int NX, int NU, int N, bool CT, int WPG, int VL>
@@ -1235,5 +1368,6 @@ int solve_d_workgroups(int nu, int N, bool const_tables, int groups) {
 #endif  // TINY_REFILL
 
 #endif  // TINY_JIT
+#endif  // TINY_LEAN
 
 }  // namespace tinympc

@@ -18,7 +18,7 @@
 //
 // DPP hazard (a VGPR written by VALU must not be read through DPP within 2 wait states; nothing guards it inside
 // inline asm): `x` is the `a` the previous block's chain wrote; forward blocks end with >= 8 non-DPP instructions
-// after that write, backward blocks with 3 (2 in the folded form, bwd_fold). tests/test_isa_hazards.py checks the generated code.
+// after that write (4 in the lean steps, fwd_*_nores), backward blocks with 3 (2 in the folded form, bwd_fold). tests/test_isa_hazards.py checks the generated code.
 #if !defined(D_NX) || !defined(D_NU)
 #error "define D_NX and D_NU before including tinympc_solve_d_chain.h"
 #endif
@@ -262,6 +262,12 @@
     "v_max_f64 %[pri], %[pri], |%[t]|\n\t"         \
     "v_add_f64 %[t], %[v], -%[sn]\n\t"             \
     "v_max_f64 %[dua], %[dua], |%[t]|\n\t"
+// S1 + D1 alone (DStep::fwd_*_nores): the first four instructions of D_PROJECT, same order, same operands.
+#define D_PROJECT_NORES                            \
+    "v_add_f64 %[s], %[a], %[g]\n\t"               \
+    "v_max_f64 %[sn], %[lo], %[s]\n\t"             \
+    "v_min_f64 %[sn], %[hi], %[sn]\n\t"            \
+    "v_add_f64 %[g], %[s], -%[sn]\n\t"
 // The same row-local block for the element of the PREVIOUS step (%[ap], its slot's g / v / bounds), woven into the chain of the
 // current step one instruction per column (layout E, round 4): the block is a dependent sequence of its own, the chain another, and a
 // wavefront issues in order -- back to back each instruction waits for its predecessor's result (~8 cycles for FP64), interleaved
@@ -328,6 +334,45 @@ struct DStep<D_NX, D_NU> {
         asm volatile(D_MOV64 " %[a], %[cf]\n\t" D_HAZ D_CHAIN_IN D_PROJECT
                      : [a] "=&v"(a), [s] "=&v"(s), [t] "=&v"(t), [sn] "=&v"(vnew), [g] "+v"(g), [pri] "+v"(pri), [dua] "+v"(dua)
                      : [d] "v"(d), [cf] "v"(c0), [lo] "v"(lo), [hi] "v"(hi), [v] "v"(v), D_MOPS);
+        lds_reads_landed();
+        return a;
+    }
+    // The four forward steps without the residual maxima (the lean sweeps of tinympc_lean_d.hip: iterations whose residuals nothing
+    // can read). The first four instructions of D_PROJECT on the same operands -- a, sn and g are bit-identical to the full step's --, the
+    // clamp written straight into the slack's register: no vold, no hand-over copy. v stays a "+v" operand although its old value is
+    // not read, so that the slot keeps its register across the iteration loop's back edge. Four non-DPP instructions follow the
+    // chain's last write; every block is a multiple of 8 bytes with what the caller puts around it, as fwd_reg / fwd_lds.
+    static __device__ __forceinline__ double fwd_reg_nores(double x, double d, const double (&m)[16], double cf, double lo, double hi, double &g,
+                                                           double &v) {
+        double a, s;
+        asm volatile("v_mov_b64 %[a], %[cf]\n\t" D_HAZ D_CHAIN D_PROJECT_NORES
+                     : [a] "=&v"(a), [s] "=&v"(s), [g] "+v"(g), [sn] "+v"(v)
+                     : [x] "v"(x), [d] "v"(d), [cf] "v"(cf), [lo] "v"(lo), [hi] "v"(hi), D_MOPS);
+        lds_reads_landed();
+        return a;
+    }
+    static __device__ __forceinline__ double fwd_lds_nores(double x, double d, const double (&m)[16], double cf, double lo, double hi, double &g,
+                                                           double &vnew) {
+        double a, s;
+        asm volatile(D_MOV64 " %[a], %[cf]\n\t" D_HAZ D_CHAIN D_PROJECT_NORES
+                     : [a] "=&v"(a), [s] "=&v"(s), [g] "+v"(g), [sn] "=&v"(vnew)
+                     : [x] "v"(x), [d] "v"(d), [cf] "v"(cf), [lo] "v"(lo), [hi] "v"(hi), D_MOPS);
+        lds_reads_landed();
+        return a;
+    }
+    static __device__ __forceinline__ double fwd_reg0_nores(double d, const double (&m)[16], double c0, double lo, double hi, double &g, double &v) {
+        double a, s;
+        asm volatile("v_mov_b64 %[a], %[cf]\n\t" D_HAZ D_CHAIN_IN D_PROJECT_NORES
+                     : [a] "=&v"(a), [s] "=&v"(s), [g] "+v"(g), [sn] "+v"(v)
+                     : [d] "v"(d), [cf] "v"(c0), [lo] "v"(lo), [hi] "v"(hi), D_MOPS);
+        lds_reads_landed();
+        return a;
+    }
+    static __device__ __forceinline__ double fwd_lds0_nores(double d, const double (&m)[16], double c0, double lo, double hi, double &g, double &vnew) {
+        double a, s;
+        asm volatile(D_MOV64 " %[a], %[cf]\n\t" D_HAZ D_CHAIN_IN D_PROJECT_NORES
+                     : [a] "=&v"(a), [s] "=&v"(s), [g] "+v"(g), [sn] "=&v"(vnew)
+                     : [d] "v"(d), [cf] "v"(c0), [lo] "v"(lo), [hi] "v"(hi), D_MOPS);
         lds_reads_landed();
         return a;
     }
@@ -468,6 +513,7 @@ struct DStep<D_NX, D_NU> {
 #undef D_CHAIN_IN
 #undef D_MOPS
 #undef D_PROJECT
+#undef D_PROJECT_NORES
 #undef D_P1
 #undef D_P2
 #undef D_P3

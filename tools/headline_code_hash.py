@@ -5,8 +5,11 @@ same instruction mix: profiles/r03_dgroup_ab.txt), so a change of this hash mean
 build on ONE box before believing any number, then record the new hash.
 Each measured state has a record of its own under tests/golden/ (headline_kernel_code*.json); RECORD names the current one. A record
 is never rewritten: a change that moves the headline's code adds a new file, points RECORD at it and records there.
-    python tools/headline_code_hash.py            print the hash of the current build
-    python tools/headline_code_hash.py --record   write RECORD (after the A/B)"""
+The lean form of the same kernel (k_admm_solve_d_lean<12, 4, 50, true, 4, 25>, tinympc_lean_d.hip: what the headline runs since its
+sweeps dropped the residual maxima nothing reads) has a record of its own, RECORD_LEAN, with the same rules.
+    python tools/headline_code_hash.py                 print the hashes of the current build
+    python tools/headline_code_hash.py --record        write RECORD (after the A/B)
+    python tools/headline_code_hash.py --record-lean   write RECORD_LEAN (after the A/B)"""
 import hashlib
 import json
 import os
@@ -19,6 +22,14 @@ KERNEL = "_ZN7tinympc14k_admm_solve_dILi12ELi4ELi50ELb1ELi4ELi25ELb0EEEvNS_11Sol
 # the current record (the earlier ones stay as the history of measured states: headline_kernel_code.json, the build before knot 0
 # and the backward tail were folded out of the sweeps)
 RECORD = os.path.join(ROOT, "tests", "golden", "headline_kernel_code_d_fold.json")
+KERNEL_LEAN = "_ZN7tinympc19k_admm_solve_d_leanILi12ELi4ELi50ELb1ELi4ELi25EEEvNS_11SolveParamsE"
+SOURCE_LEAN = "tinympc_lean_d.hip"
+RECORD_LEAN = os.path.join(ROOT, "tests", "golden", "headline_kernel_code_d_lean.json")
+# what was measured for the lean kernel's recorded code (profiles/d_lean_headline_ab.txt)
+LEAN_MEASURED = ("kernel 1.436 ms avg (8,192 x 200 iterations, bench.py on MI355X; profiles/d_lean_kernel_stats.csv); tools/headline_ab.py, one box, against "
+                 "the parent build's plain kernel (4,249 instructions, headline_kernel_code_d_fold.json): 1.4326 vs 1.6376 ms (-12.5 %), and 1.4310 vs "
+                 "1.6334 ms at TINY_D_PAD=1, four interleaved rounds each, ranges disjoint; 786.1 M against 892.8 M VALU instructions per launch; "
+                 "profiles/d_lean_headline_ab.txt")
 
 
 def compiler_version() -> str:
@@ -30,14 +41,14 @@ def compiler_version() -> str:
     return m.group(0).strip() if m else out.strip().splitlines()[0]
 
 
-def current_hash() -> dict | None:
+def current_hash(kernel: str = KERNEL, source: str = "tinympc_solve_d.hip") -> dict | None:
     sys.path.insert(0, ROOT)
     import __graft_entry__ as ge
-    path = ge.device_asm_path("tinympc_solve_d.hip")
+    path = ge.device_asm_path(source)
     if not os.path.exists(path):
         return None
     text = open(path).read()
-    m = re.search(r"^%s:(.*?)^\.Lfunc_end" % re.escape(KERNEL), text, re.S | re.M)
+    m = re.search(r"^%s:(.*?)^\.Lfunc_end" % re.escape(kernel), text, re.S | re.M)
     if not m:
         return None
     lines = []
@@ -47,7 +58,7 @@ def current_hash() -> dict | None:
             lines.append("L:")
         elif t.startswith("\t") and not t.strip().startswith("."):
             lines.append(re.sub(r"\.LBB\d+_\d+", ".LBB", t.strip()))
-    return {"kernel": KERNEL, "instructions": sum(1 for x in lines if x != "L:"), "sha256": hashlib.sha256("\n".join(lines).encode()).hexdigest(),
+    return {"kernel": kernel, "instructions": sum(1 for x in lines if x != "L:"), "sha256": hashlib.sha256("\n".join(lines).encode()).hexdigest(),
             "compiler": compiler_version()}
 
 
@@ -56,6 +67,9 @@ if __name__ == "__main__":
     if h is None:
         sys.exit("no build assembly: run __graft_entry__.build() first")
     print(json.dumps(h, indent=1))
+    lean = current_hash(KERNEL_LEAN, SOURCE_LEAN)
+    if lean is not None:
+        print(json.dumps(lean, indent=1))
     if "--record" in sys.argv:
         h["measured"] = ("kernel 1.647 ms avg (8,192 x 200 iterations, bench.py on MI355X; profiles/d_fold_kernel_stats.csv); tools/headline_ab.py, one box, "
                          "against the build before knot 0 and the backward tail were folded (4,257 instructions): 1.6350 vs 1.6733 ms (-2.3 %), and "
@@ -64,3 +78,11 @@ if __name__ == "__main__":
             json.dump(h, f, indent=1)
             f.write("\n")
         print("recorded", RECORD)
+    if "--record-lean" in sys.argv:
+        if lean is None:
+            sys.exit("no assembly of the lean kernel: run __graft_entry__.build() first")
+        lean["measured"] = LEAN_MEASURED
+        with open(RECORD_LEAN, "w") as f:
+            json.dump(lean, f, indent=1)
+            f.write("\n")
+        print("recorded", RECORD_LEAN)
