@@ -204,7 +204,7 @@ int tinympc_get_residuals(tinympc_solver *s, double residuals[4]);
 
 /* Batched setup: `batch` independent MPC instances sharing (A,B,fdyn,Q,R,rho,settings) and, by default, bounds and refs,
  * each with its own x0 and its own persistent ADMM state (references per instance: tinympc_set_x_ref_batch below; bounds per
- * instance: tinympc_set_bound_constraints_batch below). device < 0 keeps the current HIP device. */
+ * instance: tinympc_set_bound_constraints_batch below; models per instance: tinympc_set_model_batch below). device < 0 keeps the current HIP device. */
 int tinympc_setup_batch(tinympc_solver **out, const double *A, const double *B, const double *fdyn,
                         const double *Q, const double *R, double rho, int nx, int nu, int N,
                         int batch, int device, int verbose);
@@ -251,6 +251,33 @@ int tinympc_set_bound_constraints_batch(tinympc_solver *s, const double *x_min, 
 /* Same, from device memory on the handle's GPU; same contract as tinympc_set_x0_batch_device. */
 int tinympc_set_bound_constraints_batch_device(tinympc_solver *s, const double *d_x_min, const double *d_x_max,
                                                const double *d_u_min, const double *d_u_max, int cols, int first, int count);
+
+/* Per-instance models for instances [first, first+count) of a batched handle.
+ * A: nx*nx*count, B: nx*nu*count, fdyn: nx*count (NULL = zeros), Q: nx*nx*count, R: nu*nu*count; column-major, instance b's block
+ * at b*(block size); of Q and R only the diagonals are used, as in tinympc_setup. rho, N and the settings stay the handle's.
+ * Instance b then solves exactly what a single-instance handle set up with (A_b, B_b, fdyn_b, Q_b, R_b, rho) would solve: its LQR
+ * cache is computed on the device by the kernels of tinympc_setup, one wavefront or workgroup per instance in one launch, and is
+ * bit-identical to that handle's. The first call turns per-instance mode on; instances outside the range keep the handle's shared
+ * model (and cache) of that moment. tinympc_clear_model_batch returns every instance to the shared model. reset_workspace,
+ * update_settings, the reference and bound verbs (shared and per-instance), the solve verbs and mpc_step_batch keep the mode. The
+ * single-model verbs (get_cache, set_cache_terms, set_sensitivity_matrices, codegen*, compute_cache_terms, solve_lqr,
+ * compute_sensitivity, print_problem_data) keep addressing the SHARED model and cache; tinympc_get_cache_batch reads per instance.
+ * The mode runs on layout A, whatever the form of references and bounds. With the cone / linear families, adaptive rho or
+ * nx+nu > 64 a solve returns TINYMPC_ERR_UNSUPPORTED (never a solve with the shared model), and so does tinympc_session_begin.
+ * Invalid arguments (a NULL A, B, Q or R, a range beyond the batch, count < 1, host memory handed to the _device form) return
+ * TINYMPC_ERR_INVALID_INPUT and leave the mode as it was. Single-instance handles: the same, on instance 0. The input has been copied
+ * when the call returns. */
+int tinympc_set_model_batch(tinympc_solver *s, const double *A, const double *B, const double *fdyn,
+                            const double *Q, const double *R, int first, int count);
+/* Same, from device memory on the handle's GPU; same contract as tinympc_set_x0_batch_device. */
+int tinympc_set_model_batch_device(tinympc_solver *s, const double *d_A, const double *d_B, const double *d_fdyn,
+                                   const double *d_Q, const double *d_R, int first, int count);
+/* Every instance back on the shared model that setup installed. */
+int tinympc_clear_model_batch(tinympc_solver *s);
+/* The LQR cache of instances [first, first+count): Kinf nu*nx*count, Pinf nx*nx*count, Quu_inv nu*nu*count, AmBKt nx*nx*count,
+ * riccati_iters[count]; any pointer may be NULL. Without per-instance models: the shared cache, repeated. */
+int tinympc_get_cache_batch(tinympc_solver *s, double *Kinf, double *Pinf, double *Quu_inv, double *AmBKt,
+                            int *riccati_iters, int first, int count);
 
 /* Zero the persistent ADMM state (cold start) of every instance and put every instance's rho back to
  * the setup value; x0 is kept. */

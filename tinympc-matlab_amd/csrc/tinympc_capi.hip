@@ -427,7 +427,7 @@ static int print_solve_result(tinympc_solver *s) {
 int tinympc_solve(tinympc_solver *s, int verbose) {
     int rc = check_handle(s);
     if (rc) return rc;
-    if (s->resident_solves && !s->resident_refused && s->host_path()) {
+    if (s->resident_solves && !s->resident_refused && s->host_path() && !s->inst.models) {  // (per-instance models: launched solves)
         if (!s->session_active) {
             rc = tinympc_session_begin(s);
             if (rc == TINYMPC_ERR_UNSUPPORTED || rc == TINYMPC_ERR_INVALID_INPUT) s->resident_refused = true;  // (launched solves from here on)
@@ -1014,24 +1014,11 @@ struct InstArray {
 // The per-instance stores of `a`, the table rows (SolveParams::iref_lr / iref_pn / ibnd) and, for the bounds, layout A's clamp rows:
 // allocated at the first per-instance verb that needs them.
 int alloc_inst_state(tinympc_solver *s, const InstArray *a, int n, bool bounds) {
-    InstState &in = s->inst;
+    const InstState &in = s->inst;
     int rc;
     for (int i = 0; i < n; ++i)
         if (!*a[i].store && (rc = dalloc(s, a[i].store, (size_t)a[i].rows * a[i].cols * s->batch))) return rc;
-    const size_t lr = inst_lr_doubles(s->groups, s->N), row = (size_t)s->groups * 64, bnd = inst_bnd_doubles(s->groups, s->N);
-    if (!in.lr) {
-        if ((rc = dalloc(s, &in.lr, lr)) || (rc = dalloc(s, &in.pn, row)) || (rc = dalloc(s, &in.lrg, row)) || (rc = dalloc(s, &in.bndg, 2 * row)))
-            return rc;
-        HIP_TRY(hipMemsetAsync(in.lr, 0, sizeof(double) * lr, s->stream));
-        HIP_TRY(hipMemsetAsync(in.pn, 0, sizeof(double) * row, s->stream));
-        HIP_TRY(hipMemsetAsync(in.lrg, 0, sizeof(double) * row, s->stream));
-        HIP_TRY(hipMemsetAsync(in.bndg, 0, sizeof(double) * 2 * row, s->stream));
-    }
-    if (bounds && !in.bnd) {
-        if ((rc = dalloc(s, &in.bnd, bnd))) return rc;
-        HIP_TRY(hipMemsetAsync(in.bnd, 0, sizeof(double) * bnd, s->stream));
-    }
-    return TINYMPC_OK;
+    return alloc_inst_rows(s, bounds || in.models);
 }
 
 // The one upload path of the per-instance verbs: arrays a[0, n) of instances [first, first+count), per knot or one column each
@@ -1185,6 +1172,189 @@ int tinympc_set_x_ref_batch_device(tinympc_solver *s, const double *d_Xrefs, int
 }
 int tinympc_set_u_ref_batch_device(tinympc_solver *s, const double *d_Urefs, int rows, int cols, int first, int count) {
     return set_ref_batch(s, false, d_Urefs, true, rows, cols, first, count);
+}
+
+namespace {
+
+// Batched precompute + operator builder for instances [first, first+count) of the per-instance model store (InstState): one wavefront
+// (k_precompute_rows) or workgroup (k_precompute) per instance -- the kernels, and so the caches, of a single-instance setup.
+int precompute_inst_models(tinympc_solver *s, int first, int count) {
+    InstState &in = s->inst;
+    const size_t nx = s->nx, nu = s->nu;
+    const char *env = getenv("TINYMPC_PRECOMPUTE");
+    const bool rows = precompute_rows_supported(s->nx, s->nu) && !(env && (env[0] == 'l' || env[0] == 'L'));
+    const size_t ws = precompute_scratch_doubles(s->nx, s->nu) + 8;
+    const bool use_lds = precompute_scratch_doubles(s->nx, s->nu) <= 6500;
+    // (working sets beyond LDS live in global scratch: at most kChunk instances per launch share one block of it)
+    constexpr int kChunk = 256;
+    const int chunk = (rows || use_lds) ? count : kChunk;
+    int rc;
+    if (!rows && !use_lds && !in.mscratch && (rc = dalloc(s, &in.mscratch, ws * kChunk))) return rc;
+    for (int b0 = first; b0 < first + count; b0 += chunk) {
+        const int n = first + count - b0 < chunk ? first + count - b0 : chunk;
+        PrecomputeParams p{};
+        p.nx = s->nx; p.nu = s->nu; p.rho = s->rho;
+        p.A = in.mA + b0 * nx * nx; p.B = in.mB + b0 * nx * nu; p.fdyn = in.mf + b0 * nx; p.Qd = in.mQd + b0 * nx; p.Rd = in.mRd + b0 * nu;
+        p.Kinf = in.cK + b0 * nu * nx; p.Pinf = in.cP + b0 * nx * nx; p.Quu_inv = in.cQuu + b0 * nu * nu; p.AmBKt = in.cAm + b0 * nx * nx;
+        p.APf = in.cAPf + b0 * nx; p.BPf = in.cBPf + b0 * nu;
+        p.info = in.cinfo + (size_t)b0 * 4; p.scratch = in.mscratch; p.scratch_stride = ws;
+        p.use_lds = use_lds ? 1 : 0;
+        p.count = n;
+        if (rows) HIP_TRY(launch_precompute_rows(p, s->stream));
+        else HIP_TRY(launch_precompute(p, s->stream));
+    }
+    OperatorParams o{};
+    o.nx = s->nx; o.nu = s->nu; o.W = s->W; o.KT = s->KT;
+    o.A = in.mA + first * nx * nx; o.B = in.mB + first * nx * nu; o.fdyn = in.mf + first * nx; o.Qd = in.mQd + first * nx; o.Rd = in.mRd + first * nu;
+    o.Kinf = in.cK + first * nu * nx; o.Quu_inv = in.cQuu + first * nu * nu; o.AmBKt = in.cAm + first * nx * nx;
+    o.APf = in.cAPf + first * nx; o.BPf = in.cBPf + first * nu;
+    o.ops = in.ops + (size_t)first * ops_doubles(s->W, s->KT);
+    o.count = count;
+    HIP_TRY(launch_build_operators(o, s->stream));
+    return TINYMPC_OK;
+}
+
+// tinympc_set_model_batch (+ _device). The mode enters at the first call: every instance then holds the shared model, cache and
+// operators of that moment; the instances named here get their own (precompute_inst_models), and their table rows are rebuilt at the
+// next launch from their own Pinf and cost diagonals (refresh_inst_tables).
+int set_model_batch(tinympc_solver *s, const double *A, const double *B, const double *fdyn, const double *Q, const double *R, bool on_device,
+                    int first, int count) {
+    const char *verb = on_device ? "set_model_batch_device" : "set_model_batch";
+    int rc = check_handle(s);
+    if (rc) return rc;
+    if (!A || !B || !Q || !R) return fail(TINYMPC_ERR_INVALID_INPUT, "%s requires A, B, Q, R", verb);
+    if (first < 0 || count < 1 || first + count > s->batch)
+        return fail(TINYMPC_ERR_INVALID_INPUT, "%s: instance range [%d, %d) is empty or outside batch of %d", verb, first, first + count, s->batch);
+    const double *src[5] = {A, B, fdyn, Q, R};
+    for (int i = 0; on_device && i < 5; ++i) {  // device memory of the handle's own GPU (a host pointer or another GPU's memory is refused here)
+        if (!src[i]) continue;
+        hipPointerAttribute_t attr{};
+        const hipError_t e = hipPointerGetAttributes(&attr, src[i]);
+        (void)hipGetLastError();
+        if (e != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != s->device)
+            return fail(TINYMPC_ERR_INVALID_INPUT, "%s: the models are not device memory of the handle's GPU %d", verb, s->device);
+    }
+    if ((rc = bind_device(s))) return rc;
+    InstState &in = s->inst;
+    if (s->layout_m) {  // (no kernel carries them: the next launch refuses until tinympc_clear_model_batch)
+        in.models = true;
+        return TINYMPC_OK;
+    }
+    const size_t nx = s->nx, nu = s->nu, batch = s->batch, od = ops_doubles(s->W, s->KT);
+    if (!in.ops) {
+        if ((rc = dalloc(s, &in.mA, nx * nx * batch)) || (rc = dalloc(s, &in.mB, nx * nu * batch)) || (rc = dalloc(s, &in.mf, nx * batch)) ||
+            (rc = dalloc(s, &in.mQd, nx * batch)) || (rc = dalloc(s, &in.mRd, nu * batch)) || (rc = dalloc(s, &in.cK, nu * nx * batch)) ||
+            (rc = dalloc(s, &in.cP, nx * nx * batch)) || (rc = dalloc(s, &in.cQuu, nu * nu * batch)) || (rc = dalloc(s, &in.cAm, nx * nx * batch)) ||
+            (rc = dalloc(s, &in.cAPf, nx * batch)) || (rc = dalloc(s, &in.cBPf, nu * batch)) || (rc = dalloc(s, &in.cinfo, 4 * batch)) ||
+            (rc = dalloc(s, &in.mstage, (nx + nu) * batch)) || (rc = dalloc(s, &in.ops, od * batch)))
+            return rc;
+        HIP_TRY(hipMemsetAsync(in.cinfo, 0, sizeof(int) * 4 * batch, s->stream));
+    }
+    if ((rc = alloc_inst_rows(s, true))) return rc;
+    if (!in.models) {  // every instance starts from the shared model of this moment
+        // (references a single-instance handle holds in pinned host memory: the per-instance rows are built from the device copies)
+        if (s->refs_on_host && (rc = flush_host_refs(s))) return rc;
+        if ((rc = refresh_derived(s))) return rc;  // (the shared operator block, from the shared cache as it is now)
+        InstModelFillParams f{};
+        f.batch = s->batch;
+        const struct { const double *src; double *dst; size_t n; } seg[] = {
+            {s->dA, in.mA, nx * nx}, {s->dB, in.mB, nx * nu}, {s->dfdyn, in.mf, nx}, {s->dQd, in.mQd, nx}, {s->dRd, in.mRd, nu},
+            {s->dKinf, in.cK, nu * nx}, {s->dPinf, in.cP, nx * nx}, {s->dQuu, in.cQuu, nu * nu}, {s->dAmBKt, in.cAm, nx * nx},
+            {s->dAPf, in.cAPf, nx}, {s->dBPf, in.cBPf, nu}, {s->dops, in.ops, od}};
+        f.nseg = 12;
+        for (int i = 0; i < 12; ++i) { f.seg[i].src = seg[i].src; f.seg[i].dst = seg[i].dst; f.seg[i].n = (int)seg[i].n; }
+        f.info_src = s->dinfo; f.info_dst = in.cinfo;
+        HIP_TRY(launch_fill_inst_models(f, s->stream));
+        in.models = true;
+        in.mark(0, s->batch);
+    }
+    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    HIP_TRY(hipMemcpyAsync(in.mA + first * nx * nx, A, sizeof(double) * nx * nx * count, kind, s->stream));
+    HIP_TRY(hipMemcpyAsync(in.mB + first * nx * nu, B, sizeof(double) * nx * nu * count, kind, s->stream));
+    if (fdyn) HIP_TRY(hipMemcpyAsync(in.mf + first * nx, fdyn, sizeof(double) * nx * count, kind, s->stream));
+    else HIP_TRY(hipMemsetAsync(in.mf + first * nx, 0, sizeof(double) * nx * count, s->stream));
+    // the cost diagonals, each + rho (tiny_api.cpp:90-91): from the caller's device memory as it lies, from host memory gathered first
+    std::vector<double> hd;
+    InstDiagParams dq{}, dr{};
+    dq.n = s->nx; dr.n = s->nu;
+    dq.first = dr.first = first; dq.count = dr.count = count; dq.add = dr.add = s->rho;
+    dq.dst = in.mQd; dr.dst = in.mRd;
+    if (on_device) {
+        dq.src = Q; dq.src_stride = nx * nx; dq.src_step = s->nx + 1;
+        dr.src = R; dr.src_stride = nu * nu; dr.src_step = s->nu + 1;
+    } else {
+        hd.resize((nx + nu) * count);
+        for (size_t b = 0; b < (size_t)count; ++b) {
+            for (size_t i = 0; i < nx; ++i) hd[b * nx + i] = Q[b * nx * nx + i * (nx + 1)];
+            for (size_t i = 0; i < nu; ++i) hd[nx * count + b * nu + i] = R[b * nu * nu + i * (nu + 1)];
+        }
+        HIP_TRY(hipMemcpyAsync(in.mstage, hd.data(), sizeof(double) * hd.size(), hipMemcpyHostToDevice, s->stream));
+        dq.src = in.mstage; dq.src_stride = nx; dq.src_step = 1;
+        dr.src = in.mstage + nx * count; dr.src_stride = nu; dr.src_step = 1;
+    }
+    HIP_TRY(launch_store_inst_diag(dq, s->stream));
+    HIP_TRY(launch_store_inst_diag(dr, s->stream));
+    if ((rc = precompute_inst_models(s, first, count))) return rc;
+    in.mark(first, first + count);
+    // the caller keeps ownership of its buffers: the copies have completed when the call returns (the tinympc_set_x0_batch_device rule)
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return TINYMPC_OK;
+}
+
+}  // namespace
+
+int tinympc_set_model_batch(tinympc_solver *s, const double *A, const double *B, const double *fdyn, const double *Q, const double *R,
+                            int first, int count) {
+    return set_model_batch(s, A, B, fdyn, Q, R, false, first, count);
+}
+int tinympc_set_model_batch_device(tinympc_solver *s, const double *d_A, const double *d_B, const double *d_fdyn, const double *d_Q,
+                                   const double *d_R, int first, int count) {
+    return set_model_batch(s, d_A, d_B, d_fdyn, d_Q, d_R, true, first, count);
+}
+
+int tinympc_clear_model_batch(tinympc_solver *s) {
+    int rc = check_handle(s);
+    if (rc) return rc;
+    if (!s->inst.models) return TINYMPC_OK;
+    s->inst.models = false;
+    // the rows that stay in use (per-instance references / bounds) are built from the shared Pinf and cost diagonals again
+    if (s->inst_tables()) s->inst.mark(0, s->batch);
+    return TINYMPC_OK;
+}
+
+int tinympc_get_cache_batch(tinympc_solver *s, double *Kinf, double *Pinf, double *Quu_inv, double *AmBKt, int *riccati_iters,
+                            int first, int count) {
+    int rc = check_handle(s);
+    if (rc) return rc;
+    if (first < 0 || count < 0 || first + count > s->batch)
+        return fail(TINYMPC_ERR_INVALID_INPUT, "get_cache_batch: instance range [%d, %d) outside batch of %d", first, first + count, s->batch);
+    if ((rc = bind_device(s))) return rc;
+    const size_t nx = s->nx, nu = s->nu, n = (size_t)count;
+    const InstState &in = s->inst;
+    if (in.models && in.ops) {
+        if (Kinf && (rc = download(s, Kinf, in.cK + first * nu * nx, sizeof(double) * nu * nx * n))) return rc;
+        if (Pinf && (rc = download(s, Pinf, in.cP + first * nx * nx, sizeof(double) * nx * nx * n))) return rc;
+        if (Quu_inv && (rc = download(s, Quu_inv, in.cQuu + first * nu * nu, sizeof(double) * nu * nu * n))) return rc;
+        if (AmBKt && (rc = download(s, AmBKt, in.cAm + first * nx * nx, sizeof(double) * nx * nx * n))) return rc;
+        if (riccati_iters) {
+            std::vector<int> info(4 * n);
+            if (n && (rc = download(s, info.data(), in.cinfo + (size_t)first * 4, sizeof(int) * 4 * n))) return rc;
+            for (size_t b = 0; b < n; ++b) riccati_iters[b] = info[4 * b];
+        }
+        return TINYMPC_OK;
+    }
+    // without per-instance models: the shared cache, repeated
+    if (n == 0) return TINYMPC_OK;
+    int it = 0;
+    if ((rc = tinympc_get_cache(s, Kinf, Pinf, Quu_inv, AmBKt, riccati_iters ? &it : nullptr))) return rc;
+    for (size_t b = 1; b < n; ++b) {
+        if (Kinf) std::memcpy(Kinf + b * nu * nx, Kinf, sizeof(double) * nu * nx);
+        if (Pinf) std::memcpy(Pinf + b * nx * nx, Pinf, sizeof(double) * nx * nx);
+        if (Quu_inv) std::memcpy(Quu_inv + b * nu * nu, Quu_inv, sizeof(double) * nu * nu);
+        if (AmBKt) std::memcpy(AmBKt + b * nx * nx, AmBKt, sizeof(double) * nx * nx);
+    }
+    for (size_t b = 0; riccati_iters && b < n; ++b) riccati_iters[b] = it;
+    return TINYMPC_OK;
 }
 
 int tinympc_reset_workspace(tinympc_solver *s) {

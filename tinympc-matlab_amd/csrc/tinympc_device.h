@@ -51,6 +51,12 @@ struct PrecomputeParams {
     int *info;        // info[0] = Riccati steps taken
     double *scratch;  // global scratch, used when the working set does not fit in LDS
     int use_lds;
+    // The batched form (per-instance models, tinympc_set_model_batch): `count` systems in one launch, one wavefront (k_precompute_rows)
+    // or workgroup (k_precompute) each, blockIdx.x selecting the system. System b's blocks lie b * (block size) behind the pointers
+    // above -- nx*nx (A, Pinf, AmBKt), nx*nu (B, Kinf), nx (fdyn, Qd, APf), nu (Rd, BPf), nu*nu (Quu_inv) --, its info at
+    // info + 4 b, its scratch at scratch + b * scratch_stride. 0: the one system of tinympc_setup, the launch as it always was.
+    int count;
+    size_t scratch_stride;
 };
 
 // The .m class's own Riccati recursions (TinyMPC.m:194-221 compute_cache_terms, :336-366 solve_lqr): full Q
@@ -83,6 +89,7 @@ struct OperatorParams {
     int nx, nu, W, KT;
     const double *A, *B, *fdyn, *Qd, *Rd, *Kinf, *Quu_inv, *AmBKt, *APf, *BPf;
     double *ops;
+    int count;  // the batched form, as in PrecomputeParams: system blockIdx.x of `count`, ops at ops + b * ops_doubles(W, KT); 0: one system
 };
 
 struct TableParams {
@@ -257,6 +264,23 @@ struct InstRefStoreParams {
     int first, count;
     double *dst;        // [batch][cols][rows]
 };
+// Per-instance models (tinympc_set_model_batch): every per-instance array <- the shared model, cache and operator block (when the mode
+// begins). seg: up to 12 arrays of doubles, dst [batch][n] <- src [n]; the Riccati step count goes to info [batch][4].
+struct InstModelFillParams {
+    int batch, nseg;
+    struct { const double *src; double *dst; int n; } seg[12];
+    const int *info_src;
+    int *info_dst;
+};
+// dst[(first + b) * n + i] = src[b * src_stride + i * src_step] + add, b < count: the cost diagonals of per-instance models (+ rho,
+// tiny_api.cpp:90-91) from full matrices (stride n*n, step n+1) or from staged diagonals (stride n, step 1)
+struct InstDiagParams {
+    const double *src;
+    size_t src_stride;
+    int src_step, n, first, count;
+    double add;
+    double *dst;
+};
 struct InstTableParams {
     int nx, nu, N, W, KT, groups;
     int en_state_bound, en_input_bound;
@@ -264,6 +288,8 @@ struct InstTableParams {
     const double *Xi, *Ui;            // per-instance references, or NULL: that half is the shared one
     const double *Xref, *Uref, *Pinf;  // shared references, Pinf for pNref
     const double *ops;                // for dg[]
+    // per-instance models: instance b's Pinf at Pinf + b * pinf_stride, its operator block at ops + b * ops_stride (0: shared)
+    size_t pinf_stride, ops_stride;
     // bounds: the per-instance store (x_min | x_max | u_min | u_max, each [batch][N][nx] / [batch][N-1][nu]; bnd_inst = 1) or the
     // shared bounds (bnd_inst = 0: instance stride 0). The enable flags act as in k_build_tables.
     const double *x_min, *x_max, *u_min, *u_max;
@@ -430,6 +456,8 @@ hipError_t launch_build_operators(const OperatorParams &p, hipStream_t stream);
 hipError_t launch_build_tables(const TableParams &p, hipStream_t stream);
 hipError_t launch_store_inst_refs(const InstRefStoreParams &p, hipStream_t stream);
 hipError_t launch_build_inst_tables(const InstTableParams &p, hipStream_t stream);
+hipError_t launch_fill_inst_models(const InstModelFillParams &p, hipStream_t stream);
+hipError_t launch_store_inst_diag(const InstDiagParams &p, hipStream_t stream);
 // Layout A: one wavefront per workgroup, all ADMM state in LDS (lowest latency, 2 waves per CU). One kernel body, three
 // variants: the box path (k_admm_solve), plus the cone / linear slack families (k_admm_solve_fam: extra duals and the extra
 // linear-cost term in HBM), plus adaptive rho (k_admm_solve_adapt: per-instance rho, Taylor-updated operators; needs
@@ -437,7 +465,9 @@ hipError_t launch_build_inst_tables(const InstTableParams &p, hipStream_t stream
 // A fourth variant, InstRefs, is the box path with every instance's linref rows and pNref read from SolveParams::iref_lr / iref_pn
 // (k_admm_solve_iref, tinympc_solve.hip). A fifth, InstBounds, reads every instance's clamp rows from SolveParams::ibnd as well
 // (k_admm_solve_ibnd, tinympc_solve.hip).
-enum class SolveExt { Box, Families, Adaptive, InstRefs, InstBounds };
+// A sixth, InstModels, is InstBounds with every instance's own operator block (k_admm_solve_imod, tinympc_imod_a.hip):
+// SolveParams::ops then is [batch][ops_doubles(W, KT)].
+enum class SolveExt { Box, Families, Adaptive, InstRefs, InstBounds, InstModels };
 hipError_t launch_solve_a(const SolveParams &p, SolveExt ext, int W, int KT, size_t lds_bytes, hipStream_t stream);
 // Layout B: four wavefronts per workgroup sharing the tables in LDS, G and D in LDS, V as an
 // L2-resident ping-pong pair in HBM (4 waves per CU). Only W = 16, N >= 8.

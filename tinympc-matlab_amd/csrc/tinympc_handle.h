@@ -68,6 +68,18 @@ struct InstState {
     double *lrg = nullptr, *bndg = nullptr;  // knot 0's linref [instance][W] and lo | hi rows (layout D's goal form)
     double *bnd = nullptr;                   // layout A's lo | hi rows (inst_bnd_doubles; bounds mode)
     double *stage = nullptr;                 // device staging of one-column host input
+    // Per-instance models (tinympc_set_model_batch): on from its first call until tinympc_clear_model_batch. Every instance's model
+    // (A | B | fdyn | Qd | Rd, the diagonals + rho as PrecomputeParams wants them), its LQR cache and its operator block, each array
+    // [batch][block]; filled from the shared model, cache and operators when the mode begins, recomputed for the instances a call names
+    // (batched precompute + operator builder, inside the call). The mode runs on layout A's InstModels variant, always with the
+    // per-instance reference and clamp rows, which are then built from the instance's own Pinf and cost diagonals.
+    bool models = false;
+    double *mA = nullptr, *mB = nullptr, *mf = nullptr, *mQd = nullptr, *mRd = nullptr;
+    double *cK = nullptr, *cP = nullptr, *cQuu = nullptr, *cAm = nullptr, *cAPf = nullptr, *cBPf = nullptr;
+    int *cinfo = nullptr;                    // [batch][4]: Riccati steps (and the rows kernel's clocks)
+    double *ops = nullptr;                   // [batch][ops_doubles(W, KT)]: SolveParams::ops of the InstModels variant
+    double *mscratch = nullptr;              // working sets of k_precompute's batched form where they do not fit LDS
+    double *mstage = nullptr;                // device staging of the cost diagonals (host input)
     int dirty_lo = 0, dirty_hi = 0;
     bool refs() const { return x || u; }
     const double *lr_rows() const { return lr + (size_t)tinympc::INST_LR_PAD * 64; }  // SolveParams::iref_lr on layout A
@@ -214,7 +226,7 @@ struct tinympc_solver {
     bool fam_dirty = true;
     // Per-instance references and bounds (tinympc_set_x_ref_batch / _u_ref_batch / _bound_constraints_batch; batched handles): InstState.
     InstState inst;
-    bool inst_tables() const { return inst.refs() || inst.bounds; }  // the per-instance table rows are in use
+    bool inst_tables() const { return inst.refs() || inst.bounds || inst.models; }  // the per-instance table rows are in use
     // Goal form (every instance's references AND bounds constant over the horizon): layout D's constant-table kernel carries it, with
     // knot 0's rows per instance; everything else runs on layout A.
     bool iref_goal() const {
@@ -304,7 +316,8 @@ int flush_host_refs(tinympc_solver *s);
 int refresh_derived(tinympc_solver *s);
 FamilyStructure family_structure(const tinympc_solver *s, double *mu = nullptr);
 int refresh_families(tinympc_solver *s);
-int refresh_inst_tables(tinympc_solver *s);  // the per-instance table rows of the instances whose references / bounds changed
+int refresh_inst_tables(tinympc_solver *s);  // the per-instance table rows of the instances whose references / bounds / models changed
+int alloc_inst_rows(tinympc_solver *s, bool bounds);  // the table rows themselves (allocated by the first per-instance verb that needs them)
 void destroy(tinympc_solver *s);
 
 // ---- tinympc_plan.hip: the kernel of a launch, decided in ONE place
@@ -315,6 +328,7 @@ struct LaunchPlan {
     bool families = false, adaptive = false;  // variant bits of the launch
     bool inst_refs = false;                  // ... per-instance references (layout A's InstRefs variant) or bounds (see inst_bounds)
     bool inst_bounds = false;                // ... per-instance bounds (layout A's InstBounds variant)
+    bool inst_models = false;                // ... per-instance models (layout A's InstModels variant; inst_refs and inst_bounds are set with it)
     bool jit = false;                        // a run-time specialisation (tinympc_jit.hip) rather than a compiled-in kernel
     bool host_exchange = false;              // the kernel serves the pinned-host paths (x0 in, solution / completion stamp out)
     int workgroups = 0;

@@ -318,6 +318,26 @@ int refresh_derived(tinympc_solver *s) {
     return TINYMPC_OK;
 }
 
+// The per-instance table rows (SolveParams::iref_lr / iref_pn / ibnd) and, for the bounds and the models, layout A's clamp rows.
+int alloc_inst_rows(tinympc_solver *s, bool bounds) {
+    InstState &in = s->inst;
+    int rc;
+    const size_t lr = inst_lr_doubles(s->groups, s->N), row = (size_t)s->groups * 64, bnd = inst_bnd_doubles(s->groups, s->N);
+    if (!in.lr) {
+        if ((rc = dalloc(s, &in.lr, lr)) || (rc = dalloc(s, &in.pn, row)) || (rc = dalloc(s, &in.lrg, row)) || (rc = dalloc(s, &in.bndg, 2 * row)))
+            return rc;
+        HIP_TRY(hipMemsetAsync(in.lr, 0, sizeof(double) * lr, s->stream));
+        HIP_TRY(hipMemsetAsync(in.pn, 0, sizeof(double) * row, s->stream));
+        HIP_TRY(hipMemsetAsync(in.lrg, 0, sizeof(double) * row, s->stream));
+        HIP_TRY(hipMemsetAsync(in.bndg, 0, sizeof(double) * 2 * row, s->stream));
+    }
+    if (bounds && !in.bnd) {
+        if ((rc = dalloc(s, &in.bnd, bnd))) return rc;
+        HIP_TRY(hipMemsetAsync(in.bnd, 0, sizeof(double) * bnd, s->stream));
+    }
+    return TINYMPC_OK;
+}
+
 int refresh_inst_tables(tinympc_solver *s) {
     InstState &in = s->inst;
     if (!s->inst_tables() || !in.lr || in.dirty_lo >= in.dirty_hi) return TINYMPC_OK;
@@ -327,11 +347,15 @@ int refresh_inst_tables(tinympc_solver *s) {
     p.first = in.dirty_lo; p.count = in.dirty_hi - in.dirty_lo;
     p.Xi = in.x ? in.Xi : nullptr; p.Ui = in.u ? in.Ui : nullptr;
     p.Xref = s->dXref; p.Uref = s->dUref; p.Pinf = s->dPinf; p.ops = s->dops;
+    if (in.models) {  // the rows of instance b from its own cost diagonals and Pinf
+        p.Pinf = in.cP; p.pinf_stride = (size_t)s->nx * s->nx;
+        p.ops = in.ops; p.ops_stride = ops_doubles(s->W, s->KT);
+    }
     p.bnd_inst = in.bounds;
     p.x_min = in.bounds ? in.xmin : s->dxmin; p.x_max = in.bounds ? in.xmax : s->dxmax;
     p.u_min = in.bounds ? in.umin : s->dumin; p.u_max = in.bounds ? in.umax : s->dumax;
     p.lr = const_cast<double *>(in.lr_rows()); p.pn = in.pn; p.lrg = in.lrg; p.bndg = in.bndg;
-    p.bnd = in.bounds ? in.bnd : nullptr;
+    p.bnd = (in.bounds || in.models) ? in.bnd : nullptr;  // (the models' kernel always reads per-instance clamp rows: shared bounds are copied)
     HIP_TRY(launch_build_inst_tables(p, s->stream));
     in.dirty_lo = in.dirty_hi = 0;
     return TINYMPC_OK;

@@ -112,8 +112,18 @@ size_t precompute_scratch_doubles(int nx, int nu) {
 // Follows tiny_api.cpp:124-190 step for step, including its two parity traps: rho is added to the
 // (already augmented) diagonals a second time (:134-135) and the fixed-point iteration is truncated
 // at max|K - Kprev| < 1e-5 keeping THAT iteration's K and P (:157).
-__global__ void __launch_bounds__(PRE_THREADS) k_precompute(const PrecomputeParams p) {
+// BATCH: PrecomputeParams::count systems in one launch, workgroup b on system b's blocks (see k_precompute_rows).
+template <bool BATCH>
+__global__ void __launch_bounds__(PRE_THREADS) k_precompute(const PrecomputeParams p_) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
+    PrecomputeParams p = p_;
+    if constexpr (BATCH) {
+        const size_t b = blockIdx.x, xx = (size_t)p.nx * p.nx, xu = (size_t)p.nx * p.nu, uu = (size_t)p.nu * p.nu;
+        p.A += b * xx; p.B += b * xu; p.fdyn += b * p.nx; p.Qd += b * p.nx; p.Rd += b * p.nu;
+        p.Kinf += b * xu; p.Pinf += b * xx; p.Quu_inv += b * uu; p.AmBKt += b * xx; p.APf += b * p.nx; p.BPf += b * p.nu;
+        p.info += b * 4;
+        p.scratch += b * p.scratch_stride;
+    }
     double *red = lds;  // PRE_THREADS doubles, always in LDS
     double *w = p.use_lds ? (lds + PRE_THREADS) : p.scratch;
     const int nx = p.nx, nu = p.nu, tid = threadIdx.x;
@@ -197,7 +207,11 @@ __global__ void __launch_bounds__(PRE_THREADS) k_precompute(const PrecomputePara
 hipError_t launch_precompute(const PrecomputeParams &p, hipStream_t stream) {
     size_t lds = sizeof(double) * PRE_THREADS;
     if (p.use_lds) lds += sizeof(double) * precompute_scratch_doubles(p.nx, p.nu);
-    hipLaunchKernelGGL(k_precompute, dim3(1), dim3(PRE_THREADS), lds, stream, p);
+    if (p.count > 0) {
+        hipLaunchKernelGGL(k_precompute<true>, dim3(p.count), dim3(PRE_THREADS), lds, stream, p);
+    } else {
+        hipLaunchKernelGGL(k_precompute<false>, dim3(1), dim3(PRE_THREADS), lds, stream, p);
+    }
     return hipGetLastError();
 }
 
@@ -474,7 +488,14 @@ hipError_t launch_finite_diff(const FiniteDiffParams &p, hipStream_t stream) {
 //             [ Quu_inv*B'   Quu_inv  ] [r_i    ] + [Quu_inv * BPf  ]
 // A-B*Kinf is formed from the installed Kinf (not from AmBKt) because the reference's forward pass
 // uses Adyn, Bdyn and Kinf; the backward operator uses the installed AmBKt, as the reference does.
-__global__ void __launch_bounds__(256) k_build_operators(const OperatorParams p) {
+__global__ void __launch_bounds__(256) k_build_operators(const OperatorParams p_) {
+    OperatorParams p = p_;
+    if (p.count > 0) {  // the batched form: system blockIdx.x's blocks
+        const size_t b = blockIdx.x, xx = (size_t)p.nx * p.nx, xu = (size_t)p.nx * p.nu, uu = (size_t)p.nu * p.nu;
+        p.A += b * xx; p.B += b * xu; p.fdyn += b * p.nx; p.Qd += b * p.nx; p.Rd += b * p.nu;
+        p.Kinf += b * xu; p.Quu_inv += b * uu; p.AmBKt += b * xx; p.APf += b * p.nx; p.BPf += b * p.nu;
+        p.ops += b * ops_doubles(p.W, p.KT);
+    }
     const int nx = p.nx, nu = p.nu, W = p.W, KT = p.KT, nxu = nx + nu;
     double *Mf = p.ops, *Mb = p.ops + (size_t)W * KT, *cf = p.ops + (size_t)2 * W * KT, *cb = cf + W, *dg = cb + W;
     for (int idx = threadIdx.x; idx < W * KT; idx += 256) {
@@ -520,7 +541,7 @@ __global__ void __launch_bounds__(256) k_build_operators(const OperatorParams p)
 }
 
 hipError_t launch_build_operators(const OperatorParams &p, hipStream_t stream) {
-    hipLaunchKernelGGL(k_build_operators, dim3(1), dim3(256), 0, stream, p);
+    hipLaunchKernelGGL(k_build_operators, dim3(p.count > 0 ? p.count : 1), dim3(256), 0, stream, p);
     return hipGetLastError();
 }
 
@@ -604,7 +625,7 @@ hipError_t launch_store_inst_refs(const InstRefStoreParams &p, hipStream_t strea
 __global__ void __launch_bounds__(256) k_build_inst_tables(const InstTableParams p) {
     const int nx = p.nx, nu = p.nu, N = p.N, W = p.W, nxu = nx + nu, TR = N + 2;
     const size_t X = (size_t)nx * N, U = (size_t)nu * (N - 1);
-    const double *dg = p.ops + (size_t)2 * W * p.KT + 2 * W;
+    const double *dg0 = p.ops + (size_t)2 * W * p.KT + 2 * W;
     const double inf = __longlong_as_double(0x7FF0000000000000LL);
     const size_t bhi = inst_bnd_hi_offset(p.groups, N);
     const size_t per = (size_t)(TR + 1) * W;  // TR table rows + the pNref row, W lanes each
@@ -616,10 +637,11 @@ __global__ void __launch_bounds__(256) k_build_inst_tables(const InstTableParams
         const int lane = (int)(inst % (64 / W)) * W + r;
         const double *Xr = p.Xi ? p.Xi + inst * X : p.Xref;
         const double *Ur = p.Ui ? p.Ui + inst * U : p.Uref;
+        const double *dg = dg0 + inst * p.ops_stride, *Pinf = p.Pinf + inst * p.pinf_stride;  // (per-instance models: the instance's own)
         if (row == TR) {
             double acc = 0.0;
             if (r < nx) {
-                for (int k = 0; k < nx; ++k) acc += Xr[k + (size_t)(N - 1) * nx] * p.Pinf[k + (size_t)r * nx];
+                for (int k = 0; k < nx; ++k) acc += Xr[k + (size_t)(N - 1) * nx] * Pinf[k + (size_t)r * nx];
                 acc = -acc;  // admm.cpp:81
             }
             p.pn[(size_t)grp * 64 + lane] = acc;
@@ -663,6 +685,38 @@ hipError_t launch_build_inst_tables(const InstTableParams &p, hipStream_t stream
     if (total == 0) return hipSuccess;
     const size_t blocks = (total + 255) / 256;
     hipLaunchKernelGGL(k_build_inst_tables, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, stream, p);
+    return hipGetLastError();
+}
+
+// Per-instance models: every instance <- the shared model, cache and operators (InstModelFillParams).
+__global__ void __launch_bounds__(256) k_fill_inst_models(const InstModelFillParams p) {
+    const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, nth = (size_t)gridDim.x * 256;
+    for (int q = 0; q < p.nseg; ++q) {
+        const size_t n = (size_t)p.seg[q].n, total = n * p.batch;
+        for (size_t i = tid; i < total; i += nth) p.seg[q].dst[i] = p.seg[q].src[i % n];
+    }
+    for (size_t i = tid; i < (size_t)p.batch; i += nth) p.info_dst[4 * i] = p.info_src[0];
+}
+hipError_t launch_fill_inst_models(const InstModelFillParams &p, hipStream_t stream) {
+    size_t most = 1;
+    for (int q = 0; q < p.nseg; ++q) most = (size_t)p.seg[q].n > most ? (size_t)p.seg[q].n : most;
+    const size_t blocks = (most * p.batch + 255) / 256;
+    hipLaunchKernelGGL(k_fill_inst_models, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, stream, p);
+    return hipGetLastError();
+}
+
+__global__ void __launch_bounds__(256) k_store_inst_diag(const InstDiagParams p) {
+    const size_t total = (size_t)p.n * p.count;
+    for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
+        const size_t b = idx / p.n, i = idx % p.n;
+        p.dst[(size_t)(p.first + b) * p.n + i] = p.src[b * p.src_stride + i * p.src_step] + p.add;
+    }
+}
+hipError_t launch_store_inst_diag(const InstDiagParams &p, hipStream_t stream) {
+    const size_t total = (size_t)p.n * p.count;
+    if (total == 0) return hipSuccess;
+    const size_t blocks = (total + 255) / 256;
+    hipLaunchKernelGGL(k_store_inst_diag, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, stream, p);
     return hipGetLastError();
 }
 

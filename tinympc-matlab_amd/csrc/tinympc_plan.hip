@@ -164,6 +164,7 @@ namespace host {
 //   cone / linear families             D (N <= 22)  >  F (small batches)  >  E (batches)  >  C<FAM> (disjoint cones only)  >  k_admm_solve_fam
 //   box path                           E (only where D has no kernel)  >  D  >  F (on request)  >  C (small batches)  >  B  >  A
 //   per-instance references / bounds   D's goal form  >  A (box path only: with the families, adaptive rho or layout M, launch() refuses)
+//   per-instance models                A, whatever the form of references and bounds (the same refusals)
 LaunchPlan current_plan(const tinympc_solver *s) {
     LaunchPlan pl;
     const bool fam = s->families_active(), adaptive = s->st.adaptive_rho != 0, d = s->use_layout_d();
@@ -173,11 +174,12 @@ LaunchPlan current_plan(const tinympc_solver *s) {
         // goals, where the handle runs layout D: its constant-table kernel (compiled in for the 16-lane shapes that are, run-time
         // specialised otherwise -- wide systems included); trajectories, and goals without such a kernel: layout A. "Goal" means that
         // references AND bounds are constant over the horizon, each per instance or shared
-        const bool goal = s->layout_d && s->iref_goal();
+        const bool goal = s->layout_d && s->iref_goal() && !s->inst.models;  // (models: layout A's InstModels variant only)
         pl.kernel = (goal && !s->d_jit && s->W == 16 && solve_d_supported(s->nx, s->nu, s->N, true)) ? KernelId::D_COMPILED
                     : (goal && s->inst.d_goal == 1) ? KernelId::D_JIT : KernelId::A;
         pl.inst_refs = true;
-        pl.inst_bounds = s->inst.bounds;
+        pl.inst_models = s->inst.models;
+        pl.inst_bounds = s->inst.bounds || pl.inst_models;  // (the models' variant always runs on per-instance clamp rows)
     } else if (s->layout_m) pl.kernel = KernelId::M;
     else if (adaptive) pl.kernel = d ? KernelId::D_JIT : KernelId::ADAPT_A;
     else if (fam)
@@ -250,7 +252,7 @@ int resolve_plan(tinympc_solver *s) {
     int rc;
     if (s->inst_tables()) {  // layout A or D's goal form, or a refusal: only the goal form's specialisation to decide
         int &known = s->inst.d_goal;
-        if (known < 0 && s->layout_d && s->iref_goal() && !(s->W == 16 && !s->d_jit && solve_d_supported(s->nx, s->nu, s->N, true)) &&
+        if (known < 0 && s->layout_d && s->iref_goal() && !s->inst.models && !(s->W == 16 && !s->d_jit && solve_d_supported(s->nx, s->nu, s->N, true)) &&
             !s->families_active() && !s->st.adaptive_rho)
             known = solve_jit_supported(s->W, s->nx, s->nu, s->N, true, false, false, true) ? 1 : 0;
         return TINYMPC_OK;
@@ -309,17 +311,24 @@ int launch(tinympc_solver *s, bool timed) {
     if ((rc = resolve_plan(s))) return rc;
     const LaunchPlan pl = current_plan(s);
     const bool fam = pl.families, adaptive = pl.adaptive;
-    if (s->inst_tables() && !pl.inst_refs) {  // never a solve with the shared references / bounds in their place
-        const bool r = s->inst.refs(), b = s->inst.bounds;
-        return fail(TINYMPC_ERR_UNSUPPORTED, "%s%s%s are not supported %s; %s%s%s", r ? "per-instance references (set_x_ref_batch / set_u_ref_batch)" : "",
-                    r && b ? " and " : "", b ? "per-instance bounds (set_bound_constraints_batch)" : "",
-                    s->layout_m ? "for systems with nx+nu > 64" : fam ? "with cone / linear constraint families" : "with adaptive rho",
-                    r ? "tinympc_set_x_ref / tinympc_set_u_ref return to shared references" : "", r && b ? ", " : "",
-                    b ? "tinympc_set_bound_constraints returns to shared bounds" : "");
+    if (s->inst_tables() && !pl.inst_refs) {  // never a solve with the shared references / bounds / model in their place
+        const bool r = s->inst.refs(), b = s->inst.bounds, m = s->inst.models;
+        const char *what[3], *back[3];
+        int n = 0;
+        if (r) { what[n] = "per-instance references (set_x_ref_batch / set_u_ref_batch)"; back[n++] = "tinympc_set_x_ref / tinympc_set_u_ref return to shared references"; }
+        if (b) { what[n] = "per-instance bounds (set_bound_constraints_batch)"; back[n++] = "tinympc_set_bound_constraints returns to shared bounds"; }
+        if (m) { what[n] = "per-instance models (set_model_batch)"; back[n++] = "tinympc_clear_model_batch returns to the shared model"; }
+        std::string subj, way;
+        for (int i = 0; i < n; ++i) {
+            subj += std::string(i == 0 ? "" : i == n - 1 ? " and " : ", ") + what[i];
+            way += std::string(i == 0 ? "" : ", ") + back[i];
+        }
+        return fail(TINYMPC_ERR_UNSUPPORTED, "%s are not supported %s; %s", subj.c_str(),
+                    s->layout_m ? "for systems with nx+nu > 64" : fam ? "with cone / linear constraint families" : "with adaptive rho", way.c_str());
     }
     // k_build_adapt reads the device copy of the references before the solve kernel starts: bring the device copies and the tables up
     // to date the ordinary way (every other kernel of a single-instance handle stages references left in pinned host memory itself)
-    if (s->refs_on_host && adaptive) {
+    if (s->refs_on_host && (adaptive || pl.inst_models)) {  // (... and so are the per-instance rows of the models' variant)
         if ((rc = flush_host_refs(s))) return rc;
     }
     if ((rc = refresh_derived(s))) return rc;
@@ -343,7 +352,8 @@ int launch(tinympc_solver *s, bool timed) {
     p.nx = s->nx; p.nu = s->nu; p.N = s->N; p.batch = s->batch;
     p.max_iter = s->st.max_iter; p.check_termination = s->st.check_termination;
     p.rho = s->rho; p.abs_pri_tol = s->st.abs_pri_tol; p.abs_dua_tol = s->st.abs_dua_tol;
-    p.ops = s->dops; p.tables = s->dtables; p.x0 = s->dx0;
+    p.ops = pl.inst_models ? s->inst.ops : s->dops;  // (per-instance models: every instance's own operator block)
+    p.tables = s->dtables; p.x0 = s->dx0;
     p.groups = s->groups;
     p.G = s->dG; p.V = s->dV; p.V2 = s->dV2; p.D = s->dD; p.sol_x = s->dsolx; p.sol_u = s->dsolu;
     p.istats = s->distats; p.dstats = s->ddstats;
@@ -440,7 +450,7 @@ int launch(tinympc_solver *s, bool timed) {
         case KernelId::FAM_A:  // (the families and adaptive rho share the persistent state -- G, canonical V, D -- with every other kernel)
         case KernelId::ADAPT_A: {
             const SolveExt ext = pl.kernel == KernelId::FAM_A ? SolveExt::Families : pl.kernel == KernelId::ADAPT_A ? SolveExt::Adaptive
-                                 : pl.inst_bounds ? SolveExt::InstBounds : pl.inst_refs ? SolveExt::InstRefs : SolveExt::Box;
+                                 : pl.inst_models ? SolveExt::InstModels : pl.inst_bounds ? SolveExt::InstBounds : pl.inst_refs ? SolveExt::InstRefs : SolveExt::Box;
             HIP_TRY(launch_solve_a(p, ext, s->W, s->KT, s->lds_bytes_a, s->stream));
             break;
         }
@@ -491,7 +501,9 @@ int tinympc_get_jit_info(tinympc_solver *s, char *buf, int len) {
     const bool ct = s->tables_const();
     if (pl.inst_refs) {
         // (per-instance-refs only when references are per instance; per-instance-bounds only when bounds are)
-        const char *words = !pl.inst_bounds ? " per-instance-refs" : s->inst.refs() ? " per-instance-refs per-instance-bounds" : " per-instance-bounds";
+        const std::string w = std::string(s->inst.refs() ? " per-instance-refs" : "") + (s->inst.bounds ? " per-instance-bounds" : "") +
+                              (pl.inst_models ? " per-instance-models" : "");
+        const char *words = w.c_str();
         if (pl.kernel == KernelId::D_JIT) {
             if ((rc = bind_device(s))) return rc;
             solve_jit_describe(s->W, s->nx, s->nu, s->N, true, false, false, buf, (size_t)len, true);

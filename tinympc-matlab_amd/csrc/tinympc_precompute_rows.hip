@@ -202,9 +202,19 @@ __device__ __forceinline__ void rows_inverse(double (&Sinv)[NUP], double (&S)[NU
     for (int j = 0; j < NUP; ++j) Sinv[j] = __shfl(E[j], src, 64);
 }
 
-template <int NXP, int NUP>
-__global__ void __launch_bounds__(64) k_precompute_rows(const PrecomputeParams p) {
+// BATCH: the batched form (PrecomputeParams::count systems, one wavefront each): the parameter block moved to system blockIdx.x's
+// blocks, everything else as it is -- the arithmetic of a system does not know about its neighbours, so system b's cache is
+// bit-identical to the one the single launch computes for it.
+template <int NXP, int NUP, bool BATCH = false>
+__global__ void __launch_bounds__(64) k_precompute_rows(const PrecomputeParams p_) {
     static_assert(NXP + NUP <= 16, "one DPP row");
+    PrecomputeParams p = p_;
+    if constexpr (BATCH) {
+        const size_t b = blockIdx.x, xx = (size_t)p.nx * p.nx, xu = (size_t)p.nx * p.nu, uu = (size_t)p.nu * p.nu;
+        p.A += b * xx; p.B += b * xu; p.fdyn += b * p.nx; p.Qd += b * p.nx; p.Rd += b * p.nu;
+        p.Kinf += b * xu; p.Pinf += b * xx; p.Quu_inv += b * uu; p.AmBKt += b * xx; p.APf += b * p.nx; p.BPf += b * p.nu;
+        p.info += b * 4;
+    }
     const int nx = p.nx, nu = p.nu;
     const int r = (int)threadIdx.x & 15;
     const bool xl = r < nx;                          // x-lane with a real row
@@ -320,7 +330,11 @@ bool precompute_rows_supported(int nx, int nu) { return nx >= 1 && nu >= 1 && nx
 
 // The exact shape where it is instantiated, else the smallest zero-padded class that holds it.
 hipError_t launch_precompute_rows(const PrecomputeParams &p, hipStream_t stream) {
-#define ROWS_LAUNCH(NXP, NUP) hipLaunchKernelGGL((k_precompute_rows<NXP, NUP>), dim3(1), dim3(64), 0, stream, p)
+#define ROWS_LAUNCH(NXP, NUP)                                                                                   \
+    do {                                                                                                        \
+        if (p.count > 0) hipLaunchKernelGGL((k_precompute_rows<NXP, NUP, true>), dim3(p.count), dim3(64), 0, stream, p); \
+        else hipLaunchKernelGGL((k_precompute_rows<NXP, NUP>), dim3(1), dim3(64), 0, stream, p);                \
+    } while (0)
     const int nx = p.nx, nu = p.nu;
     if (nx == 4 && nu == 1) ROWS_LAUNCH(4, 1);
     else if (nx == 6 && nu == 3) ROWS_LAUNCH(6, 3);

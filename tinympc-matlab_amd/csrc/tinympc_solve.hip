@@ -102,6 +102,9 @@ hipError_t launch_solve_a(const SolveParams &p, SolveExt ext, int W, int KT, siz
         case SolveExt::InstBounds:
             if (!p.iref_lr || !p.iref_pn || !p.ibnd) return hipErrorInvalidValue;
             return launch_solve_a_e<SolveExt::InstBounds>(p, W, KT, lds_bytes, stream);
+        case SolveExt::InstModels:
+            if (!p.iref_lr || !p.iref_pn || !p.ibnd) return hipErrorInvalidValue;
+            return launch_solve_a_e<SolveExt::InstModels>(p, W, KT, lds_bytes, stream);
     }
     return hipErrorInvalidValue;
 }

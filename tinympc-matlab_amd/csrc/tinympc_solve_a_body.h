@@ -1,5 +1,5 @@
 // tinympc_solve_a_body.h -- the body of layout A's three solve kernels (k_admm_solve, k_admm_solve_fam, k_admm_solve_adapt;
-// tinympc_solve_a.h; and k_admm_solve_iref, k_admm_solve_ibnd). Included INSIDE each kernel, with the kernel's template parameters W, KT,
+// tinympc_solve_a.h; and k_admm_solve_iref, k_admm_solve_ibnd, k_admm_solve_imod). Included INSIDE each kernel, with the kernel's template parameters W, KT,
 // TLDS, GMEM, its parameter p and the variant E (SolveExt) in scope; the families', adaptive rho's and per-instance references' and
 // bounds' additions are compiled only into their variant.
 // No include guard: it is meant to be included once per kernel.
@@ -7,7 +7,10 @@
     // per-instance references: this instance's linref rows and pNref from p.iref_lr / iref_pn (HBM / L2, the lane's own 512-byte line
     // per knot) instead of the shared tables; everything else as on the box path
     // per-instance bounds (with the per-instance references' rows): this instance's clamp rows from p.ibnd, streamed like the linref rows
-    constexpr bool IBND = E == SolveExt::InstBounds;
+    // per-instance models (with the per-instance rows of both kinds): this lane's operator rows and constants from its INSTANCE's block
+    // of p.ops, [batch][ops_doubles(W, KT)] -- loads at the start of the solve only; the sweeps are InstBounds' sweeps
+    constexpr bool IMOD = E == SolveExt::InstModels;
+    constexpr bool IBND = E == SolveExt::InstBounds || IMOD;
     constexpr bool IREF = E == SolveExt::InstRefs || IBND;
     extern __shared__ __attribute__((aligned(16))) double smem[];
     refresh_reference_tables(p, W, KT);  // references handed over in pinned host memory (single-instance handles; adaptive rho: never)
@@ -73,7 +76,9 @@
     double mf[KT], mb_store[RELOAD ? 1 : KT], mt[KT], cn[RED ? 1 : KT], ct[RED ? 1 : KT], ty[RED ? 1 : KT];
     double (&mb)[KT] = *reinterpret_cast<double (*)[KT]>(RELOAD ? &mf[0] : &mb_store[0]);  // (RELOAD: the one array, Mb during the backward sweep)
     const size_t M = (size_t)W * KT;
-    const double *Mf0 = p.ops + (size_t)r * KT, *Mb0 = p.ops + M + (size_t)r * KT;
+    const double *ops = p.ops;
+    if constexpr (IMOD) ops += (size_t)(inst_ok ? inst : 0) * ops_doubles(W, KT);  // (lanes beyond the batch: instance 0's block)
+    const double *Mf0 = ops + (size_t)r * KT, *Mb0 = ops + M + (size_t)r * KT;
     if constexpr (!ADAPT) {
         const double *Cn = p.fam + 4 * W + (size_t)r * KT, *Ct = Cn + M, *Ty = Ct + M;
 #pragma unroll
@@ -144,11 +149,11 @@
     // wave-uniform switches: is either family in use at all?
     const bool any_cone = FAM && __ballot(famc) != 0ull, any_lin = FAM && __ballot(faml) != 0ull;
 
-    const double cf = p.ops[(size_t)2 * W * KT + r];
-    const double cb = p.ops[(size_t)2 * W * KT + W + r];
+    const double cf = ops[(size_t)2 * W * KT + r];
+    const double cb = ops[(size_t)2 * W * KT + W + r];
     double pnref = IREF ? p.iref_pn[(size_t)grp * 64 + lane] : p.tables[(size_t)3 * TOFF + r];
     double rho = p.rho;
-    const double rho0 = p.rho, dgr = ADAPT ? p.ops[2 * M + 2 * W + r] : 0.0;  // Q + rho0 / R + rho0 diagonal of this row (tiny_api.cpp:90-91)
+    const double rho0 = p.rho, dgr = ADAPT ? ops[2 * M + 2 * W + r] : 0.0;  // Q + rho0 / R + rho0 diagonal of this row (tiny_api.cpp:90-91)
     const double pnref0 = pnref, dpnref = ADAPT ? p.adapt[5 * M + r] : 0.0;
     if constexpr (ADAPT) {
         rho = inst_ok ? p.rho_inst[inst] : rho0;  // persists across solves like cache->rho

@@ -339,6 +339,64 @@ class TinyMPC:
         self.settings["en_state_bound"] = True
         self.settings["en_input_bound"] = True
 
+    def set_model_batch(self, A, B, Q, R, fdyn=None, first: int = 0):
+        """Per-instance models for instances first, first+1, ...: numpy arrays of shape (nx, nx, count), (nx, nu, count), (nx, nx, count),
+        (nu, nu, count) and, optionally, fdyn (nx, count) -- or contiguous float64 CUDA tensors with the same memory layout, (count, nx, nx)
+        holding A_b', (count, nu, nx) holding B_b', (count, nx, nx), (count, nu, nu), (count, nx). Of Q and R only the diagonals are used;
+        rho, N and the settings stay the handle's. Instance b then solves what a single-instance solver set up with its model would
+        solve. clear_model_batch() returns every instance to the shared model; get_cache_batch() reads the per-instance caches."""
+        self._check_setup()
+        nx, nu = self.nx, self.nu
+        arrays = [A, B, Q, R] + ([fdyn] if fdyn is not None else [])
+        shapes = [(nx, nx), (nx, nu), (nx, nx), (nu, nu)] + ([(nx,)] if fdyn is not None else [])
+        on_device = [hasattr(a, "data_ptr") and getattr(a, "is_cuda", False) for a in arrays]
+        if any(on_device):
+            import torch
+            if not all(on_device):
+                raise TinyMPCError(_lib.ERR_INVALID_INPUT, "models: all must be CUDA tensors, or none")
+            for a, sh in zip(arrays, shapes):
+                if a.dtype != torch.float64 or not a.is_contiguous() or tuple(a.shape[1:]) != tuple(reversed(sh)):
+                    raise TinyMPCError(_lib.ERR_INVALID_INPUT, "models on the device must be contiguous float64 tensors of shape (count, %s), got %s %s"
+                                       % (", ".join(str(d) for d in reversed(sh)), a.dtype, tuple(a.shape)))
+            counts = {int(a.shape[0]) for a in arrays}
+            ptrs = [C.c_void_p(a.data_ptr()) for a in arrays] + ([None] if fdyn is None else [])
+            f = self._L.tinympc_set_model_batch_device
+        else:
+            arrays = [np.asarray(a, dtype=np.float64) for a in arrays]
+            for a, sh in zip(arrays, shapes):
+                if a.ndim != len(sh) + 1 or tuple(a.shape[:-1]) != sh:
+                    raise TinyMPCError(_lib.ERR_INVALID_INPUT, "models must be %s x count, got %s" % (" x ".join(str(d) for d in sh), a.shape))
+            counts = {int(a.shape[-1]) for a in arrays}
+            arrays = [_f(a) for a in arrays]
+            ptrs = [_p(a) for a in arrays] + ([None] if fdyn is None else [])
+            f = self._L.tinympc_set_model_batch
+        if len(counts) != 1:
+            raise TinyMPCError(_lib.ERR_INVALID_INPUT, "models: all must have the same count")
+        (count,) = counts
+        if on_device[0]:
+            torch.cuda.current_stream(arrays[0].device).synchronize()  # (the set_x0_batch contract)
+        pA, pB, pQ, pR, pf = ptrs
+        _lib.check(f(self._h, pA, pB, pf, pQ, pR, int(first), count))
+
+    def clear_model_batch(self):
+        """Every instance back on the shared model of setup()."""
+        self._check_setup()
+        _lib.check(self._L.tinympc_clear_model_batch(self._h))
+
+    def get_cache_batch(self, first: int = 0, count: int | None = None) -> dict:
+        """The LQR cache of instances first .. first+count-1: Kinf (nu, nx, count), Pinf (nx, nx, count), Quu_inv (nu, nu, count),
+        AmBKt (nx, nx, count), riccati_iters (count,). Without per-instance models: the shared cache, repeated."""
+        self._check_setup()
+        count = self.batch - first if count is None else count
+        n = max(count, 0)
+        K = np.zeros((self.nu, self.nx, n), order="F")
+        P = np.zeros((self.nx, self.nx, n), order="F")
+        Qi = np.zeros((self.nu, self.nu, n), order="F")
+        Am = np.zeros((self.nx, self.nx, n), order="F")
+        it = np.zeros(n, dtype=np.int32)
+        _lib.check(self._L.tinympc_get_cache_batch(self._h, _p(K), _p(P), _p(Qi), _p(Am), it.ctypes.data_as(_lib.c_int_p), int(first), int(count)))
+        return dict(Kinf=K, Pinf=P, Quu_inv=Qi, AmBKt=Am, riccati_iters=it)
+
     def _set_batch(self, what, arrays, rows, full, f_host, f_device, first, *extra):
         """The per-instance verbs: numpy arrays of shape (rows, count) / (rows, cols, count), or contiguous float64 CUDA tensors with the
         same memory layout, (count, rows) / (count, cols, rows) -- one column held over the horizon, or cols = full. All arrays in the
