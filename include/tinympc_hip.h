@@ -262,8 +262,11 @@ int tinympc_set_bound_constraints_batch_device(tinympc_solver *s, const double *
  * update_settings, the reference and bound verbs (shared and per-instance), the solve verbs and mpc_step_batch keep the mode. The
  * single-model verbs (get_cache, set_cache_terms, set_sensitivity_matrices, codegen*, compute_cache_terms, solve_lqr,
  * compute_sensitivity, print_problem_data) keep addressing the SHARED model and cache; tinympc_get_cache_batch reads per instance.
- * The mode runs on layout A, whatever the form of references and bounds. With the cone / linear families, adaptive rho or
- * nx+nu > 64 a solve returns TINYMPC_ERR_UNSUPPORTED (never a solve with the shared model), and so does tinympc_session_begin.
+ * The mode runs on layout A unless tinympc_prepare was called on the handle (before or after this verb): then batches that run the
+ * register-resident throughput kernel (layout D) keep it -- every wavefront holds its four instances' operators -- where nx+nu <= 16,
+ * references and bounds are constant over the horizon (shared or per instance) and the horizon fits that kernel's plan; trajectories,
+ * per-knot bounds, wider systems, longer horizons and a refused specialisation (tinympc_get_jit_info says why) stay on layout A. With
+ * the cone / linear families, adaptive rho or nx+nu > 64 a solve returns TINYMPC_ERR_UNSUPPORTED (never a solve with the shared model), and so does tinympc_session_begin.
  * Invalid arguments (a NULL A, B, Q or R, a range beyond the batch, count < 1, host memory handed to the _device form) return
  * TINYMPC_ERR_INVALID_INPUT and leave the mode as it was. Single-instance handles: the same, on instance 0. The input has been copied
  * when the call returns. */
@@ -403,7 +406,8 @@ int tinympc_get_jit_info(tinympc_solver *s, char *buf, int len);
  * one-off cost out of the first real-time tick. It also tells the library that run-time specialisation is welcome on this handle:
  * a single instance / small batch of a shape that is not compiled in then runs on the structure-specialised latency kernel (layout
  * F: 5-25 % fewer microseconds per iteration than the generic latency kernel, resident session included) instead of staying on the
- * generic one, which needs no compiler. No reference counterpart (the reference has one code path). */
+ * generic one, which needs no compiler; and a batch with per-instance models (tinympc_set_model_batch, in either order) runs on layout
+ * D's per-instance model form where one exists instead of layout A. No reference counterpart (the reference has one code path). */
 int tinympc_prepare(tinympc_solver *s);
 
 /* The HIP stream of the handle as an opaque pointer (hipStream_t). */

@@ -72,8 +72,10 @@ struct InstState {
     // (A | B | fdyn | Qd | Rd, the diagonals + rho as PrecomputeParams wants them), its LQR cache and its operator block, each array
     // [batch][block]; filled from the shared model, cache and operators when the mode begins, recomputed for the instances a call names
     // (batched precompute + operator builder, inside the call). The mode runs on layout A's InstModels variant, always with the
-    // per-instance reference and clamp rows, which are then built from the instance's own Pinf and cost diagonals.
+    // per-instance reference and clamp rows, which are then built from the instance's own Pinf and cost diagonals -- or, once the caller
+    // has asked for specialised kernels (tinympc_prepare) and references and bounds are constant over the horizon, on layout D's IMOD form.
     bool models = false;
+    int d_models = -1;  // layout D's per-instance model form (16 lanes; compiled in or run-time specialised): -1 not asked yet, 0 no, 1 yes
     double *mA = nullptr, *mB = nullptr, *mf = nullptr, *mQd = nullptr, *mRd = nullptr;
     double *cK = nullptr, *cP = nullptr, *cQuu = nullptr, *cAm = nullptr, *cAPf = nullptr, *cBPf = nullptr;
     int *cinfo = nullptr;                    // [batch][4]: Riccati steps (and the rows kernel's clocks)

@@ -153,6 +153,14 @@ bool d_is_jit(const tinympc_solver *s, bool fam, bool adaptive) {
     return s->d_jit || fam || adaptive || (!s->tables_const() && s->d_varying_jit);
 }
 
+// Per-instance models on layout D: opt-in (tinympc_prepare -- without it the mode stays on layout A, which needs no specialisation),
+// where the handle runs layout D, 16 lanes per instance (wider operators do not fit a wavefront's LDS share), references and bounds
+// constant over the horizon, box path. Whether the kernel exists is inst.d_models (resolve_plan).
+bool models_want_d(const tinympc_solver *s) {
+    return s->inst.models && s->specialise_asked && s->layout_d && !s->layout_m && s->W == 16 && s->iref_goal() && !s->families_active() &&
+           !s->st.adaptive_rho;
+}
+
 }  // namespace
 
 namespace tinympc {
@@ -164,7 +172,8 @@ namespace host {
 //   cone / linear families             D (N <= 22)  >  F (small batches)  >  E (batches)  >  C<FAM> (disjoint cones only)  >  k_admm_solve_fam
 //   box path                           E (only where D has no kernel)  >  D  >  F (on request)  >  C (small batches)  >  B  >  A
 //   per-instance references / bounds   D's goal form  >  A (box path only: with the families, adaptive rho or layout M, launch() refuses)
-//   per-instance models                A, whatever the form of references and bounds (the same refusals)
+//   per-instance models                D's model form (only after tinympc_prepare: 16 lanes, references and bounds constant over the horizon,
+//                                      a horizon its per-wavefront operator plan holds)  >  A (the same refusals)
 LaunchPlan current_plan(const tinympc_solver *s) {
     LaunchPlan pl;
     const bool fam = s->families_active(), adaptive = s->st.adaptive_rho != 0, d = s->use_layout_d();
@@ -174,9 +183,12 @@ LaunchPlan current_plan(const tinympc_solver *s) {
         // goals, where the handle runs layout D: its constant-table kernel (compiled in for the 16-lane shapes that are, run-time
         // specialised otherwise -- wide systems included); trajectories, and goals without such a kernel: layout A. "Goal" means that
         // references AND bounds are constant over the horizon, each per instance or shared
-        const bool goal = s->layout_d && s->iref_goal() && !s->inst.models;  // (models: layout A's InstModels variant only)
+        // models: layout A's InstModels variant, or -- where the caller asked for specialised kernels -- layout D's model form (the goal
+        // form with every wavefront's four operator blocks in its own LDS region; compiled in or run-time specialised: KernelId::D_JIT)
+        const bool goal = s->layout_d && s->iref_goal() && !s->inst.models;
+        const bool d_models = models_want_d(s) && s->inst.d_models == 1;
         pl.kernel = (goal && !s->d_jit && s->W == 16 && solve_d_supported(s->nx, s->nu, s->N, true)) ? KernelId::D_COMPILED
-                    : (goal && s->inst.d_goal == 1) ? KernelId::D_JIT : KernelId::A;
+                    : ((goal && s->inst.d_goal == 1) || d_models) ? KernelId::D_JIT : KernelId::A;
         pl.inst_refs = true;
         pl.inst_models = s->inst.models;
         pl.inst_bounds = s->inst.bounds || pl.inst_models;  // (the models' variant always runs on per-instance clamp rows)
@@ -199,8 +211,8 @@ LaunchPlan current_plan(const tinympc_solver *s) {
         case KernelId::D_JIT:
             pl.layout = 'D';
             pl.jit = true;
-            pl.workgroups = solve_jit_workgroups(s->W, s->nx, s->nu, s->N, ct, s->groups, fam, adaptive, pl.inst_refs);
-            pl.lds_bytes = solve_jit_lds_bytes(s->W, s->nx, s->nu, s->N, ct, fam, adaptive, pl.inst_refs);
+            pl.workgroups = solve_jit_workgroups(s->W, s->nx, s->nu, s->N, ct, s->groups, fam, adaptive, pl.inst_refs, pl.inst_models);
+            pl.lds_bytes = solve_jit_lds_bytes(s->W, s->nx, s->nu, s->N, ct, fam, adaptive, pl.inst_refs, pl.inst_models);
             break;
         case KernelId::D_COMPILED:
             pl.layout = 'D';
@@ -255,6 +267,9 @@ int resolve_plan(tinympc_solver *s) {
         if (known < 0 && s->layout_d && s->iref_goal() && !s->inst.models && !(s->W == 16 && !s->d_jit && solve_d_supported(s->nx, s->nu, s->N, true)) &&
             !s->families_active() && !s->st.adaptive_rho)
             known = solve_jit_supported(s->W, s->nx, s->nu, s->N, true, false, false, true) ? 1 : 0;
+        // ... and the model form's (compiled in for the quadrotor N=50, specialised now otherwise; a refusal leaves the mode on layout A)
+        if (s->inst.d_models < 0 && models_want_d(s))
+            s->inst.d_models = solve_jit_supported(s->W, s->nx, s->nu, s->N, true, false, false, false, true) ? 1 : 0;
         return TINYMPC_OK;
     }
     decide_layout_d_variants(s);
@@ -270,6 +285,7 @@ static bool refill_applies(const tinympc_solver *s, const LaunchPlan &pl) {
     if ((pl.kernel != KernelId::D_COMPILED && !jit) || s->W != 16 || pl.adaptive || pl.families || pl.inst_refs || s->zero_copy_tick || s->st.max_iter <= 0 ||
         s->st.check_termination <= 0)
         return false;
+    if (pl.inst_models) return false;  // (the model form has no slot-refill variant)
     const char *env = getenv("TINYMPC_REFILL");
     const int mode = env ? atoi(env) : -1;
     if (mode == 0) return false;
@@ -296,6 +312,7 @@ static bool refill_applies(const tinympc_solver *s, const LaunchPlan &pl) {
 static bool lean_applies(const tinympc_solver *s, const LaunchPlan &pl) {
     if (pl.kernel != KernelId::D_COMPILED || s->W != 16 || pl.adaptive || pl.families || s->zero_copy_tick || s->st.max_iter <= 0)
         return false;
+    if (pl.inst_models) return false;  // (the model form has no lean variant: it is a specialisation, never D_COMPILED)
     if (refill_applies(s, pl)) return false;
     const char *env = getenv("TINYMPC_LEAN");
     const int mode = env ? atoi(env) : -1;
@@ -423,7 +440,7 @@ int launch(tinympc_solver *s, bool timed) {
             HIP_TRY(launch_solve_m(p, s->stream));
             break;
         case KernelId::D_JIT:  // (box path, families with everything in registers, or adaptive rho per lane)
-            HIP_TRY(launch_solve_jit(p, s->W, s->stream));
+            HIP_TRY(launch_solve_jit(p, s->W, s->stream, pl.inst_models));
             break;
         case KernelId::D_COMPILED:
             if (lean_applies(s, pl) && !p.x0_mirror && !p.u0_host && !p.refill_next) HIP_TRY(launch_solve_d_lean(p, s->stream));
@@ -506,9 +523,13 @@ int tinympc_get_jit_info(tinympc_solver *s, char *buf, int len) {
         const char *words = w.c_str();
         if (pl.kernel == KernelId::D_JIT) {
             if ((rc = bind_device(s))) return rc;
-            solve_jit_describe(s->W, s->nx, s->nu, s->N, true, false, false, buf, (size_t)len, true);
+            solve_jit_describe(s->W, s->nx, s->nu, s->N, true, false, false, buf, (size_t)len, true, pl.inst_models);
             strncat(buf, words, (size_t)len - strlen(buf) - 1);
             strncat(buf, " goal", (size_t)len - strlen(buf) - 1);
+        } else if (pl.inst_models && models_want_d(s) && s->inst.d_models == 0) {  // asked for and refused: layout A, and why
+            if ((rc = bind_device(s))) return rc;
+            solve_jit_describe(s->W, s->nx, s->nu, s->N, true, false, false, buf, (size_t)len, false, true);
+            strncat(buf, words, (size_t)len - strlen(buf) - 1);
         } else {
             snprintf(buf, (size_t)len, "compiled-in layout=%c%s%s%s", pl.layout, words, pl.kernel == KernelId::D_COMPILED ? " goal" : "",
                      lean_applies(s, pl) ? " lean" : "");

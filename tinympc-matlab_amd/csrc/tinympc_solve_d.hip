@@ -35,6 +35,12 @@
 // the PREVIOUS iterate in v/z (admm.cpp:181-197) -- the stale copy goes to p.V2, written only in sweeps that can
 // still end converged (decided on knot 0, after D_FIRST steps and then every D_GROUP steps; exact because the
 // residual maxima only grow).
+// A compiled-in specialisation (TINY_BUILTIN: __graft_entry__.HIP_BUILTINS_D) is the run-time specialisation's text -- one shape from
+// -D options, one extern "C" entry point, no host side -- compiled by the build under the name TINY_BUILTIN_NAME; the build lints it,
+// so it keeps the bare chain blocks (tinympc_solve_d_chain.h).
+#if defined(TINY_BUILTIN) && !defined(TINY_JIT)
+#define TINY_JIT 1
+#endif
 #ifndef TINY_JIT
 #include <atomic>  // (host side only: the run-time compiler has no use for it)
 #endif
@@ -104,6 +110,7 @@ __device__ __forceinline__ void static_for(F &&f) {
 }
 
 // ---- LDS plan per workgroup, in doubles: operators [2][16 k][16 r] | tables (!CT) | per wave: V[VL][64], D[(N-1)*4*nu]
+// (IMOD: no shared operators; per wave V | D | its four instances' operator blocks)
 constexpr int D_OPS_DOUBLES = 2 * 16 * 16;
 #ifdef TINY_D_GROUP
 constexpr int D_GROUP = TINY_D_GROUP;  // (experiments)
@@ -133,20 +140,25 @@ __host__ __device__ constexpr int d_d_doubles(int nu, int N) { return ((N - 1) *
 __host__ __device__ constexpr int d_tab_doubles(int N) { return 3 * (N + 2) * 16 + 16; }
 constexpr int D_FAM_DOUBLES = 3 * MAX_LIN_ROWS * 16;  // FAM: a_k | b_k | 1/||a_k||^2 of the linear rows, per lane row
 constexpr int D_ADAPT_DOUBLES = 5 * 16 * 16;         // ADAPT: dMf | dMb | [A'; B'] | Pinf | dPinf, transposed like the operators
+// IMOD: the operators are per WAVEFRONT, one [2][16 k][16 r] block for each of its four instances, and no workgroup-shared copy. A row
+// read is a 64-bit read per lane, served in two groups of 32 lanes = two instances, bank = (byte address / 4) mod 64: the two blocks
+// of a group must lie an odd multiple of 32 banks = 16 doubles apart -- 512 + 16.
+constexpr int D_IMOD_STRIDE = D_OPS_DOUBLES + 16;
+constexpr int D_IMOD_WAVE_DOUBLES = 4 * D_IMOD_STRIDE;
 // number of slack slots in LDS; -1 if the shape does not fit the plan (cu_waves wavefronts per CU: 8, or 4 for the
 // long-horizon plan with one wavefront per SIMD and 512 registers)
-__host__ __device__ constexpr int d_vl(int nu, int N, bool ct, int wpg, int cu_waves = 8, bool fam = false, bool adapt = false) {
+__host__ __device__ constexpr int d_vl(int nu, int N, bool ct, int wpg, int cu_waves = 8, bool fam = false, bool adapt = false, bool imod = false) {
     const int ns = N - 1;
-    const int wg_doubles = D_LDS_PER_CU / 8 * wpg / cu_waves - D_OPS_DOUBLES - (ct ? 0 : d_tab_doubles(N)) - (fam ? D_FAM_DOUBLES : 0) - (adapt ? D_ADAPT_DOUBLES : 0);
-    const int wave_doubles = wg_doubles / wpg - d_d_doubles(nu, N);
+    const int wg_doubles = D_LDS_PER_CU / 8 * wpg / cu_waves - (imod ? 0 : D_OPS_DOUBLES) - (ct ? 0 : d_tab_doubles(N)) - (fam ? D_FAM_DOUBLES : 0) - (adapt ? D_ADAPT_DOUBLES : 0);
+    const int wave_doubles = wg_doubles / wpg - d_d_doubles(nu, N) - (imod ? D_IMOD_WAVE_DOUBLES : 0);
     if (wave_doubles < 0) return -1;
     const int vlmax = wave_doubles / 64;
     const int want = ns > D_VREG_MAX ? ns - D_VREG_MAX : 0;
     return want <= vlmax ? want : -1;
 }
-__host__ __device__ constexpr size_t d_lds_bytes(int nu, int N, bool ct, int wpg, int vl, bool fam = false, bool adapt = false) {
-    return sizeof(double) * ((size_t)D_OPS_DOUBLES + (ct ? 0 : d_tab_doubles(N)) + (fam ? D_FAM_DOUBLES : 0) + (adapt ? D_ADAPT_DOUBLES : 0) +
-                             (size_t)wpg * (vl * 64 + d_d_doubles(nu, N)));
+__host__ __device__ constexpr size_t d_lds_bytes(int nu, int N, bool ct, int wpg, int vl, bool fam = false, bool adapt = false, bool imod = false) {
+    return sizeof(double) * ((size_t)(imod ? 0 : D_OPS_DOUBLES) + (ct ? 0 : d_tab_doubles(N)) + (fam ? D_FAM_DOUBLES : 0) + (adapt ? D_ADAPT_DOUBLES : 0) +
+                             (size_t)wpg * (vl * 64 + d_d_doubles(nu, N) + (imod ? D_IMOD_WAVE_DOUBLES : 0)));
 }
 
 // LDS traffic of the sweeps: WHERE a read is issued is this file's decision, not the scheduler's (see tinympc_solve_d_chain.h) -- reads
@@ -235,16 +247,21 @@ __device__ __forceinline__ bool wave_may_converge_d(unsigned long long bad, unsi
 // arithmetic of an instance is that of the plain kernel (bit-identical results: tests/test_hip_parity.py); what changes is that
 // a wavefront's time is the sum of what its rows worked, not four times its slowest instance.
 template <int NX, int NU, int N, bool CT, int WPG, int VL, bool FAM = false, bool ADAPT = false, bool TWO_PER_SIMD = true, bool HOSTX = false,
-          bool REFILL = false, bool IGOAL = false>
+          bool REFILL = false, bool IGOAL = false, bool IMOD = false>
 #else
 // IGOAL: the per-instance goal form (every instance's references and bounds constant over the horizon; k_admm_solve_d_gbnd) -- the
 // four table constants lr_c, pNref, lo_c and hi_c come per lane from SolveParams::iref_lr / iref_pn / ibnd ([instance][16], ibnd's hi
 // at groups*64) instead of the shared table. The same registers, loaded from elsewhere; nothing else changes.
+// IMOD: the per-instance model form (tinympc_set_model_batch; the goal form with SolveParams::ops [batch][ops_doubles(W, KT)]) -- the
+// two sweep operators a lane reads its rows from are its INSTANCE's, staged by its wavefront into the wavefront's own LDS region, and
+// cf, cb, c0 and the folded start value come from the instance's block. The per-lane arithmetic is the goal kernel's.
 template <int NX, int NU, int N, bool CT, int WPG, int VL, bool FAM = false, bool ADAPT = false, bool TWO_PER_SIMD = true, bool HOSTX = false,
-          bool REFILL = false, bool IGOAL = false>
+          bool REFILL = false, bool IGOAL = false, bool IMOD = false>
 #endif
 __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double *smem) {
     static_assert(!(FAM && ADAPT), "adaptive rho and the constraint families exclude each other (as in the C ABI)");
+    static_assert(!IMOD || (IGOAL && CT && !FAM && !ADAPT && !REFILL && !HOSTX && !TINY_LEAN),
+                  "per-instance models: the goal form of the box path (its rows are always built per instance), plain sweeps");
 #if TINY_REFILL
     static_assert(!REFILL || (!FAM && !ADAPT && !HOSTX), "slot refill: box-constrained path only");
 #endif
@@ -278,17 +295,32 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
     const int koff = is_x ? 1 : 0;  // slot s = knot s+1 on state lanes, knot s on input lanes
 
     double *sOps = smem;
-    double *sT = smem + D_OPS_DOUBLES;
+    double *sT = smem + (IMOD ? 0 : D_OPS_DOUBLES);
     double *sLin = sT + (CT ? 0 : d_tab_doubles(N));  // FAM
     double *sAd = sLin + (FAM ? D_FAM_DOUBLES : 0);   // ADAPT: [5][16 k][16 r]
-    double *sV = sAd + (ADAPT ? D_ADAPT_DOUBLES : 0) + (size_t)wv * (VL * 64 + d_d_doubles(NU, N));
+    double *sV = sAd + (ADAPT ? D_ADAPT_DOUBLES : 0) + (size_t)wv * (VL * 64 + d_d_doubles(NU, N) + (IMOD ? D_IMOD_WAVE_DOUBLES : 0));
     double *sD = sV + VL * 64;
+    double *sOpsW = sD + d_d_doubles(NU, N);  // IMOD: [4 instances][D_IMOD_STRIDE]
 
     // ---- workgroup-shared: the two sweep operators, transposed to [k][r] (conflict-free row reads), and the tables
-    for (int i = threadIdx.x; i < D_OPS_DOUBLES; i += 64 * WPG) {
-        const int which = i >> 8, k = (i >> 4) & 15, rr = i & 15;
-        const double v = (k < KT) ? p.ops[(size_t)which * W * KT + (size_t)rr * KT + k] : 0.0;
-        sOps[i] = (FOLD && which == 1 && k >= NX) ? -p.rho * v : v;  // (FOLD: -rho * Mb[:, nx:])
+    if constexpr (IMOD) {
+        // ... per wavefront: the blocks of its four instances, each from the instance's own p.ops block, transposed, padded and scaled
+        // like the shared copy (lanes beyond the batch: instance 0's block, as k_admm_solve_imod does)
+        if (grp_ok) {
+            for (int i = lane; i < IPW * D_OPS_DOUBLES; i += 64) {
+                const int jj = i >> 9, e = i & 511, which = e >> 8, k = (e >> 4) & 15, rr = e & 15;
+                const long ib = grp * IPW + jj;
+                const double *const ops_i = p.ops + (size_t)(ib < p.batch ? ib : 0) * ops_doubles(W, KT);
+                const double v = (k < KT) ? ops_i[(size_t)which * W * KT + (size_t)rr * KT + k] : 0.0;
+                sOpsW[jj * D_IMOD_STRIDE + e] = (FOLD && which == 1 && k >= NX) ? -p.rho * v : v;
+            }
+        }
+    } else {
+        for (int i = threadIdx.x; i < D_OPS_DOUBLES; i += 64 * WPG) {
+            const int which = i >> 8, k = (i >> 4) & 15, rr = i & 15;
+            const double v = (k < KT) ? p.ops[(size_t)which * W * KT + (size_t)rr * KT + k] : 0.0;
+            sOps[i] = (FOLD && which == 1 && k >= NX) ? -p.rho * v : v;  // (FOLD: -rho * Mb[:, nx:])
+        }
     }
     if constexpr (!CT)
         for (int i = threadIdx.x; i < d_tab_doubles(N); i += 64 * WPG) sT[i] = p.tables[i];
@@ -442,8 +474,12 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
     };
     const bool row_ok = r < NXU;
 
-    const double cf = p.ops[(size_t)2 * W * KT + r];
-    const double cb = p.ops[(size_t)2 * W * KT + W + r];
+    // (IMOD: from this lane's instance's block of p.ops, at opsI; otherwise the one shared block, in the expressions it always had -- as one
+    // pointer for both forms the plain kernels kept their instructions but not their order)
+    size_t opsI = 0;  // (doubles)
+    if constexpr (IMOD) opsI = (size_t)(inst_ok ? inst : 0) * ops_doubles(W, KT);
+    const double cf = IMOD ? p.ops[opsI + (size_t)2 * W * KT + r] : p.ops[(size_t)2 * W * KT + r];
+    const double cb = IMOD ? p.ops[opsI + (size_t)2 * W * KT + W + r] : p.ops[(size_t)2 * W * KT + W + r];
     const double pnref0 = IGOAL ? (inst_ok ? p.iref_pn[inst * W + r] : 0.0) : p.tables[(size_t)3 * TOFF + r];
     // (ADAPT: rho, its negative and pNref are lane variables that change every fifth iteration; otherwise they never change and
     // stay in scalar registers)
@@ -473,7 +509,7 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
     const double *const sDr = sD + dIdx;
     double *const sDw = sD + dIdx;
     const double *const sTl = sT + koff * W + r;  // (!CT) row of slot s: sTl[(s + 1) * W]
-    const double *const sMf = sOps + r, *const sMb = sOps + 256 + r;
+    const double *const sMf = (IMOD ? sOpsW + j * D_IMOD_STRIDE : sOps) + r, *const sMb = sMf + 256;
     const unsigned aV = lds_addr(sVl), aD = lds_addr(sDr), aT = lds_addr(sTl);
     const int ct = p.check_termination;
     // K0: c0 = cf + Mf[:, :nx] * x_0 -- the chain's state columns, its FMAs in its order, so forward step 0 (the input columns behind
@@ -489,6 +525,7 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
     if constexpr (FOLD) {
         double mb[16];
         static_for<0, 16>([&](auto K) { mb[K.value] = (K.value >= NX && K.value < NXU) ? p.ops[(size_t)W * KT + (size_t)r * KT + K.value] : 0.0; });
+        if constexpr (IMOD) static_for<NX, NXU>([&](auto K) { mb[K.value] = p.ops[opsI + (size_t)W * KT + (size_t)r * KT + K.value]; });
         lrmc_f = Step::acc_inputs(is_x ? lr_c + cb : cb, lr_c, mb);
     }
 
@@ -1203,8 +1240,21 @@ __global__ void __launch_bounds__(64 * WPG) __attribute__((amdgpu_waves_per_eu(2
 #ifndef TINY_JIT_WPG
 #define TINY_JIT_WPG (4 * TINY_JIT_WPS)
 #endif
+// the entry point: `tinympc_jit_solve` as a run-time specialisation (tinympc_jit.hip looks it up by that name), the name the build
+// gives it as a compiled-in one
+#ifdef TINY_BUILTIN
+#define TINY_KERNEL_NAME TINY_BUILTIN_NAME
+#else
+#define TINY_KERNEL_NAME tinympc_jit_solve
+#endif
+#ifndef TINY_JIT_IMOD
+#define TINY_JIT_IMOD 0
+#endif
+#if TINY_JIT_IMOD && TINY_REFILL
+#error "per-instance models: no slot-refill variant"
+#endif
 extern "C" __global__ void __launch_bounds__(64 * TINY_JIT_WPG) __attribute__((amdgpu_waves_per_eu(TINY_JIT_WPS, TINY_JIT_WPS)))
-tinympc_jit_solve(const tinympc::SolveParams p) {
+TINY_KERNEL_NAME(const tinympc::SolveParams p) {
 #ifndef TINY_JIT_CT
 #define TINY_JIT_CT 1
 #endif
@@ -1218,9 +1268,10 @@ tinympc_jit_solve(const tinympc::SolveParams p) {
 #define TINY_JIT_ADAPT 0
 #endif
     constexpr bool ADJ = TINY_JIT_ADAPT != 0;  // adaptive rho
-    constexpr int VLJ = tinympc::d_vl(TINY_JIT_NU, TINY_JIT_N, CTJ, WPGJ, 4 * TINY_JIT_WPS, FAMJ, ADJ);
+    constexpr bool IMJ = TINY_JIT_IMOD != 0;  // per-instance models (implies the goal form)
+    constexpr int VLJ = tinympc::d_vl(TINY_JIT_NU, TINY_JIT_N, CTJ, WPGJ, 4 * TINY_JIT_WPS, FAMJ, ADJ, IMJ);
     static_assert(VLJ >= 0, "shape does not fit the layout-D plan");
-    __shared__ __attribute__((aligned(16))) double smem_jit[tinympc::d_lds_bytes(TINY_JIT_NU, TINY_JIT_N, CTJ, WPGJ, VLJ, FAMJ, ADJ) / sizeof(double)];
+    __shared__ __attribute__((aligned(16))) double smem_jit[tinympc::d_lds_bytes(TINY_JIT_NU, TINY_JIT_N, CTJ, WPGJ, VLJ, FAMJ, ADJ, IMJ) / sizeof(double)];
 #if TINY_REFILL
 #ifndef TINY_JIT_REFILL
 #define TINY_JIT_REFILL 0
@@ -1230,8 +1281,8 @@ tinympc_jit_solve(const tinympc::SolveParams p) {
 #ifndef TINY_JIT_IGOAL
 #define TINY_JIT_IGOAL 0
 #endif
-    tinympc::k_admm_solve_d_body<TINY_JIT_NX, TINY_JIT_NU, TINY_JIT_N, CTJ, WPGJ, VLJ, FAMJ, ADJ, TINY_JIT_WPS == 2, false, false, TINY_JIT_IGOAL != 0>(
-        p, smem_jit);
+    tinympc::k_admm_solve_d_body<TINY_JIT_NX, TINY_JIT_NU, TINY_JIT_N, CTJ, WPGJ, VLJ, FAMJ, ADJ, TINY_JIT_WPS == 2, false, false,
+                                 TINY_JIT_IGOAL != 0 || IMJ, IMJ>(p, smem_jit);
 #endif
 }
 namespace tinympc {

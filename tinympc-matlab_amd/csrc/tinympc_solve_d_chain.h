@@ -45,7 +45,7 @@
 #define D_MOV64 "v_mov_b64_e64"
 #endif
 #endif
-#if defined(TINY_JIT) || defined(TINY_CHAIN_NOP)
+#if (defined(TINY_JIT) && !defined(TINY_BUILTIN)) || defined(TINY_CHAIN_NOP)  // (TINY_BUILTIN: a specialisation the build compiles and lints)
 #define D_HAZ "s_nop 1\n\t" D_AL
 #else
 #define D_HAZ D_AL

@@ -7,6 +7,13 @@ Solve (default): kernel milliseconds (HIP events, tinympc_solve_timed) of the sa
 The variants run interleaved, `--rounds` times; the median of `--reps` launches per round is reported, one JSON line per variant.
     python tools/instance_models_sweep.py [--batch 8192] [--N 50] [--iters 200] [--rounds 4] [--reps 5] [--only ibnd,models]
 
+Layout D (--d): the same solve with one constant box per instance (what layout D's per-instance forms carry) on
+  models-D   a model per instance after prepare(): layout D's model form (every wavefront's four operator blocks in its LDS region)
+  models-A   the same handle without prepare(): layout A's k_admm_solve_imod, the path the mode takes by default
+  goal-D     the shared model: layout D's goal kernel (k_admm_solve_d_gbnd, two wavefronts per SIMD) -- the floor
+interleaved and reported in the same way.
+    python tools/instance_models_sweep.py --d [--N 50 | --N 20]
+
 Setup (--setup): wall milliseconds of tinympc_set_model_batch for `--batch` quadrotor and cartpole models -- the first call (which
 allocates the per-instance stores and fills them from the shared model), then `--reps` further calls, from host memory and, where
 device memory can be filled, from device memory -- beside the wall time of one single-instance tinympc_setup of the same problem.
@@ -27,6 +34,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 VARIANTS = ["shared-A", "ibnd", "models"]
+D_VARIANTS = ["models-D", "models-A", "goal-D"]
 
 
 def models(prob, batch, seed=0):
@@ -56,21 +64,26 @@ def make(pkg, variant, batch, N, iters):
     wave = 1.0 - 0.3 * np.abs(np.sin(0.3 * np.arange(N)))  # per-knot shrink factor
     if variant == "shared-A":
         s.set_bound_constraints(prob.x_min, prob.x_max, prob.u_min, prob.u_max)
+    elif variant in D_VARIANTS:  # (tools/instance_bounds_sweep.py's `box` variant: one constant box per instance)
+        fx, fu = rng.uniform(0.5, 1.0, (nx, batch)), rng.uniform(0.3, 1.0, (nu, batch))
+        s.set_bound_constraints_batch(prob.x_min[:, None] * fx, prob.x_max[:, None] * fx, prob.u_min[:, None] * fu, prob.u_max[:, None] * fu)
     else:  # (tools/instance_bounds_sweep.py's `knot` variant)
         fx, fu = rng.uniform(0.5, 1.0, (nx, batch)), rng.uniform(0.3, 1.0, (nu, batch))
         xl, xh, ul, uh = prob.x_min[:, None] * fx, prob.x_max[:, None] * fx, prob.u_min[:, None] * fu, prob.u_max[:, None] * fu
         wx, wu = wave[None, :, None], wave[None, :N - 1, None]
         s.set_bound_constraints_batch(xl[:, None, :] * wx, xh[:, None, :] * wx, ul[:, None, :] * wu, uh[:, None, :] * wu)
-    if variant == "models":
+    if variant in ("models", "models-D", "models-A"):
         A, B, Q, R, f = models(prob, batch)
         s.set_model_batch(A, B, Q, R, fdyn=f)
+    if variant == "models-D":
+        s.prepare()
     s.set_x_ref(np.tile(0.3 * rng.standard_normal((nx, 1)), (1, N)))
     s.set_x0_batch(P.quadrotor_batch_x0(batch))
     return s
 
 
 def solve_sweep(pkg, a):
-    names = [v for v in VARIANTS if not a.only or v in a.only.split(",")]
+    names = [v for v in (D_VARIANTS if a.d else VARIANTS) if not a.only or v in a.only.split(",")]
     solvers = {v: make(pkg, v, a.batch, a.N, a.iters) for v in names}
     for s in solvers.values():  # warm-up: first launch, table builds
         s.solve_timed()
@@ -163,6 +176,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=4)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--only", default="")
+    ap.add_argument("--d", action="store_true")
     ap.add_argument("--setup", action="store_true")
     ap.add_argument("--probe", type=int, default=0)
     a = ap.parse_args()
