@@ -321,6 +321,12 @@ static bool lean_applies(const tinympc_solver *s, const LaunchPlan &pl) {
     const bool reachable = s->st.abs_pri_tol > 0.0 && s->st.abs_dua_tol > 0.0;
     return s->st.check_termination != 1 || !reachable;
 }
+// ... and where they apply, the lean kernels are those of tinympc_lstart_d.hip (accumulator starts read from LDS, loop control out of
+// the lean inner loop; bit-identical again). TINYMPC_LEAN_START=0 selects the lean kernels of tinympc_lean_d.hip.
+static bool lean_start_applies() {
+    const char *env = getenv("TINYMPC_LEAN_START");
+    return !env || atoi(env) != 0;
+}
 
 int launch(tinympc_solver *s, bool timed) {
     int rc;
@@ -443,7 +449,8 @@ int launch(tinympc_solver *s, bool timed) {
             HIP_TRY(launch_solve_jit(p, s->W, s->stream, pl.inst_models));
             break;
         case KernelId::D_COMPILED:
-            if (lean_applies(s, pl) && !p.x0_mirror && !p.u0_host && !p.refill_next) HIP_TRY(launch_solve_d_lean(p, s->stream));
+            if (lean_applies(s, pl) && !p.x0_mirror && !p.u0_host && !p.refill_next)
+                HIP_TRY(lean_start_applies() ? launch_solve_d_lean_start(p, s->stream) : launch_solve_d_lean(p, s->stream));
             else HIP_TRY(s->W == 64 ? launch_solve_dx(p, s->stream) : s->W == 32 ? launch_solve_dw(p, s->stream) : launch_solve_d(p, s->stream));
             break;
         case KernelId::E:
@@ -532,7 +539,7 @@ int tinympc_get_jit_info(tinympc_solver *s, char *buf, int len) {
             strncat(buf, words, (size_t)len - strlen(buf) - 1);
         } else {
             snprintf(buf, (size_t)len, "compiled-in layout=%c%s%s%s", pl.layout, words, pl.kernel == KernelId::D_COMPILED ? " goal" : "",
-                     lean_applies(s, pl) ? " lean" : "");
+                     !lean_applies(s, pl) ? "" : lean_start_applies() ? " lean lds-start" : " lean");
         }
         return TINYMPC_OK;
     }
@@ -547,7 +554,8 @@ int tinympc_get_jit_info(tinympc_solver *s, char *buf, int len) {
         if ((rc = bind_device(s))) return rc;
         solve_jit_describe(s->W, s->nx, s->nu, s->N, ct, pl.families && !pl.adaptive, pl.adaptive && !pl.families, buf, (size_t)len);
         if (pl.kernel == KernelId::D_JIT && refill_applies(s, pl)) strncat(buf, " slot-refill", (size_t)len - strlen(buf) - 1);
-    } else snprintf(buf, (size_t)len, "compiled-in layout=%c%s%s", pl.layout, refill_applies(s, pl) ? " slot-refill" : "", lean_applies(s, pl) ? " lean" : "");
+    } else snprintf(buf, (size_t)len, "compiled-in layout=%c%s%s", pl.layout, refill_applies(s, pl) ? " slot-refill" : "",
+                  !lean_applies(s, pl) ? "" : lean_start_applies() ? " lean lds-start" : " lean");
     return TINYMPC_OK;
 }
 

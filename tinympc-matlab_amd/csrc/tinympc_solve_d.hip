@@ -77,6 +77,32 @@
 #if TINY_LEAN && (TINY_REFILL || defined(TINY_JIT))
 #error "TINY_LEAN: compiled-in plain kernels only"
 #endif
+// ... and the lean kernels have a textual variant of their own (TINY_LEAN_START: tinympc_lstart_d.hip sets it with TINY_LEAN; new
+// symbols k_admm_solve_d_lean_start, k_admm_solve_d_gbnd_lean_start, launch_solve_d_lean_start), two changes to the lean inner loop that
+// keep every instruction of its arithmetic, its order and its operands:
+//   LDS start  a forward step's accumulator does not start as a VALU copy of cf: cf sits in a 16-double table behind the shared
+//              operators and a ds_read issued one block ahead, beside the read of d, fills the accumulator (Step::fwd_*_start). Step 0
+//              keeps its copy of c0, which is per instance. (-DTINY_LEAN_NO_LDS_START: without it, for the A/B)
+//   hoist      nothing inside the lean inner loop can change pending, active or final_round -- only an iteration with residuals sets
+//              them --, so the write-back test and the "all instances done" exit are evaluated once in front of the inner loop, and
+//              it_done is set once behind it: a lean round is fair_share_priority, forward sweep, backward sweep, back edge.
+//              (-DTINY_LEAN_NO_HOIST: without it)
+#ifndef TINY_LEAN_START
+#define TINY_LEAN_START 0
+#endif
+#if TINY_LEAN_START && !TINY_LEAN
+#error "TINY_LEAN_START: a variant of the lean kernels"
+#endif
+#if TINY_LEAN_START && !defined(TINY_LEAN_NO_LDS_START)
+#define TINY_LDS_START 1
+#else
+#define TINY_LDS_START 0
+#endif
+#if TINY_LEAN_START && !defined(TINY_LEAN_NO_HOIST)
+#define TINY_LEAN_HOIST 1
+#else
+#define TINY_LEAN_HOIST 0
+#endif
 
 #define TINY_STR2(x) #x
 #define TINY_STR(x) TINY_STR2(x)
@@ -112,6 +138,8 @@ __device__ __forceinline__ void static_for(F &&f) {
 // ---- LDS plan per workgroup, in doubles: operators [2][16 k][16 r] | tables (!CT) | per wave: V[VL][64], D[(N-1)*4*nu]
 // (IMOD: no shared operators; per wave V | D | its four instances' operator blocks)
 constexpr int D_OPS_DOUBLES = 2 * 16 * 16;
+// (TINY_LDS_START: cf per lane row, behind the shared operators -- the accumulator starts of the lean forward steps; this variant only)
+constexpr int D_START_DOUBLES = TINY_LDS_START ? 16 : 0;
 #ifdef TINY_D_GROUP
 constexpr int D_GROUP = TINY_D_GROUP;  // (experiments)
 constexpr int D_FIRST = TINY_D_FIRST;
@@ -149,7 +177,7 @@ constexpr int D_IMOD_WAVE_DOUBLES = 4 * D_IMOD_STRIDE;
 // long-horizon plan with one wavefront per SIMD and 512 registers)
 __host__ __device__ constexpr int d_vl(int nu, int N, bool ct, int wpg, int cu_waves = 8, bool fam = false, bool adapt = false, bool imod = false) {
     const int ns = N - 1;
-    const int wg_doubles = D_LDS_PER_CU / 8 * wpg / cu_waves - (imod ? 0 : D_OPS_DOUBLES) - (ct ? 0 : d_tab_doubles(N)) - (fam ? D_FAM_DOUBLES : 0) - (adapt ? D_ADAPT_DOUBLES : 0);
+    const int wg_doubles = D_LDS_PER_CU / 8 * wpg / cu_waves - (imod ? 0 : D_OPS_DOUBLES + D_START_DOUBLES) - (ct ? 0 : d_tab_doubles(N)) - (fam ? D_FAM_DOUBLES : 0) - (adapt ? D_ADAPT_DOUBLES : 0);
     const int wave_doubles = wg_doubles / wpg - d_d_doubles(nu, N) - (imod ? D_IMOD_WAVE_DOUBLES : 0);
     if (wave_doubles < 0) return -1;
     const int vlmax = wave_doubles / 64;
@@ -157,7 +185,7 @@ __host__ __device__ constexpr int d_vl(int nu, int N, bool ct, int wpg, int cu_w
     return want <= vlmax ? want : -1;
 }
 __host__ __device__ constexpr size_t d_lds_bytes(int nu, int N, bool ct, int wpg, int vl, bool fam = false, bool adapt = false, bool imod = false) {
-    return sizeof(double) * ((size_t)(imod ? 0 : D_OPS_DOUBLES) + (ct ? 0 : d_tab_doubles(N)) + (fam ? D_FAM_DOUBLES : 0) + (adapt ? D_ADAPT_DOUBLES : 0) +
+    return sizeof(double) * ((size_t)(imod ? 0 : D_OPS_DOUBLES + D_START_DOUBLES) + (ct ? 0 : d_tab_doubles(N)) + (fam ? D_FAM_DOUBLES : 0) + (adapt ? D_ADAPT_DOUBLES : 0) +
                              (size_t)wpg * (vl * 64 + d_d_doubles(nu, N) + (imod ? D_IMOD_WAVE_DOUBLES : 0)));
 }
 
@@ -295,7 +323,13 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
     const int koff = is_x ? 1 : 0;  // slot s = knot s+1 on state lanes, knot s on input lanes
 
     double *sOps = smem;
+#if TINY_LDS_START
+    static_assert(!IMOD && !FAM && !ADAPT && !REFILL, "the table of accumulator starts: lean kernels only");
+    double *sStart = smem + D_OPS_DOUBLES;  // cf[16 r]
+    double *sT = sStart + D_START_DOUBLES;
+#else
     double *sT = smem + (IMOD ? 0 : D_OPS_DOUBLES);
+#endif
     double *sLin = sT + (CT ? 0 : d_tab_doubles(N));  // FAM
     double *sAd = sLin + (FAM ? D_FAM_DOUBLES : 0);   // ADAPT: [5][16 k][16 r]
     double *sV = sAd + (ADAPT ? D_ADAPT_DOUBLES : 0) + (size_t)wv * (VL * 64 + d_d_doubles(NU, N) + (IMOD ? D_IMOD_WAVE_DOUBLES : 0));
@@ -322,6 +356,9 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
             sOps[i] = (FOLD && which == 1 && k >= NX) ? -p.rho * v : v;  // (FOLD: -rho * Mb[:, nx:])
         }
     }
+#if TINY_LDS_START
+    if (threadIdx.x < D_START_DOUBLES) sStart[threadIdx.x] = p.ops[(size_t)2 * W * KT + threadIdx.x];  // cf, as the lanes load it below
+#endif
     if constexpr (!CT)
         for (int i = threadIdx.x; i < d_tab_doubles(N); i += 64 * WPG) sT[i] = p.tables[i];
     if constexpr (ADAPT) {  // k_build_adapt's tables: mt | pinf | dpinf | dmf | dmb, each [W][KT]; here: dmf | dmb | mt | pinf | dpinf
@@ -511,6 +548,9 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
     const double *const sTl = sT + koff * W + r;  // (!CT) row of slot s: sTl[(s + 1) * W]
     const double *const sMf = (IMOD ? sOpsW + j * D_IMOD_STRIDE : sOps) + r, *const sMb = sMf + 256;
     const unsigned aV = lds_addr(sVl), aD = lds_addr(sDr), aT = lds_addr(sTl);
+#if TINY_LDS_START
+    const unsigned aC = lds_addr(sStart + r);
+#endif
     const int ct = p.check_termination;
     // K0: c0 = cf + Mf[:, :nx] * x_0 -- the chain's state columns, its FMAs in its order, so forward step 0 (the input columns behind
     // c0) is bit-identical to the full chain.
@@ -571,7 +611,13 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
     // One round of the loop below, in two forms: LEAN_ = true without residuals, false the plain kernel's. Returns true when the solve
     // is over. (Each form is called from one place and inlined there.)
     auto iteration = [&](auto LEAN_, const int it) __attribute__((always_inline)) -> bool {
+#if TINY_LEAN_HOIST
+        // (2: the control of a run of lean rounds alone -- write-back of what the last iteration with residuals left pending, then
+        // "is anything still iterating"; the lean rounds proper, 1, have neither)
+        constexpr bool LEANI = decltype(LEAN_)::value != 0, CTL_ONLY = decltype(LEAN_)::value == 2, NO_CTL = LEANI && !CTL_ONLY;
+#else
         constexpr bool LEANI = decltype(LEAN_)::value;
+#endif
 #else
     for (int it = 0; max_iter > 0; ++it) {  // admm.cpp:129
 #endif
@@ -585,12 +631,18 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
 #else
         const bool final_round = it0 >= max_iter;
 #endif
+#if TINY_LEAN_HOIST
+        if constexpr (TWO_PER_SIMD && !CTL_ONLY) fair_share_priority<NS>(it0, simd_slot);
+#else
         if constexpr (TWO_PER_SIMD) fair_share_priority<NS>(it0, simd_slot);  // (tinympc_sweep.h: the two wavefronts of a SIMD finish together)
+#endif
         // ---- write-back: G, D and the canonical v|z (not converged: v = vnew, admm.cpp:196-197; converged: the solve
         // returned before v <- vnew, so the canonical copy is the stale one in V2); solution = vnew / znew (:187-188, 204-205)
 #if TINY_REFILL
         const bool fin = REFILL ? it_done >= max_iter : final_round;
         const bool wb = pending || (fin && active);
+#elif TINY_LEAN_HOIST
+        const bool wb = NO_CTL ? false : pending || (final_round && active);  // (a lean round: the block below folds away)
 #else
         const bool wb = pending || (final_round && active);
 #endif
@@ -727,7 +779,12 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
             }
             pending = false;
         }
-#if TINY_LEAN
+#if TINY_LEAN_HOIST
+        if constexpr (!NO_CTL) {
+            if (final_round || __ballot(active) == 0ull) return true;
+        }
+        if constexpr (CTL_ONLY) return false;
+#elif TINY_LEAN
         if (final_round || __ballot(active) == 0ull) return true;
 #else
         if (final_round || __ballot(active) == 0ull) break;
@@ -767,7 +824,12 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
             const double lo0 = CT ? lo_c : sT[W + r], hi0 = CT ? hi_c : sT[TOFF + W + r];
             const double s = x0v + G0;
             const double snew = fmin(hi0, fmax(lo0, s));
+#if TINY_LEAN_HOIST
+            if constexpr (LEANI) G0 = s;  // (G0 = s - snew follows in front of the backward sweep's first block, see there)
+            else G0 = s - snew;
+#else
             G0 = s - snew;
+#endif
             pri = is_x ? fabs(x0v - snew) : 0.0;
             dua = is_x ? fabs(V0 - snew) : 0.0;
             // First "can this sweep still converge" test, on knot 0's residuals alone (exact like the later ones: the
@@ -813,6 +875,9 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
             hicur = lds_read_async<(TOFF + W) * 8>(aT);
         }
         lds_wait_ops(m);
+#if TINY_LDS_START
+        double acur = 0.0;  // the accumulator of the step at hand, holding its start value (lean sweeps, from step 1 on)
+#endif
         auto fstep = [&](auto S) {
             constexpr int q = decltype(S)::value;
             double dn = 0.0, vn = 0.0, lon = lo_c, hin = hi_c;
@@ -826,18 +891,32 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
                 lon = lds_read_async<(q + 2) * W * 8>(aT);
                 hin = lds_read_async<(TOFF + (q + 2) * W) * 8>(aT);
             }
+#if TINY_LDS_START
+            // (the NEXT step's accumulator start, cf: in flight during this step's block like d_{q+1}; step 0 starts from c0)
+            static_assert(K0, "step 0 starts from c0");
+            double an = 0.0;
+            if constexpr (LEANI && q + 1 < NS) an = lds_read_issued_here<0>(aC);
+#endif
             const double xprev = xcur;
             double snew_q;
 #if TINY_LEAN
             if constexpr (LEANI) {  // S1 + D1 without R1's maxima: the clamp goes straight into the slot
                 if constexpr (q >= VL) {
                     if constexpr (K0 && q == 0) xcur = Step::fwd_reg0_nores(dcur, m, c0, locur, hicur, G[q], Vr[q - VL]);
+#if TINY_LDS_START
+                    else xcur = Step::fwd_reg_start(xcur, dcur, m, acur, locur, hicur, G[q], Vr[q - VL]);
+#else
                     else xcur = Step::fwd_reg_nores(xcur, dcur, m, cf, locur, hicur, G[q], Vr[q - VL]);
+#endif
                     snew_q = Vr[q - VL];
                 } else {
                     double vnew;
                     if constexpr (K0 && q == 0) xcur = Step::fwd_lds0_nores(dcur, m, c0, locur, hicur, G[q], vnew);
+#if TINY_LDS_START
+                    else xcur = Step::fwd_lds_start(xcur, dcur, m, acur, locur, hicur, G[q], vnew);
+#else
                     else xcur = Step::fwd_lds_nores(xcur, dcur, m, cf, locur, hicur, G[q], vnew);
+#endif
                     lds_write_async<q * 512>(aV, vnew);
                     snew_q = vnew;
                 }
@@ -879,6 +958,9 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
             }
             dcur = dn;
             vcur = vn;
+#if TINY_LDS_START
+            acur = an;
+#endif
             if constexpr (!CT) {
                 locur = lon;
                 hicur = hin;
@@ -926,6 +1008,10 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
             if (active) it_done += 1;
         } else {
             if (active) it_done = it1;  // admm.cpp:143
+        }
+#elif TINY_LEAN_HOIST
+        if constexpr (!NO_CTL) {
+            if (active) it_done = it1;  // (lean rounds: once behind their loop)
         }
 #else
         if (active) it_done = it1;  // admm.cpp:143
@@ -1044,6 +1130,17 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
             };
             double v2cur = vreq(std::integral_constant<int, (NS >= 3 ? NS - 3 : 0)>{});
             lds_wait_ops(m);
+#if TINY_LEAN_HOIST
+            // Knot 0's dual update, G0 = s - snew (V0 is snew by now), placed here by hand: the first backward block follows the asm
+            // statement above directly, and between two asm statements with nothing but the wait in between the compiler puts a hazard
+            // s_nop, which this instruction makes unnecessary (in the lean kernels of tinympc_lean_d.hip the scheduler happens to leave
+            // it here; with the control hoisted it moved to the loop's end). The same instruction on the same operands.
+            if constexpr (LEANI) {
+                asm volatile("" : "+v"(G0));
+                G0 = G0 - V0;
+                asm volatile("" ::"v"(G0));
+            }
+#endif
             static_for<0, NS - 1>([&](auto I) {
                 constexpr int s = NS - 1 - I.value;           // NS-1 .. 1
                 constexpr int s2 = s >= 2 ? s - 2 : 0;        // slot feeding the tail (s = 1: any finite t will do)
@@ -1083,6 +1180,15 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
         if (ct > 0 && reachable) nres = (it / ct + 1) * ct;
         else if (last_check > it) nres = last_check;
         const int lean_end = __builtin_amdgcn_readfirstlane(nres - 1 < max_iter ? nres - 1 : max_iter);
+#if TINY_LEAN_HOIST
+        if (it < lean_end) {
+            // what can end a run of lean rounds, or ask it for a write-back, is decided before the run starts: once, here
+            if (iteration(std::integral_constant<int, 2>{}, it)) break;
+            for (; it < lean_end; ++it) (void)iteration(std::true_type{}, it);
+            if (active) it_done = __builtin_amdgcn_readfirstlane(it);  // admm.cpp:143, for the whole run
+        }
+        if (iteration(std::false_type{}, it)) break;
+#else
         bool over = false;
         for (; it < lean_end; ++it) {
             if (iteration(std::true_type{}, it)) {
@@ -1091,6 +1197,7 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
             }
         }
         if (over || iteration(std::false_type{}, it)) break;
+#endif
         ++it;
     }
 #else
@@ -1152,7 +1259,14 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
 
 #if TINY_LEAN
 // (the lean translation unit, tinympc_lean_d.hip: the plain kernel and its per-instance goal form with lean sweeps; tinympc_plan.hip
-// decides when -- lean_applies)
+// decides when -- lean_applies; tinympc_lstart_d.hip: the same under the names of its variant)
+#if TINY_LEAN_START
+#define k_admm_solve_d_lean k_admm_solve_d_lean_start
+#define k_admm_solve_d_gbnd_lean k_admm_solve_d_gbnd_lean_start
+#define launch_solve_d_lean launch_solve_d_lean_start
+// (the quadrotor's plan has 1,644 doubles per wavefront behind d with the 16 of the table taken out: 25 slots of 64 still fit)
+static_assert(d_vl(4, 50, true, 4) == 25, "quadrotor N=50: 25 slack slots in LDS with four wavefronts per workgroup");
+#endif
 template <int NX, int NU, int N, bool CT, int WPG, int VL>
 __global__ void __launch_bounds__(64 * WPG) __attribute__((amdgpu_waves_per_eu(2, 2))) k_admm_solve_d_lean(const SolveParams p) {
     extern __shared__ __attribute__((aligned(16))) double smem[];

@@ -360,6 +360,29 @@ struct DStep<D_NX, D_NU> {
         lds_reads_landed();
         return a;
     }
+    // ... and the two of them with the accumulator start already in `a` (tinympc_lstart_d.hip: cf comes from a 16-double table in LDS,
+    // read one block ahead like d -- a ds_read fills the register pair without the VALU, so the block has no v_mov_b64). The text is
+    // otherwise fwd_*_nores': the same chain, the same four instructions behind it. `a` is early-clobber: it must never share a
+    // register with x or d. With its s_waitcnt and the caller's 8-byte LDS instructions a block is 4 bytes more than a multiple
+    // of 8, as fwd_lds_nores' is: D_AL pads each with one 4-byte s_nop (in the object code; the compiler's assembly shows the directive).
+    static __device__ __forceinline__ double fwd_reg_start(double x, double d, const double (&m)[16], double a, double lo, double hi, double &g,
+                                                           double &v) {
+        double s;
+        asm volatile(D_HAZ D_CHAIN D_PROJECT_NORES
+                     : [a] "+&v"(a), [s] "=&v"(s), [g] "+v"(g), [sn] "+v"(v)
+                     : [x] "v"(x), [d] "v"(d), [lo] "v"(lo), [hi] "v"(hi), D_MOPS);
+        lds_reads_landed();
+        return a;
+    }
+    static __device__ __forceinline__ double fwd_lds_start(double x, double d, const double (&m)[16], double a, double lo, double hi, double &g,
+                                                           double &vnew) {
+        double s;
+        asm volatile(D_HAZ D_CHAIN D_PROJECT_NORES
+                     : [a] "+&v"(a), [s] "=&v"(s), [g] "+v"(g), [sn] "=&v"(vnew)
+                     : [x] "v"(x), [d] "v"(d), [lo] "v"(lo), [hi] "v"(hi), D_MOPS);
+        lds_reads_landed();
+        return a;
+    }
     static __device__ __forceinline__ double fwd_reg0_nores(double d, const double (&m)[16], double c0, double lo, double hi, double &g, double &v) {
         double a, s;
         asm volatile("v_mov_b64 %[a], %[cf]\n\t" D_HAZ D_CHAIN_IN D_PROJECT_NORES

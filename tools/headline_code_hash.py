@@ -9,7 +9,10 @@ The lean form of the same kernel (k_admm_solve_d_lean<12, 4, 50, true, 4, 25>, t
 sweeps dropped the residual maxima nothing reads) has a record of its own, RECORD_LEAN, with the same rules.
     python tools/headline_code_hash.py                 print the hashes of the current build
     python tools/headline_code_hash.py --record        write RECORD (after the A/B)
-    python tools/headline_code_hash.py --record-lean   write RECORD_LEAN (after the A/B)"""
+The lean kernel with its accumulator starts read from LDS and its loop control hoisted (k_admm_solve_d_lean_start<12, 4, 50, true, 4, 25>,
+tinympc_lstart_d.hip: what the headline runs now) has the third, RECORD_LEAN_START.
+    python tools/headline_code_hash.py --record-lean   write RECORD_LEAN (after the A/B)
+    python tools/headline_code_hash.py --record-lean-start   write RECORD_LEAN_START (after the A/B)"""
 import hashlib
 import json
 import os
@@ -30,6 +33,14 @@ LEAN_MEASURED = ("kernel 1.436 ms avg (8,192 x 200 iterations, bench.py on MI355
                  "the parent build's plain kernel (4,249 instructions, headline_kernel_code_d_fold.json): 1.4326 vs 1.6376 ms (-12.5 %), and 1.4310 vs "
                  "1.6334 ms at TINY_D_PAD=1, four interleaved rounds each, ranges disjoint; 786.1 M against 892.8 M VALU instructions per launch; "
                  "profiles/d_lean_headline_ab.txt")
+KERNEL_LEAN_START = "_ZN7tinympc25k_admm_solve_d_lean_startILi12ELi4ELi50ELb1ELi4ELi25EEEvNS_11SolveParamsE"
+SOURCE_LEAN_START = "tinympc_lstart_d.hip"
+RECORD_LEAN_START = os.path.join(ROOT, "tests", "golden", "headline_kernel_code_d_lean_start.json")
+# what was measured for its recorded code (profiles/d_lean_start_headline_ab.txt)
+LEAN_START_MEASURED = ("kernel 1.409 ms avg (8,192 x 200 iterations, bench.py on MI355X; profiles/d_lean_start_kernel_stats.csv); tools/headline_ab.py, one box, against "
+                       "the parent build's lean kernel (7,091 instructions, headline_kernel_code_d_lean.json) and the hoist-only build: 1.4350 / 1.4222 / 1.3987 ms "
+                       "(-0.9 %, -2.5 %), and 1.4256 / 1.4181 / 1.3942 ms at TINY_D_PAD=1, four interleaved rounds each, ranges disjoint step by step; 764.5 M "
+                       "against 786.1 M VALU instructions per launch; profiles/d_lean_start_headline_ab.txt")
 
 
 def compiler_version() -> str:
@@ -70,6 +81,9 @@ if __name__ == "__main__":
     lean = current_hash(KERNEL_LEAN, SOURCE_LEAN)
     if lean is not None:
         print(json.dumps(lean, indent=1))
+    start = current_hash(KERNEL_LEAN_START, SOURCE_LEAN_START)
+    if start is not None:
+        print(json.dumps(start, indent=1))
     if "--record" in sys.argv:
         h["measured"] = ("kernel 1.647 ms avg (8,192 x 200 iterations, bench.py on MI355X; profiles/d_fold_kernel_stats.csv); tools/headline_ab.py, one box, "
                          "against the build before knot 0 and the backward tail were folded (4,257 instructions): 1.6350 vs 1.6733 ms (-2.3 %), and "
@@ -86,3 +100,11 @@ if __name__ == "__main__":
             json.dump(lean, f, indent=1)
             f.write("\n")
         print("recorded", RECORD_LEAN)
+    if "--record-lean-start" in sys.argv:
+        if start is None:
+            sys.exit("no assembly of the lean kernel with LDS starts: run __graft_entry__.build() first")
+        start["measured"] = LEAN_START_MEASURED
+        with open(RECORD_LEAN_START, "w") as f:
+            json.dump(start, f, indent=1)
+            f.write("\n")
+        print("recorded", RECORD_LEAN_START)
