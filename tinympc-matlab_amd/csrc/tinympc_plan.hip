@@ -327,6 +327,15 @@ static bool lean_start_applies() {
     const char *env = getenv("TINYMPC_LEAN_START");
     return !env || atoi(env) != 0;
 }
+// ... in their trimmed form (tinympc_ltrim_d.hip: the d stores of a lean round go through a per-lane address instead of a narrowed EXEC;
+// bit-identical again). TINYMPC_LEAN_TRIM=0 selects the kernels of tinympc_lstart_d.hip.
+static bool lean_trim_applies() {
+    const char *env = getenv("TINYMPC_LEAN_TRIM");
+    return lean_start_applies() && (!env || atoi(env) != 0);
+}
+static const char *lean_words(const tinympc_solver *s, const LaunchPlan &pl) {
+    return !lean_applies(s, pl) ? "" : lean_trim_applies() ? " lean lds-start trim" : lean_start_applies() ? " lean lds-start" : " lean";
+}
 
 int launch(tinympc_solver *s, bool timed) {
     int rc;
@@ -450,7 +459,9 @@ int launch(tinympc_solver *s, bool timed) {
             break;
         case KernelId::D_COMPILED:
             if (lean_applies(s, pl) && !p.x0_mirror && !p.u0_host && !p.refill_next)
-                HIP_TRY(lean_start_applies() ? launch_solve_d_lean_start(p, s->stream) : launch_solve_d_lean(p, s->stream));
+                HIP_TRY(lean_trim_applies()    ? launch_solve_d_lean_trim(p, s->stream)
+                        : lean_start_applies() ? launch_solve_d_lean_start(p, s->stream)
+                                               : launch_solve_d_lean(p, s->stream));
             else HIP_TRY(s->W == 64 ? launch_solve_dx(p, s->stream) : s->W == 32 ? launch_solve_dw(p, s->stream) : launch_solve_d(p, s->stream));
             break;
         case KernelId::E:
@@ -539,7 +550,7 @@ int tinympc_get_jit_info(tinympc_solver *s, char *buf, int len) {
             strncat(buf, words, (size_t)len - strlen(buf) - 1);
         } else {
             snprintf(buf, (size_t)len, "compiled-in layout=%c%s%s%s", pl.layout, words, pl.kernel == KernelId::D_COMPILED ? " goal" : "",
-                     !lean_applies(s, pl) ? "" : lean_start_applies() ? " lean lds-start" : " lean");
+                     lean_words(s, pl));
         }
         return TINYMPC_OK;
     }
@@ -555,7 +566,7 @@ int tinympc_get_jit_info(tinympc_solver *s, char *buf, int len) {
         solve_jit_describe(s->W, s->nx, s->nu, s->N, ct, pl.families && !pl.adaptive, pl.adaptive && !pl.families, buf, (size_t)len);
         if (pl.kernel == KernelId::D_JIT && refill_applies(s, pl)) strncat(buf, " slot-refill", (size_t)len - strlen(buf) - 1);
     } else snprintf(buf, (size_t)len, "compiled-in layout=%c%s%s", pl.layout, refill_applies(s, pl) ? " slot-refill" : "",
-                  !lean_applies(s, pl) ? "" : lean_start_applies() ? " lean lds-start" : " lean");
+                  lean_words(s, pl));
     return TINYMPC_OK;
 }
 

@@ -103,6 +103,30 @@
 #else
 #define TINY_LEAN_HOIST 0
 #endif
+// ... and the lean-start kernels have a textual variant in turn (TINY_LEAN_TRIM: tinympc_ltrim_d.hip sets it with the two above; new symbols
+// k_admm_solve_d_lean_trim, k_admm_solve_d_gbnd_lean_trim, launch_solve_d_lean_trim). The lean loop's arithmetic is at its floor; what this
+// variant takes out of a lean round are instructions BESIDE the arithmetic, which the results cannot see (docs/NOTEBOOK.md section 15 has
+// what was tried; one part passed its A/B):
+//   dstore  the backward sweep stored d_s for the input lanes of live instances by narrowing EXEC around each store (two scalar
+//           instructions per step). `active` cannot change inside a run of lean rounds, so the mask is turned into a per-lane ADDRESS in
+//           front of the run: input lanes of live instances keep the address of their d, every other lane gets a dump address, and the
+//           49 stores of a round are plain ds_write_b64. A dump address is a live instance's column of d one or two rows UP: with the
+//           step's immediate offset the lane writes row s-1 or s-2 of that column at step s, and the column's own lane overwrites it at
+//           step s-1 / s-2, which comes later (the sweep runs from the last row down, LDS operations of a wavefront complete in order);
+//           rows -1 and -2 are D_DUMP_DOUBLES spare doubles in front of d. No row of an instance that is not live is ever touched.
+//           (-DTINY_TRIM_NO_DSTORE: without it)
+#ifndef TINY_LEAN_TRIM
+#define TINY_LEAN_TRIM 0
+#endif
+#if TINY_LEAN_TRIM && !(TINY_LEAN_START && TINY_LEAN_HOIST && TINY_LDS_START)
+#error "TINY_LEAN_TRIM: a variant of the lean-start kernels (LDS starts and hoisted control)"
+#endif
+#if TINY_LEAN_TRIM && !defined(TINY_TRIM_NO_DSTORE)
+#define TINY_TRIM_DSTORE 1
+#define D_DUMP_DOUBLES(nu) (2 * 4 * (nu))  // two rows of d (4 instances x nu inputs) in front of a wavefront's d: see `dstore` above
+#else
+#define TINY_TRIM_DSTORE 0
+#endif
 
 #define TINY_STR2(x) #x
 #define TINY_STR(x) TINY_STR2(x)
@@ -178,7 +202,11 @@ constexpr int D_IMOD_WAVE_DOUBLES = 4 * D_IMOD_STRIDE;
 __host__ __device__ constexpr int d_vl(int nu, int N, bool ct, int wpg, int cu_waves = 8, bool fam = false, bool adapt = false, bool imod = false) {
     const int ns = N - 1;
     const int wg_doubles = D_LDS_PER_CU / 8 * wpg / cu_waves - (imod ? 0 : D_OPS_DOUBLES + D_START_DOUBLES) - (ct ? 0 : d_tab_doubles(N)) - (fam ? D_FAM_DOUBLES : 0) - (adapt ? D_ADAPT_DOUBLES : 0);
+#if TINY_TRIM_DSTORE
+    const int wave_doubles = wg_doubles / wpg - d_d_doubles(nu, N) - D_DUMP_DOUBLES(nu) - (imod ? D_IMOD_WAVE_DOUBLES : 0);
+#else
     const int wave_doubles = wg_doubles / wpg - d_d_doubles(nu, N) - (imod ? D_IMOD_WAVE_DOUBLES : 0);
+#endif
     if (wave_doubles < 0) return -1;
     const int vlmax = wave_doubles / 64;
     const int want = ns > D_VREG_MAX ? ns - D_VREG_MAX : 0;
@@ -186,7 +214,11 @@ __host__ __device__ constexpr int d_vl(int nu, int N, bool ct, int wpg, int cu_w
 }
 __host__ __device__ constexpr size_t d_lds_bytes(int nu, int N, bool ct, int wpg, int vl, bool fam = false, bool adapt = false, bool imod = false) {
     return sizeof(double) * ((size_t)(imod ? 0 : D_OPS_DOUBLES + D_START_DOUBLES) + (ct ? 0 : d_tab_doubles(N)) + (fam ? D_FAM_DOUBLES : 0) + (adapt ? D_ADAPT_DOUBLES : 0) +
+#if TINY_TRIM_DSTORE
+                             (size_t)wpg * (vl * 64 + D_DUMP_DOUBLES(nu) + d_d_doubles(nu, N) + (imod ? D_IMOD_WAVE_DOUBLES : 0)));
+#else
                              (size_t)wpg * (vl * 64 + d_d_doubles(nu, N) + (imod ? D_IMOD_WAVE_DOUBLES : 0)));
+#endif
 }
 
 // LDS traffic of the sweeps: WHERE a read is issued is this file's decision, not the scheduler's (see tinympc_solve_d_chain.h) -- reads
@@ -332,8 +364,14 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
 #endif
     double *sLin = sT + (CT ? 0 : d_tab_doubles(N));  // FAM
     double *sAd = sLin + (FAM ? D_FAM_DOUBLES : 0);   // ADAPT: [5][16 k][16 r]
+#if TINY_TRIM_DSTORE
+    static_assert(!IMOD, "the dump rows: lean kernels only");
+    double *sV = sAd + (ADAPT ? D_ADAPT_DOUBLES : 0) + (size_t)wv * (VL * 64 + D_DUMP_DOUBLES(NU) + d_d_doubles(NU, N));
+    double *sD = sV + VL * 64 + D_DUMP_DOUBLES(NU);  // (rows -1 and -2 of d: written by the dump lanes of the lean backward sweeps, never read)
+#else
     double *sV = sAd + (ADAPT ? D_ADAPT_DOUBLES : 0) + (size_t)wv * (VL * 64 + d_d_doubles(NU, N) + (IMOD ? D_IMOD_WAVE_DOUBLES : 0));
     double *sD = sV + VL * 64;
+#endif
     double *sOpsW = sD + d_d_doubles(NU, N);  // IMOD: [4 instances][D_IMOD_STRIDE]
 
     // ---- workgroup-shared: the two sweep operators, transposed to [k][r] (conflict-free row reads), and the tables
@@ -607,6 +645,9 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
     asm volatile(".p2align " TINY_STR(TINY_D_LOOP_ALIGN) ::: "memory");
 #endif
     const int max_iter = p.max_iter;
+#if TINY_TRIM_DSTORE
+    unsigned aDw = aD;  // where this lane's d stores of a lean round go: set in front of every run of lean rounds
+#endif
 #if TINY_LEAN
     // One round of the loop below, in two forms: LEAN_ = true without residuals, false the plain kernel's. Returns true when the solve
     // is over. (Each form is called from one place and inlined there.)
@@ -1155,7 +1196,12 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
                 if constexpr (ADAPT) Step::bwd_v(a, px, rcur, m, v2cur, G[s2], rhom_lin, lrmc2, nrho_lin, lr2, an, rn);
                 else if constexpr (FOLD) Step::bwd_fold(a, px, rcur, m, v2cur, G[s2], rhom, lrmc_f, an, rn);
                 else Step::bwd(a, px, rcur, m, v2cur, G[s2], rhom, lrmc2, nrho, lr2, an, rn);
+#if TINY_TRIM_DSTORE
+                if constexpr (NO_CTL) lds_write_async<s * DS * 8>(aDw, a);  // d_s, or a dump row (see `dstore` at the top of the file)
+                else lds_write_masked<s * DS * 8>(aD, a, wr_d);
+#else
                 lds_write_masked<s * DS * 8>(aD, a, wr_d);  // d_s
+#endif
                 px = a;
                 rcur = rnext;
                 rnext = rn;
@@ -1165,7 +1211,12 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
             {
                 double a = acc;
                 Step::bwd_last(a, px, rcur, m);
+#if TINY_TRIM_DSTORE
+                if constexpr (NO_CTL) lds_write_async<0>(aDw, a);
+                else lds_write_masked<0>(aD, a, wr_d);
+#else
                 lds_write_masked<0>(aD, a, wr_d);  // d_0
+#endif
             }
         }
 #if TINY_LEAN
@@ -1184,6 +1235,21 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
         if (it < lean_end) {
             // what can end a run of lean rounds, or ask it for a write-back, is decided before the run starts: once, here
             if (iteration(std::integral_constant<int, 2>{}, it)) break;
+#if TINY_TRIM_DSTORE
+            {   // `active` is fixed for the run, and some instance of the wavefront is live (the control above would have ended the solve)
+                const unsigned long long live = __ballot(active);
+                const unsigned lm = (unsigned)(live & 1ull) | (unsigned)((live >> 15) & 2ull) | (unsigned)((live >> 30) & 4ull) | (unsigned)((live >> 45) & 8ull);
+                const int first = __builtin_ctz(lm | 16u);
+                // dump lanes: the columns of this lane's own instance (row -1), of the instance two further (row -1) and of that one again
+                // (row -2): with four live instances the 24 dump lanes and the 8 storing lanes of a half-wavefront hit 32 different
+                // addresses in 64 different banks. An instance that is not live is replaced by the first live one.
+                const int cls = (r / NU) % 3;
+                int jt = cls == 0 ? j : (j ^ 2);
+                if (((lm >> jt) & 1u) == 0u) jt = first & 3;
+                const unsigned dump = lds_addr(sD) + (unsigned)((jt * NU + r % NU) * 8) - (unsigned)((cls == 2 ? 2 : 1) * DS * 8);
+                aDw = (is_u && active) ? aD : dump;
+            }
+#endif
             for (; it < lean_end; ++it) (void)iteration(std::true_type{}, it);
             if (active) it_done = __builtin_amdgcn_readfirstlane(it);  // admm.cpp:143, for the whole run
         }
@@ -1260,7 +1326,13 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
 #if TINY_LEAN
 // (the lean translation unit, tinympc_lean_d.hip: the plain kernel and its per-instance goal form with lean sweeps; tinympc_plan.hip
 // decides when -- lean_applies; tinympc_lstart_d.hip: the same under the names of its variant)
-#if TINY_LEAN_START
+#if TINY_LEAN_TRIM
+#define k_admm_solve_d_lean k_admm_solve_d_lean_trim
+#define k_admm_solve_d_gbnd_lean k_admm_solve_d_gbnd_lean_trim
+#define launch_solve_d_lean launch_solve_d_lean_trim
+// (... and the two dump rows in front of d, 32 doubles, come out of the 44 the plan had left)
+static_assert(d_vl(4, 50, true, 4) == 25, "quadrotor N=50: 25 slack slots in LDS with four wavefronts per workgroup");
+#elif TINY_LEAN_START
 #define k_admm_solve_d_lean k_admm_solve_d_lean_start
 #define k_admm_solve_d_gbnd_lean k_admm_solve_d_gbnd_lean_start
 #define launch_solve_d_lean launch_solve_d_lean_start

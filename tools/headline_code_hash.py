@@ -12,7 +12,10 @@ sweeps dropped the residual maxima nothing reads) has a record of its own, RECOR
 The lean kernel with its accumulator starts read from LDS and its loop control hoisted (k_admm_solve_d_lean_start<12, 4, 50, true, 4, 25>,
 tinympc_lstart_d.hip: what the headline runs now) has the third, RECORD_LEAN_START.
     python tools/headline_code_hash.py --record-lean   write RECORD_LEAN (after the A/B)
-    python tools/headline_code_hash.py --record-lean-start   write RECORD_LEAN_START (after the A/B)"""
+    python tools/headline_code_hash.py --record-lean-start   write RECORD_LEAN_START (after the A/B)
+The lean-start kernel with the d stores of its lean rounds going through a per-lane address instead of a narrowed EXEC
+(k_admm_solve_d_lean_trim<12, 4, 50, true, 4, 25>, tinympc_ltrim_d.hip: what the headline runs now) has the fourth, RECORD_LEAN_TRIM.
+    python tools/headline_code_hash.py --record-lean-trim    write RECORD_LEAN_TRIM (after the A/B)"""
 import hashlib
 import json
 import os
@@ -41,6 +44,14 @@ LEAN_START_MEASURED = ("kernel 1.409 ms avg (8,192 x 200 iterations, bench.py on
                        "the parent build's lean kernel (7,091 instructions, headline_kernel_code_d_lean.json) and the hoist-only build: 1.4350 / 1.4222 / 1.3987 ms "
                        "(-0.9 %, -2.5 %), and 1.4256 / 1.4181 / 1.3942 ms at TINY_D_PAD=1, four interleaved rounds each, ranges disjoint step by step; 764.5 M "
                        "against 786.1 M VALU instructions per launch; profiles/d_lean_start_headline_ab.txt")
+KERNEL_LEAN_TRIM = "_ZN7tinympc24k_admm_solve_d_lean_trimILi12ELi4ELi50ELb1ELi4ELi25EEEvNS_11SolveParamsE"
+SOURCE_LEAN_TRIM = "tinympc_ltrim_d.hip"
+RECORD_LEAN_TRIM = os.path.join(ROOT, "tests", "golden", "headline_kernel_code_d_lean_trim.json")
+# what was measured for its recorded code (profiles/d_lean_trim_headline_ab.txt)
+LEAN_TRIM_MEASURED = ("kernel 1.384 ms avg (8,192 x 200 iterations, bench.py on MI355X; profiles/d_lean_trim_kernel_stats.csv); tools/headline_ab.py, one box, against "
+                      "the parent build's lean-start kernel (7,152 instructions, headline_kernel_code_d_lean_start.json): 1.3822 vs 1.3991 ms (-1.2 %), and 1.3791 vs "
+                      "1.3945 ms at TINY_D_PAD=1, four interleaved rounds each, ranges disjoint; 4.0 M against 43.9 M scalar and 763.7 M against 764.5 M VALU "
+                      "instructions per launch; profiles/d_lean_trim_headline_ab.txt")
 
 
 def compiler_version() -> str:
@@ -84,6 +95,9 @@ if __name__ == "__main__":
     start = current_hash(KERNEL_LEAN_START, SOURCE_LEAN_START)
     if start is not None:
         print(json.dumps(start, indent=1))
+    trim = current_hash(KERNEL_LEAN_TRIM, SOURCE_LEAN_TRIM)
+    if trim is not None:
+        print(json.dumps(trim, indent=1))
     if "--record" in sys.argv:
         h["measured"] = ("kernel 1.647 ms avg (8,192 x 200 iterations, bench.py on MI355X; profiles/d_fold_kernel_stats.csv); tools/headline_ab.py, one box, "
                          "against the build before knot 0 and the backward tail were folded (4,257 instructions): 1.6350 vs 1.6733 ms (-2.3 %), and "
@@ -108,3 +122,11 @@ if __name__ == "__main__":
             json.dump(start, f, indent=1)
             f.write("\n")
         print("recorded", RECORD_LEAN_START)
+    if "--record-lean-trim" in sys.argv:
+        if trim is None:
+            sys.exit("no assembly of the trimmed lean kernel: run __graft_entry__.build() first")
+        trim["measured"] = LEAN_TRIM_MEASURED
+        with open(RECORD_LEAN_TRIM, "w") as f:
+            json.dump(trim, f, indent=1)
+            f.write("\n")
+        print("recorded", RECORD_LEAN_TRIM)
