@@ -254,8 +254,9 @@ int tinympc_set_bound_constraints_batch_device(tinympc_solver *s, const double *
 
 /* Per-instance models for instances [first, first+count) of a batched handle.
  * A: nx*nx*count, B: nx*nu*count, fdyn: nx*count (NULL = zeros), Q: nx*nx*count, R: nu*nu*count; column-major, instance b's block
- * at b*(block size); of Q and R only the diagonals are used, as in tinympc_setup. rho, N and the settings stay the handle's.
- * Instance b then solves exactly what a single-instance handle set up with (A_b, B_b, fdyn_b, Q_b, R_b, rho) would solve: its LQR
+ * at b*(block size); of Q and R only the diagonals are used, as in tinympc_setup. N and the settings stay the handle's; rho is the
+ * handle's unless tinympc_set_rho_batch below gave the instance its own.
+ * Instance b then solves exactly what a single-instance handle set up with (A_b, B_b, fdyn_b, Q_b, R_b, rho_b) would solve: its LQR
  * cache is computed on the device by the kernels of tinympc_setup, one wavefront or workgroup per instance in one launch, and is
  * bit-identical to that handle's. The first call turns per-instance mode on; instances outside the range keep the handle's shared
  * model (and cache) of that moment. tinympc_clear_model_batch returns every instance to the shared model. reset_workspace,
@@ -275,7 +276,27 @@ int tinympc_set_model_batch(tinympc_solver *s, const double *A, const double *B,
 /* Same, from device memory on the handle's GPU; same contract as tinympc_set_x0_batch_device. */
 int tinympc_set_model_batch_device(tinympc_solver *s, const double *d_A, const double *d_B, const double *d_fdyn,
                                    const double *d_Q, const double *d_R, int first, int count);
-/* Every instance back on the shared model that setup installed. */
+/* Per-instance ADMM penalty for instances [first, first+count) of a batched handle: rho[count], each a finite number > 0.
+ * Instance first+b then solves exactly what a single-instance handle set up with (its model, rho[b]) would solve: its LQR cache is
+ * computed on the device by the kernels of tinympc_setup and is bit-identical to that handle's (tinympc_get_cache_batch against
+ * tinympc_get_cache, riccati_iters included). This IS the per-instance model mode: the first call enters it exactly as
+ * tinympc_set_model_batch does -- every instance starts from the shared model, cache, operators and rho of that moment, instances outside
+ * the range keep the shared rho -- and everything that mode implies holds (layout A; layout D's model form after tinympc_prepare, in
+ * either order; " per-instance-models" in tinympc_get_jit_info; no slot refill, lean sweeps, session or zero-copy tick).
+ * tinympc_clear_model_batch returns every instance to the shared model AND the shared rho. The two verbs commute: the handle keeps
+ * every instance's raw cost diagonals and forms Q_b + rho_b by one addition, as tinympc_setup does, so rho then model gives the bits of
+ * model then rho and of (model_b, rho_b) from scratch. tinympc_get_rho_batch returns the instance's rho while the mode is on and the
+ * setup value again after tinympc_clear_model_batch; reset_workspace, update_settings, the reference and bound verbs (shared and per
+ * instance), the solve verbs and mpc_step_batch keep the per-instance values. With the cone / linear families, adaptive rho or
+ * nx+nu > 64 a solve returns TINYMPC_ERR_UNSUPPORTED (never a solve with the shared rho), and so does tinympc_session_begin. Invalid
+ * arguments (a NULL pointer, a range that is empty or beyond the batch, a value that is not finite or <= 0, host memory or another
+ * GPU's memory handed to the _device form) return TINYMPC_ERR_INVALID_INPUT and leave the mode, the store and every cache as they were:
+ * everything is validated before anything is written. Single-instance handles: the same, on instance 0. The input has been copied when
+ * the call returns. */
+int tinympc_set_rho_batch(tinympc_solver *s, const double *rho, int first, int count);
+/* Same, from device memory on the handle's GPU (validated there); same contract as tinympc_set_x0_batch_device. */
+int tinympc_set_rho_batch_device(tinympc_solver *s, const double *d_rho, int first, int count);
+/* Every instance back on the shared model and rho that setup installed. */
 int tinympc_clear_model_batch(tinympc_solver *s);
 /* The LQR cache of instances [first, first+count): Kinf nu*nx*count, Pinf nx*nx*count, Quu_inv nu*nu*count, AmBKt nx*nx*count,
  * riccati_iters[count]; any pointer may be NULL. Without per-instance models: the shared cache, repeated. */
@@ -283,12 +304,13 @@ int tinympc_get_cache_batch(tinympc_solver *s, double *Kinf, double *Pinf, doubl
                             int *riccati_iters, int first, int count);
 
 /* Zero the persistent ADMM state (cold start) of every instance and put every instance's rho back to
- * the setup value; x0 is kept. */
+ * the setup value -- with per-instance models on, to the instance's own set value (tinympc_set_rho_batch); x0 is kept. */
 int tinympc_reset_workspace(tinympc_solver *s);
 
 /* Adaptive rho (settings adaptive_rho*, admm.cpp:117-174, rho_benchmark.cpp): every instance carries its own
  * rho, adapted every 5th iteration and kept across solves like the reference's cache->rho. Reads it back for
- * instances [first, first+count). Equals the setup rho while adaptive_rho has never been on. */
+ * instances [first, first+count). Equals the setup rho while adaptive_rho has never been on. While per-instance models are on
+ * (tinympc_set_model_batch / tinympc_set_rho_batch): the instance's own rho. */
 int tinympc_get_rho_batch(tinympc_solver *s, double *rho_out, int first, int count);
 
 /* Solutions of instances [first, first+count): x_out nx*N*count, u_out nu*(N-1)*count. */

@@ -86,6 +86,8 @@ SIGNATURES = {
                                                              C.c_int, C.c_int, C.c_int]),
     "tinympc_set_model_batch": (C.c_int, [Handle, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, C.c_int, C.c_int]),
     "tinympc_set_model_batch_device": (C.c_int, [Handle, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+    "tinympc_set_rho_batch": (C.c_int, [Handle, c_double_p, C.c_int, C.c_int]),
+    "tinympc_set_rho_batch_device": (C.c_int, [Handle, C.c_void_p, C.c_int, C.c_int]),
     "tinympc_clear_model_batch": (C.c_int, [Handle]),
     "tinympc_get_cache_batch": (C.c_int, [Handle, c_double_p, c_double_p, c_double_p, c_double_p, c_int_p, C.c_int, C.c_int]),
     "tinympc_reset_workspace": (C.c_int, [Handle]),

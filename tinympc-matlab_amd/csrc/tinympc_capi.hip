@@ -6,6 +6,7 @@
 
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <cstring>
 #include <limits>
 #include <new>
@@ -1193,7 +1194,7 @@ int precompute_inst_models(tinympc_solver *s, int first, int count) {
     for (int b0 = first; b0 < first + count; b0 += chunk) {
         const int n = first + count - b0 < chunk ? first + count - b0 : chunk;
         PrecomputeParams p{};
-        p.nx = s->nx; p.nu = s->nu; p.rho = s->rho;
+        p.nx = s->nx; p.nu = s->nu; p.rho_sys = in.mrho + b0;  // (indexed by the launch's blockIdx.x: the ABSOLUTE instance b0 + b)
         p.A = in.mA + b0 * nx * nx; p.B = in.mB + b0 * nx * nu; p.fdyn = in.mf + b0 * nx; p.Qd = in.mQd + b0 * nx; p.Rd = in.mRd + b0 * nu;
         p.Kinf = in.cK + b0 * nu * nx; p.Pinf = in.cP + b0 * nx * nx; p.Quu_inv = in.cQuu + b0 * nu * nu; p.AmBKt = in.cAm + b0 * nx * nx;
         p.APf = in.cAPf + b0 * nx; p.BPf = in.cBPf + b0 * nu;
@@ -1214,29 +1215,14 @@ int precompute_inst_models(tinympc_solver *s, int first, int count) {
     return TINYMPC_OK;
 }
 
-// tinympc_set_model_batch (+ _device). The mode enters at the first call: every instance then holds the shared model, cache and
-// operators of that moment; the instances named here get their own (precompute_inst_models), and their table rows are rebuilt at the
-// next launch from their own Pinf and cost diagonals (refresh_inst_tables).
-int set_model_batch(tinympc_solver *s, const double *A, const double *B, const double *fdyn, const double *Q, const double *R, bool on_device,
-                    int first, int count) {
-    const char *verb = on_device ? "set_model_batch_device" : "set_model_batch";
-    int rc = check_handle(s);
-    if (rc) return rc;
-    if (!A || !B || !Q || !R) return fail(TINYMPC_ERR_INVALID_INPUT, "%s requires A, B, Q, R", verb);
-    if (first < 0 || count < 1 || first + count > s->batch)
-        return fail(TINYMPC_ERR_INVALID_INPUT, "%s: instance range [%d, %d) is empty or outside batch of %d", verb, first, first + count, s->batch);
-    const double *src[5] = {A, B, fdyn, Q, R};
-    for (int i = 0; on_device && i < 5; ++i) {  // device memory of the handle's own GPU (a host pointer or another GPU's memory is refused here)
-        if (!src[i]) continue;
-        hipPointerAttribute_t attr{};
-        const hipError_t e = hipPointerGetAttributes(&attr, src[i]);
-        (void)hipGetLastError();
-        if (e != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != s->device)
-            return fail(TINYMPC_ERR_INVALID_INPUT, "%s: the models are not device memory of the handle's GPU %d", verb, s->device);
-    }
-    if ((rc = bind_device(s))) return rc;
+// The per-instance model mode begins (the first tinympc_set_model_batch or tinympc_set_rho_batch): the stores, and every instance <- the
+// shared model, cache, operators and rho of this moment.
+int enter_model_mode(tinympc_solver *s) {
     InstState &in = s->inst;
-    if (s->layout_m) {  // (no kernel carries them: the next launch refuses until tinympc_clear_model_batch)
+    int rc;
+    if (!in.mrho && (rc = dalloc(s, &in.mrho, (size_t)s->batch))) return rc;
+    if (s->layout_m) {  // (no kernel carries the mode: the next launch refuses until tinympc_clear_model_batch)
+        if (!in.models) HIP_TRY(launch_fill(in.mrho, (size_t)s->batch, s->rho, s->stream));
         in.models = true;
         return TINYMPC_OK;
     }
@@ -1246,7 +1232,8 @@ int set_model_batch(tinympc_solver *s, const double *A, const double *B, const d
             (rc = dalloc(s, &in.mQd, nx * batch)) || (rc = dalloc(s, &in.mRd, nu * batch)) || (rc = dalloc(s, &in.cK, nu * nx * batch)) ||
             (rc = dalloc(s, &in.cP, nx * nx * batch)) || (rc = dalloc(s, &in.cQuu, nu * nu * batch)) || (rc = dalloc(s, &in.cAm, nx * nx * batch)) ||
             (rc = dalloc(s, &in.cAPf, nx * batch)) || (rc = dalloc(s, &in.cBPf, nu * batch)) || (rc = dalloc(s, &in.cinfo, 4 * batch)) ||
-            (rc = dalloc(s, &in.mstage, (nx + nu) * batch)) || (rc = dalloc(s, &in.ops, od * batch)))
+            (rc = dalloc(s, &in.mstage, (nx + nu) * batch)) || (rc = dalloc(s, &in.mQ0, nx * batch)) || (rc = dalloc(s, &in.mR0, nu * batch)) ||
+            (rc = dalloc(s, &in.ops, od * batch)))
             return rc;
         HIP_TRY(hipMemsetAsync(in.cinfo, 0, sizeof(int) * 4 * batch, s->stream));
     }
@@ -1265,20 +1252,77 @@ int set_model_batch(tinympc_solver *s, const double *A, const double *B, const d
         for (int i = 0; i < 12; ++i) { f.seg[i].src = seg[i].src; f.seg[i].dst = seg[i].dst; f.seg[i].n = (int)seg[i].n; }
         f.info_src = s->dinfo; f.info_dst = in.cinfo;
         HIP_TRY(launch_fill_inst_models(f, s->stream));
+        // ... the raw diagonals of the shared Q and R (setup's device copies of the full matrices), and the shared rho
+        InstDiagParams q0{}, r0{};
+        q0.src = s->dQfull; q0.src_step = s->nx + 1; q0.n = s->nx; q0.dst = in.mQ0;
+        r0.src = s->dRfull; r0.src_step = s->nu + 1; r0.n = s->nu; r0.dst = in.mR0;
+        q0.count = r0.count = s->batch;  // (src_stride 0: the one shared matrix for every instance)
+        HIP_TRY(launch_store_inst_diag(q0, s->stream));
+        HIP_TRY(launch_store_inst_diag(r0, s->stream));
+        HIP_TRY(launch_fill(in.mrho, batch, s->rho, s->stream));
         in.models = true;
         in.mark(0, s->batch);
     }
+    return TINYMPC_OK;
+}
+
+// Qd_b = Q0_b + rho_b, Rd_b = R0_b + rho_b for instances [first, first+count): ONE addition from the raw diagonals, as tinympc_setup forms
+// them (tiny_api.cpp:90-91), then the instances' caches and operators (precompute_inst_models); their table rows are rebuilt at the next
+// launch (refresh_inst_tables). What both per-instance model verbs end with.
+int rebuild_inst_models(tinympc_solver *s, int first, int count) {
+    InstState &in = s->inst;
+    InstDiagParams dq{}, dr{};
+    dq.n = s->nx; dr.n = s->nu;
+    dq.first = dr.first = first; dq.count = dr.count = count; dq.add_inst = dr.add_inst = in.mrho;
+    dq.src = in.mQ0 + (size_t)first * s->nx; dq.src_stride = s->nx; dq.src_step = 1; dq.dst = in.mQd;
+    dr.src = in.mR0 + (size_t)first * s->nu; dr.src_stride = s->nu; dr.src_step = 1; dr.dst = in.mRd;
+    HIP_TRY(launch_store_inst_diag(dq, s->stream));
+    HIP_TRY(launch_store_inst_diag(dr, s->stream));
+    int rc;
+    if ((rc = precompute_inst_models(s, first, count))) return rc;
+    in.mark(first, first + count);
+    return TINYMPC_OK;
+}
+
+// `p` is device memory of the handle's own GPU (a host pointer or another GPU's memory is not)
+bool on_handles_device(const tinympc_solver *s, const void *p) {
+    hipPointerAttribute_t attr{};
+    const hipError_t e = hipPointerGetAttributes(&attr, p);
+    (void)hipGetLastError();
+    return e == hipSuccess && attr.type == hipMemoryTypeDevice && attr.device == s->device;
+}
+
+// tinympc_set_model_batch (+ _device). The mode enters at the first call: every instance then holds the shared model, cache and
+// operators of that moment; the instances named here get their own (precompute_inst_models), and their table rows are rebuilt at the
+// next launch from their own Pinf and cost diagonals (refresh_inst_tables).
+int set_model_batch(tinympc_solver *s, const double *A, const double *B, const double *fdyn, const double *Q, const double *R, bool on_device,
+                    int first, int count) {
+    const char *verb = on_device ? "set_model_batch_device" : "set_model_batch";
+    int rc = check_handle(s);
+    if (rc) return rc;
+    if (!A || !B || !Q || !R) return fail(TINYMPC_ERR_INVALID_INPUT, "%s requires A, B, Q, R", verb);
+    if (first < 0 || count < 1 || first + count > s->batch)
+        return fail(TINYMPC_ERR_INVALID_INPUT, "%s: instance range [%d, %d) is empty or outside batch of %d", verb, first, first + count, s->batch);
+    const double *src[5] = {A, B, fdyn, Q, R};
+    for (int i = 0; on_device && i < 5; ++i)  // device memory of the handle's own GPU (a host pointer or another GPU's memory is refused here)
+        if (src[i] && !on_handles_device(s, src[i]))
+            return fail(TINYMPC_ERR_INVALID_INPUT, "%s: the models are not device memory of the handle's GPU %d", verb, s->device);
+    if ((rc = bind_device(s))) return rc;
+    InstState &in = s->inst;
+    if ((rc = enter_model_mode(s))) return rc;
+    if (s->layout_m) return TINYMPC_OK;
+    const size_t nx = s->nx, nu = s->nu;
     const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     HIP_TRY(hipMemcpyAsync(in.mA + first * nx * nx, A, sizeof(double) * nx * nx * count, kind, s->stream));
     HIP_TRY(hipMemcpyAsync(in.mB + first * nx * nu, B, sizeof(double) * nx * nu * count, kind, s->stream));
     if (fdyn) HIP_TRY(hipMemcpyAsync(in.mf + first * nx, fdyn, sizeof(double) * nx * count, kind, s->stream));
     else HIP_TRY(hipMemsetAsync(in.mf + first * nx, 0, sizeof(double) * nx * count, s->stream));
-    // the cost diagonals, each + rho (tiny_api.cpp:90-91): from the caller's device memory as it lies, from host memory gathered first
+    // the raw cost diagonals: from the caller's device memory as it lies, from host memory gathered first (rebuild_inst_models adds rho)
     std::vector<double> hd;
     InstDiagParams dq{}, dr{};
     dq.n = s->nx; dr.n = s->nu;
-    dq.first = dr.first = first; dq.count = dr.count = count; dq.add = dr.add = s->rho;
-    dq.dst = in.mQd; dr.dst = in.mRd;
+    dq.first = dr.first = first; dq.count = dr.count = count;
+    dq.dst = in.mQ0; dr.dst = in.mR0;
     if (on_device) {
         dq.src = Q; dq.src_stride = nx * nx; dq.src_step = s->nx + 1;
         dr.src = R; dr.src_stride = nu * nu; dr.src_step = s->nu + 1;
@@ -1294,10 +1338,44 @@ int set_model_batch(tinympc_solver *s, const double *A, const double *B, const d
     }
     HIP_TRY(launch_store_inst_diag(dq, s->stream));
     HIP_TRY(launch_store_inst_diag(dr, s->stream));
-    if ((rc = precompute_inst_models(s, first, count))) return rc;
-    in.mark(first, first + count);
+    if ((rc = rebuild_inst_models(s, first, count))) return rc;
     // the caller keeps ownership of its buffers: the copies have completed when the call returns (the tinympc_set_x0_batch_device rule)
     HIP_TRY(hipStreamSynchronize(s->stream));
+    return TINYMPC_OK;
+}
+
+// tinympc_set_rho_batch (+ _device): the same mode, entered the same way; the instances named here get their own rho, and with it their
+// own Qd + rho, cache, operators and table rows -- from the raw diagonals of whatever model they hold, so the order of the two verbs
+// does not matter. Everything is validated before anything is written (device input: on the device, one flag read back).
+int set_rho_batch(tinympc_solver *s, const double *rho, bool on_device, int first, int count) {
+    const char *verb = on_device ? "set_rho_batch_device" : "set_rho_batch";
+    int rc = check_handle(s);
+    if (rc) return rc;
+    if (!rho) return fail(TINYMPC_ERR_INVALID_INPUT, "%s requires rho", verb);
+    if (first < 0 || count < 1 || first + count > s->batch)
+        return fail(TINYMPC_ERR_INVALID_INPUT, "%s: instance range [%d, %d) is empty or outside batch of %d", verb, first, first + count, s->batch);
+    InstState &in = s->inst;
+    if (on_device) {
+        if (!on_handles_device(s, rho))
+            return fail(TINYMPC_ERR_INVALID_INPUT, "%s: rho is not device memory of the handle's GPU %d", verb, s->device);
+        if ((rc = bind_device(s))) return rc;
+        if (!in.mflag && (rc = dalloc(s, &in.mflag, (size_t)1))) return rc;
+        int bad = 0;
+        HIP_TRY(hipMemsetAsync(in.mflag, 0, sizeof(int), s->stream));
+        HIP_TRY(launch_check_positive(rho, count, in.mflag, s->stream));
+        if ((rc = download(s, &bad, in.mflag, sizeof(int)))) return rc;
+        if (bad) return fail(TINYMPC_ERR_INVALID_INPUT, "%s: every rho must be a finite number > 0", verb);
+    } else {
+        for (int b = 0; b < count; ++b)
+            if (!(rho[b] > 0.0) || !std::isfinite(rho[b]))
+                return fail(TINYMPC_ERR_INVALID_INPUT, "%s: rho[%d] = %g. Expected a finite number > 0.", verb, b, rho[b]);
+        if ((rc = bind_device(s))) return rc;
+    }
+    if ((rc = enter_model_mode(s))) return rc;
+    in.rho_verb = true;
+    HIP_TRY(hipMemcpyAsync(in.mrho + first, rho, sizeof(double) * count, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s->stream));
+    if (!s->layout_m && (rc = rebuild_inst_models(s, first, count))) return rc;
+    HIP_TRY(hipStreamSynchronize(s->stream));  // (the caller keeps ownership of its buffer: copied when the call returns)
     return TINYMPC_OK;
 }
 
@@ -1312,11 +1390,15 @@ int tinympc_set_model_batch_device(tinympc_solver *s, const double *d_A, const d
     return set_model_batch(s, d_A, d_B, d_fdyn, d_Q, d_R, true, first, count);
 }
 
+int tinympc_set_rho_batch(tinympc_solver *s, const double *rho, int first, int count) { return set_rho_batch(s, rho, false, first, count); }
+int tinympc_set_rho_batch_device(tinympc_solver *s, const double *d_rho, int first, int count) { return set_rho_batch(s, d_rho, true, first, count); }
+
 int tinympc_clear_model_batch(tinympc_solver *s) {
     int rc = check_handle(s);
     if (rc) return rc;
     if (!s->inst.models) return TINYMPC_OK;
     s->inst.models = false;
+    s->inst.rho_verb = false;  // (and every instance is back on the shared rho)
     // the rows that stay in use (per-instance references / bounds) are built from the shared Pinf and cost diagonals again
     if (s->inst_tables()) s->inst.mark(0, s->batch);
     return TINYMPC_OK;
@@ -1384,7 +1466,9 @@ int tinympc_get_rho_batch(tinympc_solver *s, double *rho_out, int first, int cou
     if (!rho_out || first < 0 || count < 0 || first + count > s->batch)
         return fail(TINYMPC_ERR_INVALID_INPUT, "get_rho_batch: range [%d, %d) outside the batch of %d", first, first + count, s->batch);
     if ((rc = bind_device(s))) return rc;
-    return download(s, rho_out, s->drho_inst + first, sizeof(double) * count);
+    // (per-instance models: the instance's own rho, which reset_workspace keeps; otherwise the adaptive-rho value / the setup value)
+    const double *src = (s->inst.models && s->inst.mrho) ? s->inst.mrho : s->drho_inst;
+    return download(s, rho_out, src + first, sizeof(double) * count);
 }
 
 int tinympc_get_solution_device_ptrs(tinympc_solver *s, const double **d_x, const double **d_u) {

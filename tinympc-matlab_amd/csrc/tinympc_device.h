@@ -45,7 +45,9 @@ __device__ __forceinline__ void host_store(double *p, double v) { __hip_atomic_s
 
 struct PrecomputeParams {
     int nx, nu;
-    double rho;
+    // rho: the one system's. The batched form (count > 0) reads system b's from rho_sys[b] instead (per-instance rho,
+    // tinympc_set_rho_batch); the two share the slot so that the single launch's argument block stays as it was.
+    union { double rho; const double *rho_sys; };
     const double *A, *B, *fdyn, *Qd, *Rd;  // Qd/Rd: diagonals already + rho (tiny_api.cpp:90-91)
     double *Kinf, *Pinf, *Quu_inv, *AmBKt, *APf, *BPf;
     int *info;        // info[0] = Riccati steps taken
@@ -54,7 +56,8 @@ struct PrecomputeParams {
     // The batched form (per-instance models, tinympc_set_model_batch): `count` systems in one launch, one wavefront (k_precompute_rows)
     // or workgroup (k_precompute) each, blockIdx.x selecting the system. System b's blocks lie b * (block size) behind the pointers
     // above -- nx*nx (A, Pinf, AmBKt), nx*nu (B, Kinf), nx (fdyn, Qd, APf), nu (Rd, BPf), nu*nu (Quu_inv) --, its info at
-    // info + 4 b, its scratch at scratch + b * scratch_stride. 0: the one system of tinympc_setup, the launch as it always was.
+    // info + 4 b, its scratch at scratch + b * scratch_stride, its rho at rho_sys[b]. 0: the one system of tinympc_setup, the launch
+    // as it always was.
     int count;
     size_t scratch_stride;
 };
@@ -272,13 +275,15 @@ struct InstModelFillParams {
     const int *info_src;
     int *info_dst;
 };
-// dst[(first + b) * n + i] = src[b * src_stride + i * src_step] + add, b < count: the cost diagonals of per-instance models (+ rho,
-// tiny_api.cpp:90-91) from full matrices (stride n*n, step n+1) or from staged diagonals (stride n, step 1)
+// dst[(first + b) * n + i] = src[b * src_stride + i * src_step] + add, b < count: the cost diagonals of per-instance models from full
+// matrices (stride n*n, step n+1) or from staged diagonals (stride n, step 1). add_inst: instance first+b adds add_inst[first + b]
+// instead of `add` -- Q_b + rho_b from the raw diagonals, ONE addition as in tiny_api.cpp:90-91.
 struct InstDiagParams {
     const double *src;
     size_t src_stride;
     int src_step, n, first, count;
     double add;
+    const double *add_inst;
     double *dst;
 };
 struct InstTableParams {
@@ -459,6 +464,8 @@ hipError_t launch_store_inst_refs(const InstRefStoreParams &p, hipStream_t strea
 hipError_t launch_build_inst_tables(const InstTableParams &p, hipStream_t stream);
 hipError_t launch_fill_inst_models(const InstModelFillParams &p, hipStream_t stream);
 hipError_t launch_store_inst_diag(const InstDiagParams &p, hipStream_t stream);
+// *flag <- 1 if any of v[0, n) is not a finite number > 0 (per-instance rho from device memory: validated where it lies)
+hipError_t launch_check_positive(const double *v, int n, int *flag, hipStream_t stream);
 // Layout A: one wavefront per workgroup, all ADMM state in LDS (lowest latency, 2 waves per CU). One kernel body, three
 // variants: the box path (k_admm_solve), plus the cone / linear slack families (k_admm_solve_fam: extra duals and the extra
 // linear-cost term in HBM), plus adaptive rho (k_admm_solve_adapt: per-instance rho, Taylor-updated operators; needs

@@ -68,15 +68,20 @@ struct InstState {
     double *lrg = nullptr, *bndg = nullptr;  // knot 0's linref [instance][W] and lo | hi rows (layout D's goal form)
     double *bnd = nullptr;                   // layout A's lo | hi rows (inst_bnd_doubles; bounds mode)
     double *stage = nullptr;                 // device staging of one-column host input
-    // Per-instance models (tinympc_set_model_batch): on from its first call until tinympc_clear_model_batch. Every instance's model
-    // (A | B | fdyn | Qd | Rd, the diagonals + rho as PrecomputeParams wants them), its LQR cache and its operator block, each array
-    // [batch][block]; filled from the shared model, cache and operators when the mode begins, recomputed for the instances a call names
-    // (batched precompute + operator builder, inside the call). The mode runs on layout A's InstModels variant, always with the
+    // Per-instance models (tinympc_set_model_batch, tinympc_set_rho_batch): on from the first call of either until
+    // tinympc_clear_model_batch. Every instance's model (A | B | fdyn | Qd | Rd, the diagonals + rho as PrecomputeParams wants them), its
+    // LQR cache and its operator block, each array [batch][block]; filled from the shared model, cache and operators when the mode
+    // begins, recomputed for the instances a call names (batched precompute + operator builder, inside the call). The store also keeps
+    // the RAW cost diagonals (mQ0 | mR0) and every instance's rho (mrho: the handle's until tinympc_set_rho_batch names the instance):
+    // Qd_b = Q0_b + rho_b is formed from them by one addition, whichever verb came last, so the two verbs commute bit for bit. The mode runs on layout A's InstModels variant, always with the
     // per-instance reference and clamp rows, which are then built from the instance's own Pinf and cost diagonals -- or, once the caller
     // has asked for specialised kernels (tinympc_prepare) and references and bounds are constant over the horizon, on layout D's IMOD form.
     bool models = false;
     int d_models = -1;  // layout D's per-instance model form (16 lanes; compiled in or run-time specialised): -1 not asked yet, 0 no, 1 yes
+    bool rho_verb = false;  // ... and tinympc_set_rho_batch was among the calls (the refusals name it)
     double *mA = nullptr, *mB = nullptr, *mf = nullptr, *mQd = nullptr, *mRd = nullptr;
+    double *mQ0 = nullptr, *mR0 = nullptr, *mrho = nullptr;  // raw diagonals [batch][nx] / [batch][nu], rho [batch] (SolveParams::rho_inst of the model kernels)
+    int *mflag = nullptr;                    // one flag: the device-side validation of tinympc_set_rho_batch_device
     double *cK = nullptr, *cP = nullptr, *cQuu = nullptr, *cAm = nullptr, *cAPf = nullptr, *cBPf = nullptr;
     int *cinfo = nullptr;                    // [batch][4]: Riccati steps (and the rows kernel's clocks)
     double *ops = nullptr;                   // [batch][ops_doubles(W, KT)]: SolveParams::ops of the InstModels variant

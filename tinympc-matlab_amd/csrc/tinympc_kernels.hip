@@ -127,7 +127,10 @@ __global__ void __launch_bounds__(PRE_THREADS) k_precompute(const PrecomputePara
     double *red = lds;  // PRE_THREADS doubles, always in LDS
     double *w = p.use_lds ? (lds + PRE_THREADS) : p.scratch;
     const int nx = p.nx, nu = p.nu, tid = threadIdx.x;
-    const double rho = p.rho;
+    double rho_;
+    if constexpr (BATCH) rho_ = p_.rho_sys[blockIdx.x];  // (the system's own rho)
+    else rho_ = p.rho;
+    const double rho = rho_;
     double *Ktp1 = w;                w += nu * nx;
     double *Kinf = w;                w += nu * nx;
     double *BtP = w;                 w += nu * nx;
@@ -709,7 +712,7 @@ __global__ void __launch_bounds__(256) k_store_inst_diag(const InstDiagParams p)
     const size_t total = (size_t)p.n * p.count;
     for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
         const size_t b = idx / p.n, i = idx % p.n;
-        p.dst[(size_t)(p.first + b) * p.n + i] = p.src[b * p.src_stride + i * p.src_step] + p.add;
+        p.dst[(size_t)(p.first + b) * p.n + i] = p.src[b * p.src_stride + i * p.src_step] + (p.add_inst ? p.add_inst[p.first + b] : p.add);
     }
 }
 hipError_t launch_store_inst_diag(const InstDiagParams &p, hipStream_t stream) {
@@ -717,6 +720,17 @@ hipError_t launch_store_inst_diag(const InstDiagParams &p, hipStream_t stream) {
     if (total == 0) return hipSuccess;
     const size_t blocks = (total + 255) / 256;
     hipLaunchKernelGGL(k_store_inst_diag, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, stream, p);
+    return hipGetLastError();
+}
+
+__global__ void __launch_bounds__(256) k_check_positive(const double *v, int n, int *flag) {
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256)
+        if (!(v[i] > 0.0 && v[i] <= 1.79769313486231570815e308)) *flag = 1;  // (NaN fails the first test, +inf the second)
+}
+hipError_t launch_check_positive(const double *v, int n, int *flag, hipStream_t stream) {
+    if (n <= 0) return hipSuccess;
+    const int blocks = (n + 255) / 256;
+    hipLaunchKernelGGL(k_check_positive, dim3(blocks < 1024 ? blocks : 1024), dim3(256), 0, stream, v, n, flag);
     return hipGetLastError();
 }
 

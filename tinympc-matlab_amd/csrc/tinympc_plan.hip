@@ -174,6 +174,7 @@ namespace host {
 //   per-instance references / bounds   D's goal form  >  A (box path only: with the families, adaptive rho or layout M, launch() refuses)
 //   per-instance models                D's model form (only after tinympc_prepare: 16 lanes, references and bounds constant over the horizon,
 //                                      a horizon its per-wavefront operator plan holds)  >  A (the same refusals)
+//                                      (the mode of tinympc_set_model_batch AND tinympc_set_rho_batch: one form, rho always read per instance)
 LaunchPlan current_plan(const tinympc_solver *s) {
     LaunchPlan pl;
     const bool fam = s->families_active(), adaptive = s->st.adaptive_rho != 0, d = s->use_layout_d();
@@ -349,7 +350,10 @@ int launch(tinympc_solver *s, bool timed) {
         int n = 0;
         if (r) { what[n] = "per-instance references (set_x_ref_batch / set_u_ref_batch)"; back[n++] = "tinympc_set_x_ref / tinympc_set_u_ref return to shared references"; }
         if (b) { what[n] = "per-instance bounds (set_bound_constraints_batch)"; back[n++] = "tinympc_set_bound_constraints returns to shared bounds"; }
-        if (m) { what[n] = "per-instance models (set_model_batch)"; back[n++] = "tinympc_clear_model_batch returns to the shared model"; }
+        if (m) {  // (entered through tinympc_set_rho_batch: the message names that verb too)
+            what[n] = s->inst.rho_verb ? "per-instance models (set_model_batch) with per-instance rho (set_rho_batch)" : "per-instance models (set_model_batch)";
+            back[n++] = s->inst.rho_verb ? "tinympc_clear_model_batch returns to the shared model and rho" : "tinympc_clear_model_batch returns to the shared model";
+        }
         std::string subj, way;
         for (int i = 0; i < n; ++i) {
             subj += std::string(i == 0 ? "" : i == n - 1 ? " and " : ", ") + what[i];
@@ -428,6 +432,7 @@ int launch(tinympc_solver *s, bool timed) {
         s->refs_on_host = false;  // the kernel brings the tables and the device copies up to date
     }
     p.adapt = s->dadapt; p.rho_inst = s->drho_inst;
+    if (pl.inst_models) p.rho_inst = s->inst.mrho;  // (the model kernels read rho per instance: the handle's, or what tinympc_set_rho_batch set)
     if (pl.inst_refs) {
         p.iref_lr = pl.kernel == KernelId::A ? s->inst.lr_rows() : s->inst.lrg;
         p.iref_pn = s->inst.pn;

@@ -220,7 +220,10 @@ __global__ void __launch_bounds__(64) k_precompute_rows(const PrecomputeParams p
     const bool xl = r < nx;                          // x-lane with a real row
     const int u = (r >= NXP && r < NXP + NUP) ? r - NXP : -1;  // u-lane (padded rows included)
     const bool ul = u >= 0 && u < nu;                // ... with a real row
-    const double rho = p.rho;
+    double rho_;
+    if constexpr (BATCH) rho_ = p_.rho_sys[blockIdx.x];  // (the system's own rho)
+    else rho_ = p.rho;
+    const double rho = rho_;
     const double *A = p.A, *B = p.B;
 
     double XA[NXP], Ar[NXP], Br[NUP], P[NXP];

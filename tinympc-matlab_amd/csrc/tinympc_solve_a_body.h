@@ -155,6 +155,8 @@
     double rho = p.rho;
     const double rho0 = p.rho, dgr = ADAPT ? ops[2 * M + 2 * W + r] : 0.0;  // Q + rho0 / R + rho0 diagonal of this row (tiny_api.cpp:90-91)
     const double pnref0 = pnref, dpnref = ADAPT ? p.adapt[5 * M + r] : 0.0;
+    // per-instance models: the instance's own rho (tinympc_set_rho_batch; the handle's where the verb never named it), constant over the solve
+    if constexpr (IMOD) rho = inst_ok ? p.rho_inst[inst] : rho0;
     if constexpr (ADAPT) {
         rho = inst_ok ? p.rho_inst[inst] : rho0;  // persists across solves like cache->rho
         pnref = fma(rho - rho0, dpnref, pnref0);

@@ -384,7 +384,8 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
                 const long ib = grp * IPW + jj;
                 const double *const ops_i = p.ops + (size_t)(ib < p.batch ? ib : 0) * ops_doubles(W, KT);
                 const double v = (k < KT) ? ops_i[(size_t)which * W * KT + (size_t)rr * KT + k] : 0.0;
-                sOpsW[jj * D_IMOD_STRIDE + e] = (FOLD && which == 1 && k >= NX) ? -p.rho * v : v;
+                const double rho_i = ib < p.batch ? p.rho_inst[ib] : p.rho;  // (the block's own instance's rho: tinympc_set_rho_batch)
+                sOpsW[jj * D_IMOD_STRIDE + e] = (FOLD && which == 1 && k >= NX) ? -rho_i * v : v;
             }
         }
     } else {
@@ -567,6 +568,8 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
         dgr = p.ops[(size_t)2 * W * KT + 2 * W + r];  // Q + rho0 / R + rho0 diagonal of this row (tiny_api.cpp:90-91)
         pnref = fma(rho - rho0, dpnref, pnref0);
     }
+    // IMOD: the instance's own rho (tinympc_set_rho_batch; the handle's where the verb never named it) -- a lane variable, constant over the solve
+    if constexpr (IMOD) rho = inst_ok ? p.rho_inst[inst] : rho0;
     double nrho = -rho;
     const double lo_c = IGOAL ? (inst_ok ? p.ibnd[inst * W + r] : 0.0) : p.tables[W + r];
     const double hi_c = IGOAL ? (inst_ok ? p.ibnd[(size_t)p.groups * 64 + inst * W + r] : 0.0) : p.tables[(size_t)TOFF + W + r];

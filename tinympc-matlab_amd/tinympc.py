@@ -343,7 +343,7 @@ class TinyMPC:
         """Per-instance models for instances first, first+1, ...: numpy arrays of shape (nx, nx, count), (nx, nu, count), (nx, nx, count),
         (nu, nu, count) and, optionally, fdyn (nx, count) -- or contiguous float64 CUDA tensors with the same memory layout, (count, nx, nx)
         holding A_b', (count, nu, nx) holding B_b', (count, nx, nx), (count, nu, nu), (count, nx). Of Q and R only the diagonals are used;
-        rho, N and the settings stay the handle's. Instance b then solves what a single-instance solver set up with its model would
+        N and the settings stay the handle's, and so does rho unless set_rho_batch() gives an instance its own. Instance b then solves what a single-instance solver set up with its model would
         solve. clear_model_batch() returns every instance to the shared model; get_cache_batch() reads the per-instance caches."""
         self._check_setup()
         nx, nu = self.nx, self.nu
@@ -378,8 +378,28 @@ class TinyMPC:
         pA, pB, pQ, pR, pf = ptrs
         _lib.check(f(self._h, pA, pB, pf, pQ, pR, int(first), count))
 
+    def set_rho_batch(self, rhos, first: int = 0):
+        """Per-instance ADMM penalty for instances first, first+1, ...: a numpy vector of `count` finite values > 0, or a contiguous
+        float64 CUDA tensor of `count` elements on the handle's GPU. Instance first+b then solves what a single-instance solver set up
+        with (its model, rhos[b]) would solve. This is the per-instance model mode of set_model_batch (the two commute; instances
+        neither names keep the shared model / rho); clear_model_batch() returns every instance to the shared model and rho, and
+        get_rho_batch() reads the values back."""
+        self._check_setup()
+        if hasattr(rhos, "data_ptr") and getattr(rhos, "is_cuda", False):
+            import torch
+            if rhos.dtype != torch.float64 or not rhos.is_contiguous() or rhos.dim() != 1:
+                raise TinyMPCError(_lib.ERR_INVALID_INPUT, "rho on the device must be a contiguous float64 tensor of shape (count,), got %s %s"
+                                   % (rhos.dtype, tuple(rhos.shape)))
+            torch.cuda.current_stream(rhos.device).synchronize()  # (the set_x0_batch contract)
+            _lib.check(self._L.tinympc_set_rho_batch_device(self._h, C.c_void_p(rhos.data_ptr()), int(first), int(rhos.numel())))
+            return
+        a = np.ascontiguousarray(np.asarray(rhos, dtype=np.float64))
+        if a.ndim != 1:
+            raise TinyMPCError(_lib.ERR_INVALID_INPUT, "rho must be a vector of count values, got %s" % (a.shape,))
+        _lib.check(self._L.tinympc_set_rho_batch(self._h, _p(a), int(first), int(a.size)))
+
     def clear_model_batch(self):
-        """Every instance back on the shared model of setup()."""
+        """Every instance back on the shared model and rho of setup()."""
         self._check_setup()
         _lib.check(self._L.tinympc_clear_model_batch(self._h))
 
@@ -567,7 +587,8 @@ class TinyMPC:
         return dict(iter=it, status=st, residuals=res)
 
     def get_rho_batch(self, first: int = 0, count: int | None = None) -> np.ndarray:
-        """Current rho of every instance (adaptive rho adapts it per instance and keeps it across solves)."""
+        """Current rho of every instance (adaptive rho adapts it per instance and keeps it across solves; with per-instance models on,
+        the instance's own value -- set_rho_batch)."""
         self._check_setup()
         count = self.batch - first if count is None else count
         rho = np.zeros(count)

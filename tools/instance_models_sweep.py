@@ -14,6 +14,14 @@ Layout D (--d): the same solve with one constant box per instance (what layout D
 interleaved and reported in the same way.
     python tools/instance_models_sweep.py --d [--N 50 | --N 20]
 
+Per-instance rho (--rho --parent-lib PATH): the --d handle kinds (layout D N=50, layout D N=20, layout A N=50; a model per instance,
+one constant box per instance) with rho_b spread log-uniformly over [0.5, 4] x rho (set_rho_batch), against the SAME handles without
+the verb on the library of the parent commit at PATH (built from a checkout of the parent). Every measurement is a fresh process --
+this tree's library and the parent's alternate, `--rounds` times each -- so the two are interleaved in one call and share its noise;
+the bar: the median of this tree's rounds lies inside the spread of the parent's rounds. Also the wall time of set_rho_batch for
+`--batch` values beside set_model_batch for as many models (the precompute is the same launch). Prints a table.
+    python tools/instance_models_sweep.py --rho --parent-lib /path/to/parent/libtinympc_hip.so
+
 Setup (--setup): wall milliseconds of tinympc_set_model_batch for `--batch` quadrotor and cartpole models -- the first call (which
 allocates the per-instance stores and fills them from the shared model), then `--reps` further calls, from host memory and, where
 device memory can be filled, from device memory -- beside the wall time of one single-instance tinympc_setup of the same problem.
@@ -99,6 +107,79 @@ def solve_sweep(pkg, a):
         s.reset()
 
 
+RHO_KINDS = [("D N=50", 50, True), ("D N=20", 20, True), ("A N=50", 50, False)]  # (name, horizon, prepare()?)
+
+
+def rho_child(pkg, a):
+    """One process of the --rho leg: the three handle kinds on whatever library this process loaded; one JSON line."""
+    P, L = pkg.problems, pkg.load_library()
+    has_verb = hasattr(L, "tinympc_set_rho_batch")
+    out = dict(library="this" if has_verb else "parent", kernel_ms={}, kernel={})
+    for name, N, prepare in RHO_KINDS:
+        s = make(pkg, "models-D" if prepare else "models-A", a.batch, N, a.iters)
+        if has_verb:
+            f = np.exp(np.random.default_rng(11).uniform(np.log(0.5), np.log(4.0), a.batch))
+            s.set_rho_batch(P.quadrotor(N).rho * f)
+        s.solve_timed()  # warm-up: first launch, table builds
+        out["kernel_ms"][name] = float(np.median([s.solve_timed() for _ in range(a.reps)]))
+        out["kernel"][name] = "%s %s" % (s.launch_info()["layout"], s.jit_info())
+        s.reset()
+    if has_verb:  # the verbs' wall time, first call (allocates and fills the stores) and repeats
+        prob = P.quadrotor(50)
+        A, B, Q, R, f = models(prob, a.batch)
+        rhos = prob.rho * np.exp(np.random.default_rng(11).uniform(np.log(0.5), np.log(4.0), a.batch))
+        for key, call in (("set_rho_batch_ms", lambda s: s.set_rho_batch(rhos)), ("set_model_batch_ms", lambda s: s.set_model_batch(A, B, Q, R, fdyn=f))):
+            s = pkg.TinyMPC()
+            s.setup(prob.A, prob.B, prob.Q, prob.R, prob.N, batch=a.batch, rho=prob.rho)
+            wall = []
+            for _ in range(1 + a.reps):
+                t0 = time.perf_counter()
+                call(s)
+                wall.append(1e3 * (time.perf_counter() - t0))
+            out[key] = wall
+            s.reset()
+    print("RHO-CHILD " + json.dumps(out), flush=True)
+
+
+def rho_sweep(a):
+    """The parent of the --rho leg: starts the children (it never opens the GPU itself) and prints the table."""
+    import subprocess
+    if not a.parent_lib or not os.path.exists(a.parent_lib):
+        raise SystemExit("--rho needs --parent-lib: libtinympc_hip.so built from the parent commit")
+    rows = {"this": [], "parent": []}
+    for rnd in range(a.rounds):
+        for lib in ("this", "parent") if rnd % 2 == 0 else ("parent", "this"):
+            env = dict(os.environ)
+            env.pop("TINYMPC_HIP_LIBRARY", None)
+            if lib == "parent":
+                env["TINYMPC_HIP_LIBRARY"] = os.path.abspath(a.parent_lib)
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--rho-child", "--batch", str(a.batch), "--iters", str(a.iters), "--reps", str(a.reps)],
+                               env=env, capture_output=True, text=True, timeout=400)
+            line = [l for l in r.stdout.splitlines() if l.startswith("RHO-CHILD ")]
+            if r.returncode != 0 or not line:
+                raise SystemExit("round %d (%s) failed with %d:\n%s\n%s" % (rnd, lib, r.returncode, r.stdout[-2000:], r.stderr[-2000:]))
+            rec = json.loads(line[0][len("RHO-CHILD "):])
+            assert rec["library"] == lib, rec
+            rows[lib].append(rec)
+            print("# round %d %-6s %s" % (rnd, lib, json.dumps(rec["kernel_ms"])), flush=True)
+    print("per-instance rho, %d quadrotors x %d forced iterations, kernel ms (median of %d launches per round, %d rounds, a fresh process each)"
+          % (a.batch, a.iters, a.reps, a.rounds))
+    print("%-8s | %-34s | %-34s | %-9s | %-17s | %s" % ("handle", "parent (set_model_batch)", "this tree (+ set_rho_batch)", "median", "parent spread", "inside"))
+    for name, _, _ in RHO_KINDS:
+        par = [r["kernel_ms"][name] for r in rows["parent"]]
+        new = [r["kernel_ms"][name] for r in rows["this"]]
+        med = float(np.median(new))
+        print("%-8s | %-34s | %-34s | %9.4f | %7.4f - %7.4f | %s" % (name, " ".join("%.4f" % v for v in par), " ".join("%.4f" % v for v in new), med,
+                                                                    min(par), max(par), "yes" if min(par) <= med <= max(par) else "NO"))
+    for name, _, _ in RHO_KINDS:
+        print("kernel %-8s this: %s | parent: %s" % (name, rows["this"][0]["kernel"][name], rows["parent"][0]["kernel"][name]))
+    for key in ("set_rho_batch_ms", "set_model_batch_ms"):
+        first = [r[key][0] for r in rows["this"]]
+        rest = [v for r in rows["this"] for v in r[key][1:]]
+        print("%-18s %d quadrotor N=50 instances, wall ms: first call %s | repeats median %.3f (min %.3f, max %.3f)"
+              % (key[:-3], a.batch, " ".join("%.3f" % v for v in first), float(np.median(rest)), min(rest), max(rest)))
+
+
 def device_copy(pkg, arrays):
     """Device copies of `arrays` through the HIP runtime the library itself uses, or None where that runtime cannot be found."""
     pkg.load_library()
@@ -179,10 +260,17 @@ def main():
     ap.add_argument("--d", action="store_true")
     ap.add_argument("--setup", action="store_true")
     ap.add_argument("--probe", type=int, default=0)
+    ap.add_argument("--rho", action="store_true")
+    ap.add_argument("--rho-child", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--parent-lib", default="")
     a = ap.parse_args()
+    if a.rho:
+        return rho_sweep(a)
     import __graft_entry__ as ge
     pkg = ge.load_package()
-    if a.probe:
+    if a.rho_child:
+        rho_child(pkg, a)
+    elif a.probe:
         probe(pkg, a)
     elif a.setup:
         setup_sweep(pkg, a)
