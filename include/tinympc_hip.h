@@ -235,6 +235,50 @@ int tinympc_set_u_ref_batch(tinympc_solver *s, const double *Urefs, int rows, in
 int tinympc_set_x_ref_batch_device(tinympc_solver *s, const double *d_Xrefs, int rows, int cols, int first, int count);
 int tinympc_set_u_ref_batch_device(tinympc_solver *s, const double *d_Urefs, int rows, int cols, int first, int count);
 
+/* Reference tracks: per-instance sliding reference windows kept on the device ("upload once, step per tick").
+ * Xtracks: nx x T x count, column-major, instance b's block at b*nx*T; Utracks: nu x T x count likewise. T >= 1 is the track's length
+ * in knots, independent of N and of the other half's. Every instance also has a step k >= 0 (one per instance, serving both halves;
+ * 0 until set). Instance b at step k then solves exactly what it would solve after tinympc_set_x_ref_batch with the trajectory
+ * X_b[:, min(k+i, Tx-1)], i = 0..N-1, and tinympc_set_u_ref_batch with U_b[:, min(k+i, Tu-1)], i = 0..N-2 -- bit for bit, on the same
+ * kernel: the last knot is held beyond the end of the track, and the window's rows are built on the device from track and step by
+ * the row builder of the per-instance references (from the instance's own Pinf and cost diagonals when per-instance models are on), so
+ * a closed-loop tick uploads x0 and nothing else.
+ * Track mode is per half. The first track call of a half must name the whole batch (first = 0, count = batch); later calls may
+ * replace a sub-range with the same T, a whole-batch call may change T; replacing a track does not touch the steps. A half in track
+ * mode IS a half with per-instance trajectories: it turns per-instance references on for that half, runs on layout A (even with
+ * T = 1: never layout D's goal form), " reference-track" is appended to tinympc_get_jit_info, and every refusal of per-instance
+ * references applies unchanged (the cone / linear families, adaptive rho, nx+nu > 64: a solve returns TINYMPC_ERR_UNSUPPORTED;
+ * tinympc_session_begin likewise). tinympc_set_x_ref / _u_ref returns the half to shared references; a whole-batch
+ * tinympc_set_x_ref_batch / _u_ref_batch returns it to plain per-instance references, while one on a sub-range returns
+ * TINYMPC_ERR_INVALID_INPUT (name the whole batch). The store of a half that left the mode is kept for its next track; the steps stay.
+ * reset_workspace, update_settings, the bound and model verbs, the solve verbs and mpc_step_batch keep tracks and steps.
+ * Everything is validated before anything is written: invalid arguments (a first call on a sub-range, a sub-range call with another
+ * T, T < 1, a range beyond the batch, a negative step, host memory or another GPU's memory handed to a _device form) return
+ * TINYMPC_ERR_INVALID_INPUT and leave mode, store, steps and rows as they were, and so does a failed allocation (TINYMPC_ERR_ALLOC).
+ * Single-instance handles: the same verbs on instance 0 -- the library keeps the track on the host and forwards the current window
+ * through tinympc_set_x_ref / tinympc_set_u_ref whenever track or step changes, so the families, the session and resident solves work
+ * with tracks (inside a session a window moved up by one knot sends one column). The input has been copied when the call returns. */
+int tinympc_set_x_ref_track_batch(tinympc_solver *s, const double *Xtracks, int rows, int T, int first, int count);
+int tinympc_set_u_ref_track_batch(tinympc_solver *s, const double *Utracks, int rows, int T, int first, int count);
+/* Same, from device memory on the handle's GPU; same contract as tinympc_set_x0_batch_device. */
+int tinympc_set_x_ref_track_batch_device(tinympc_solver *s, const double *d_Xtracks, int rows, int T, int first, int count);
+int tinympc_set_u_ref_track_batch_device(tinympc_solver *s, const double *d_Utracks, int rows, int T, int first, int count);
+/* The steps of instances [first, first+count): steps[count], each >= 0 (a step beyond the end of a track holds its last knot). The
+ * _device form reads device memory of the handle's GPU and validates it there (one flag read back). The rows of the range are
+ * rebuilt at the next launch. */
+int tinympc_set_ref_step_batch(tinympc_solver *s, const int *steps, int first, int count);
+int tinympc_set_ref_step_batch_device(tinympc_solver *s, const int *d_steps, int first, int count);
+/* Every instance's step += delta, on the device: one small kernel on the handle's stream, saturating at INT_MAX (it cannot wrap), no
+ * copy and no synchronisation for delta >= 0. A delta < 0 that would take some step below 0 returns TINYMPC_ERR_INVALID_INPUT and
+ * changes nothing (validated on the device first: one flag read back, for negative deltas only). */
+int tinympc_advance_ref_step_batch(tinympc_solver *s, int delta);
+/* tinympc_mpc_step_batch adds delta >= 0 to every instance's step AFTER its solve (the tick solves the window of the step it found);
+ * nothing is read back. 0 (the default) switches it off. tinympc_mpc_step_batch only: the other solve verbs and the session leave the
+ * steps alone. The setting, like the steps, outlives the tracks: while it is on, every tick queues the one small kernel that moves
+ * the steps, also on a handle whose halves have both left track mode -- switch it off with the tracks where that launch matters. */
+int tinympc_set_ref_auto_advance(tinympc_solver *s, int delta);
+int tinympc_get_ref_step_batch(tinympc_solver *s, int *steps_out, int first, int count);
+
 /* Per-instance box bounds for instances [first, first+count) of a batched handle.
  * x_min, x_max: nx x cols x count, column-major, instance b's block at b*nx*cols; u_min, u_max: nu x ucols x count likewise.
  * cols = N (bounds per knot; then ucols = N-1) or cols = 1 (one box per instance, held over the whole horizon; then ucols = 1).

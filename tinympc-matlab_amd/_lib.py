@@ -80,6 +80,15 @@ SIGNATURES = {
     "tinympc_set_u_ref_batch": (C.c_int, [Handle, c_double_p, C.c_int, C.c_int, C.c_int, C.c_int]),
     "tinympc_set_x_ref_batch_device": (C.c_int, [Handle, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
     "tinympc_set_u_ref_batch_device": (C.c_int, [Handle, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "tinympc_set_x_ref_track_batch": (C.c_int, [Handle, c_double_p, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "tinympc_set_u_ref_track_batch": (C.c_int, [Handle, c_double_p, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "tinympc_set_x_ref_track_batch_device": (C.c_int, [Handle, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "tinympc_set_u_ref_track_batch_device": (C.c_int, [Handle, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "tinympc_set_ref_step_batch": (C.c_int, [Handle, c_int_p, C.c_int, C.c_int]),
+    "tinympc_set_ref_step_batch_device": (C.c_int, [Handle, C.c_void_p, C.c_int, C.c_int]),
+    "tinympc_advance_ref_step_batch": (C.c_int, [Handle, C.c_int]),
+    "tinympc_set_ref_auto_advance": (C.c_int, [Handle, C.c_int]),
+    "tinympc_get_ref_step_batch": (C.c_int, [Handle, c_int_p, C.c_int, C.c_int]),
     "tinympc_set_bound_constraints_batch": (C.c_int, [Handle, c_double_p, c_double_p, c_double_p, c_double_p,
                                                       C.c_int, C.c_int, C.c_int]),
     "tinympc_set_bound_constraints_batch_device": (C.c_int, [Handle, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

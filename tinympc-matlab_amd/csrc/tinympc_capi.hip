@@ -279,7 +279,9 @@ int tinympc_set_x0(tinympc_solver *s, const double *x0, int len, int verbose) {
     return rc;
 }
 
-int tinympc_set_x_ref(tinympc_solver *s, const double *Xref, int rows, int cols, int verbose) {
+// tinympc_set_x_ref / tinympc_set_u_ref. keep_track: the call forwards the current window of a single-instance handle's reference
+// track (forward_track_window below) -- the caller's own call ends the half's track mode.
+static int set_x_ref_shared(tinympc_solver *s, const double *Xref, int rows, int cols, int verbose, bool keep_track) {
     int rc = check_handle(s);
     if (rc) return rc;
     if (!Xref) return fail(TINYMPC_ERR_INVALID_INPUT, "set_x_ref: Xref is NULL");
@@ -288,6 +290,7 @@ int tinympc_set_x_ref(tinympc_solver *s, const double *Xref, int rows, int cols,
     if (rows != s->nx || cols != s->N)
         return fail(TINYMPC_ERR_INVALID_INPUT, "State reference trajectory (x_ref) is %d x %d. Expected %d x %d.", rows, cols, s->nx, s->N);
     s->inst.x = false;  // (per-instance references: this half is shared again, for every instance)
+    if (!keep_track) { s->inst.x_track = false; s->inst.hXt.clear(); }  // (... and no longer a reference track)
     s->xref_const = rows_constant(Xref, s->nx, s->N);
     if (s->host_path()) {  // no device call: the next launch reads the pinned copy and rebuilds the table rows itself
         if (s->host_sol_state == 1 && (rc = tinympc_synchronize(s))) return rc;  // a launch in flight may be reading it
@@ -310,14 +313,18 @@ int tinympc_set_x_ref(tinympc_solver *s, const double *Xref, int rows, int cols,
     if (!rc && verbose) printf("State reference set\n");
     return rc;
 }
+int tinympc_set_x_ref(tinympc_solver *s, const double *Xref, int rows, int cols, int verbose) {
+    return set_x_ref_shared(s, Xref, rows, cols, verbose, false);
+}
 
-int tinympc_set_u_ref(tinympc_solver *s, const double *Uref, int rows, int cols, int verbose) {
+static int set_u_ref_shared(tinympc_solver *s, const double *Uref, int rows, int cols, int verbose, bool keep_track) {
     int rc = check_handle(s);
     if (rc) return rc;
     if (!Uref) return fail(TINYMPC_ERR_INVALID_INPUT, "set_u_ref: Uref is NULL");
     if (rows != s->nu || cols != s->N - 1)
         return fail(TINYMPC_ERR_INVALID_INPUT, "Control/input reference trajectory (u_ref) is %d x %d. Expected %d x %d.", rows, cols, s->nu, s->N - 1);
     s->inst.u = false;
+    if (!keep_track) { s->inst.u_track = false; s->inst.hUt.clear(); }
     s->uref_const = rows_constant(Uref, s->nu, s->N - 1);
     if (s->host_path()) {
         if (s->host_sol_state == 1 && (rc = tinympc_synchronize(s))) return rc;
@@ -340,6 +347,9 @@ int tinympc_set_u_ref(tinympc_solver *s, const double *Uref, int rows, int cols,
     s->tables_dirty = true;
     if (!rc && verbose) printf("Input reference set\n");
     return rc;
+}
+int tinympc_set_u_ref(tinympc_solver *s, const double *Uref, int rows, int cols, int verbose) {
+    return set_u_ref_shared(s, Uref, rows, cols, verbose, false);
 }
 
 int tinympc_set_bound_constraints(tinympc_solver *s, const double *x_min, const double *x_max,
@@ -506,6 +516,8 @@ int tinympc_collect_kernel_ms(tinympc_solver *s, float *kernel_ms, int capacity,
     return TINYMPC_OK;
 }
 
+static int advance_ref_steps_after_tick(tinympc_solver *s);  // (defined with the reference-track verbs below)
+
 int tinympc_mpc_step_batch(tinympc_solver *s, const double *x0s, double *u0_out) {
     int rc = check_handle(s);
     if (rc) return rc;
@@ -551,6 +563,9 @@ int tinympc_mpc_step_batch(tinympc_solver *s, const double *x0s, double *u0_out)
         HIP_TRY(hipStreamSynchronize(s->stream));
     }
     std::memcpy(u0_out, s->h_u0, sizeof(double) * nu0);
+    // reference tracks: every step moves AFTER the tick's solve -- one small kernel behind it on the stream, nothing read back; the next
+    // launch rebuilds the rows
+    if (s->inst.auto_advance && (rc = advance_ref_steps_after_tick(s))) return rc;
     return TINYMPC_OK;
 }
 
@@ -1002,6 +1017,14 @@ int tinympc_set_x0_batch_device(tinympc_solver *s, const double *d_x0s, int firs
 
 namespace {
 
+// `p` is device memory of the handle's own GPU (a host pointer or another GPU's memory is not)
+bool on_handles_device(const tinympc_solver *s, const void *p) {
+    hipPointerAttribute_t attr{};
+    const hipError_t e = hipPointerGetAttributes(&attr, p);
+    (void)hipGetLastError();
+    return e == hipSuccess && attr.type == hipMemoryTypeDevice && attr.device == s->device;
+}
+
 // One array of a per-instance verb: the handle's rows x cols block per instance, and where it goes.
 struct InstArray {
     const double *src;      // the caller's blocks, one per instance: rows x cols, or rows x 1 (one column held over the horizon)
@@ -1009,7 +1032,7 @@ struct InstArray {
     double **store;         // the per-instance store [batch][cols][rows] (InstState; alloc_inst_state)
     const double *shared;   // what every instance holds when the mode begins ...
     bool shared_const;      // ... and whether that is constant over the horizon
-    bool *constant;         // the mode's "constant over the horizon" flag
+    bool *constant;         // the mode's "constant over the horizon" flag (NULL: the caller keeps it -- reference tracks)
 };
 
 // The per-instance stores of `a`, the table rows (SolveParams::iref_lr / iref_pn / ibnd) and, for the bounds, layout A's clamp rows:
@@ -1086,9 +1109,9 @@ int set_inst_batch(tinympc_solver *s, const char *verb, const char *dev_verb, co
             const int R = a[i].rows, C = a[i].cols;
             const size_t per = (size_t)R * C;
             if (!one_col) {  // per knot: the caller's layout is the handle's
-                bool constant = !on_device;  // (device input: not looked at)
+                bool constant = !on_device && a[i].constant;  // (device input: not looked at; reference tracks: never constant)
                 for (int b = 0; constant && b < count; ++b) constant = rows_constant(a[i].src + (size_t)b * per, R, C);
-                if (!constant) *a[i].constant = false;
+                if (!constant && a[i].constant) *a[i].constant = false;
                 HIP_TRY(hipMemcpyAsync(*a[i].store + (size_t)first * per, a[i].src, sizeof(double) * per * count,
                                        on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s->stream));
             } else {  // one column: held over the horizon on the device
@@ -1122,6 +1145,20 @@ int set_ref_batch(tinympc_solver *s, bool is_x, const double *src, bool on_devic
     if (rows != R || (cols != C && cols != 1))
         return fail(TINYMPC_ERR_INVALID_INPUT, "%s: the references are %d x %d per instance. Expected %d x %d or %d x 1.", verb, rows, cols, R, C, R);
     InstState &in = s->inst;
+    bool &track = is_x ? in.x_track : in.u_track;
+    if (track && s->batch > 1) {  // a half in track mode: a whole-batch call returns it to plain per-instance references
+        if (first != 0 || count != s->batch)
+            return fail(TINYMPC_ERR_INVALID_INPUT, "%s: this half holds a reference track: name the whole batch (first = 0, count = %d) to replace it "
+                        "with per-instance references", verb, s->batch);
+        if (on_device && !on_handles_device(s, src))
+            return fail(TINYMPC_ERR_INVALID_INPUT, "%s: the references are not device memory of the handle's GPU %d",
+                        is_x ? "set_x_ref_batch_device" : "set_u_ref_batch_device", s->device);
+        if ((rc = bind_device(s))) return rc;
+        double **store = is_x ? &in.Xi : &in.Ui;
+        if (!s->layout_m && !*store && (rc = dalloc(s, store, (size_t)R * C * s->batch))) return rc;
+        track = false;  // (the track store stays for the next track; the steps stay)
+        *(is_x ? &in.x_const : &in.u_const) = true;  // as when the mode begins: the data of this call decides
+    }
     const InstArray a = {src, R, C, is_x ? &in.Xi : &in.Ui, is_x ? s->dXref : s->dUref, is_x ? s->xref_const : s->uref_const,
                          is_x ? &in.x_const : &in.u_const};
     auto shared = is_x ? +[](tinympc_solver *q, const double *const *h) { return tinympc_set_x_ref(q, h[0], q->nx, q->N, 0); }
@@ -1173,6 +1210,237 @@ int tinympc_set_x_ref_batch_device(tinympc_solver *s, const double *d_Xrefs, int
 }
 int tinympc_set_u_ref_batch_device(tinympc_solver *s, const double *d_Urefs, int rows, int cols, int first, int count) {
     return set_ref_batch(s, false, d_Urefs, true, rows, cols, first, count);
+}
+
+namespace {
+
+// hipFree of a block dalloc() made (it leaves the handle's list). Only where nothing queued reads it any more.
+void dfree(tinympc_solver *s, void *p) {
+    if (!p) return;
+    (void)hipStreamSynchronize(s->stream);
+    if (!s->session_active) park_sessions_on_device(s->device, s);
+    (void)hipFree(p);
+    for (size_t i = 0; i < s->allocs.size(); ++i)
+        if (s->allocs[i] == p) { s->allocs.erase(s->allocs.begin() + (long)i); break; }
+}
+
+// Every instance's step (batched handles): allocated by the first verb that needs it, zeros.
+int ensure_ref_steps(tinympc_solver *s) {
+    InstState &in = s->inst;
+    int rc;
+    if (in.steps) return TINYMPC_OK;
+    if ((rc = dalloc(s, &in.steps, (size_t)s->batch))) return rc;
+    HIP_TRY(hipMemsetAsync(in.steps, 0, sizeof(int) * s->batch, s->stream));
+    return TINYMPC_OK;
+}
+
+// Single-instance handles: the current window of the host copy of a half's track, through the shared reference verb (pinned-host path,
+// session and resident solves included: a window moved up by one knot is what those verbs recognise).
+int forward_track_window(tinympc_solver *s, bool is_x) {
+    const InstState &in = s->inst;
+    const int R = is_x ? s->nx : s->nu, C = is_x ? s->N : s->N - 1, T = is_x ? in.Tx : in.Tu;
+    const std::vector<double> &track = is_x ? in.hXt : in.hUt;
+    std::vector<double> w((size_t)R * C);
+    for (int k = 0; k < C; ++k) {
+        const long col = (long)in.hstep + k < T ? (long)in.hstep + k : T - 1;
+        std::memcpy(w.data() + (size_t)k * R, track.data() + (size_t)col * R, sizeof(double) * R);
+    }
+    return is_x ? set_x_ref_shared(s, w.data(), R, C, 0, true) : set_u_ref_shared(s, w.data(), R, C, 0, true);
+}
+int forward_track_windows(tinympc_solver *s) {
+    int rc;
+    if (s->inst.x_track && (rc = forward_track_window(s, true))) return rc;
+    if (s->inst.u_track && (rc = forward_track_window(s, false))) return rc;
+    return TINYMPC_OK;
+}
+
+// tinympc_set_x_ref_track_batch / _u_ref_track_batch (+ _device): T knots of one half of the references per instance, kept on the
+// device; the rows of the window the instance's step selects are built there (k_build_inst_tables). Everything is validated, and every
+// block the call needs allocated, before anything is written; the upload itself is the per-instance verbs' (set_inst_batch, cols = T).
+int set_ref_track(tinympc_solver *s, bool is_x, const double *src, bool on_device, int rows, int T, int first, int count) {
+    const char *verb = is_x ? (on_device ? "set_x_ref_track_batch_device" : "set_x_ref_track_batch")
+                            : (on_device ? "set_u_ref_track_batch_device" : "set_u_ref_track_batch");
+    int rc = check_handle(s);
+    if (rc) return rc;
+    if (!src) return fail(TINYMPC_ERR_INVALID_INPUT, "%s: the tracks are NULL", verb);
+    const int R = is_x ? s->nx : s->nu;
+    if (rows != R || T < 1)
+        return fail(TINYMPC_ERR_INVALID_INPUT, "%s: the tracks are %d x %d per instance. Expected %d x T with T >= 1.", verb, rows, T, R);
+    if (first < 0 || count < 0 || first + count > s->batch)
+        return fail(TINYMPC_ERR_INVALID_INPUT, "%s: instance range [%d, %d) outside batch of %d", verb, first, first + count, s->batch);
+    if (on_device && count > 0 && !on_handles_device(s, src))
+        return fail(TINYMPC_ERR_INVALID_INPUT, "%s: the tracks are not device memory of the handle's GPU %d", verb, s->device);
+    InstState &in = s->inst;
+    bool &track = is_x ? in.x_track : in.u_track, &mode = is_x ? in.x : in.u;
+    int &Tcur = is_x ? in.Tx : in.Tu;
+    const bool whole = first == 0 && count == s->batch;
+    if (!track && !whole)
+        return fail(TINYMPC_ERR_INVALID_INPUT, "%s: the first track call of a half must name the whole batch (first = 0, count = %d)", verb, s->batch);
+    if (track && !whole && T != Tcur)
+        return fail(TINYMPC_ERR_INVALID_INPUT, "%s: a call on a sub-range must keep the track length T = %d (got %d); a whole-batch call may change it",
+                    verb, Tcur, T);
+    const size_t per = (size_t)R * T;
+    if (s->batch == 1) {  // the host copy; the current window goes through the shared verb
+        if (count == 0) return TINYMPC_OK;
+        std::vector<double> h(per);
+        if (on_device) {
+            if ((rc = bind_device(s))) return rc;
+            if ((rc = download(s, h.data(), src, sizeof(double) * per))) return rc;
+        } else {
+            std::memcpy(h.data(), src, sizeof(double) * per);
+        }
+        (is_x ? in.hXt : in.hUt).swap(h);
+        Tcur = T;
+        track = true;
+        return forward_track_window(s, is_x);
+    }
+    if ((rc = bind_device(s))) return rc;
+    double *&store = is_x ? in.Xt : in.Ut;
+    size_t &cap = is_x ? in.xt_cap : in.ut_cap;
+    double *grown = nullptr;
+    if (!s->layout_m) {  // (layout M: no kernel carries per-instance references -- the next launch refuses, as for trajectories)
+        if ((rc = ensure_ref_steps(s)) || (rc = alloc_inst_rows(s, in.models))) return rc;
+        if (per * s->batch > cap && (rc = dalloc(s, &grown, per * s->batch))) return rc;
+    }
+    // the upload, into the new store where the call needed one; mode, store and T change only after it has succeeded
+    double *dst = grown ? grown : store;
+    bool on = true;  // (set_inst_batch: the mode counts as on -- nothing is filled from the shared reference, the whole batch has been named)
+    const InstArray a = {src, R, T, &dst, nullptr, false, nullptr};
+    if ((rc = set_inst_batch(s, verb, verb, "tracks", &a, 1, on, false, on_device, false, first, count, nullptr))) {
+        dfree(s, grown);
+        return rc;
+    }
+    if (grown) {  // (a whole-batch call: nothing of the old store is kept)
+        dfree(s, store);
+        store = grown;
+        cap = per * s->batch;
+    }
+    Tcur = T;
+    track = true;
+    mode = true;
+    *(is_x ? &in.x_const : &in.u_const) = false;  // (even T = 1: a track is a trajectory, layout A)
+    return TINYMPC_OK;
+}
+
+// tinympc_set_ref_step_batch (+ _device).
+int set_ref_steps(tinympc_solver *s, const int *steps, bool on_device, int first, int count) {
+    const char *verb = on_device ? "set_ref_step_batch_device" : "set_ref_step_batch";
+    int rc = check_handle(s);
+    if (rc) return rc;
+    if (!steps) return fail(TINYMPC_ERR_INVALID_INPUT, "%s: steps is NULL", verb);
+    if (first < 0 || count < 0 || first + count > s->batch)
+        return fail(TINYMPC_ERR_INVALID_INPUT, "%s: instance range [%d, %d) outside batch of %d", verb, first, first + count, s->batch);
+    InstState &in = s->inst;
+    if (count == 0) return TINYMPC_OK;
+    if (on_device) {
+        if (!on_handles_device(s, steps))
+            return fail(TINYMPC_ERR_INVALID_INPUT, "%s: the steps are not device memory of the handle's GPU %d", verb, s->device);
+        if ((rc = bind_device(s))) return rc;
+        if (!in.mflag && (rc = dalloc(s, &in.mflag, (size_t)1))) return rc;
+        int bad = 0;
+        HIP_TRY(hipMemsetAsync(in.mflag, 0, sizeof(int), s->stream));
+        HIP_TRY(launch_check_ref_steps(steps, count, 0, in.mflag, s->stream));
+        if ((rc = download(s, &bad, in.mflag, sizeof(int)))) return rc;
+        if (bad) return fail(TINYMPC_ERR_INVALID_INPUT, "%s: every step must be >= 0", verb);
+    } else {
+        for (int b = 0; b < count; ++b)
+            if (steps[b] < 0) return fail(TINYMPC_ERR_INVALID_INPUT, "%s: steps[%d] = %d. Expected a step >= 0.", verb, b, steps[b]);
+    }
+    if (s->batch == 1) {
+        int v = 0;
+        if (on_device) { if ((rc = download(s, &v, steps, sizeof(int)))) return rc; }
+        else v = steps[0];
+        in.hstep = v;
+        return forward_track_windows(s);
+    }
+    if (!on_device && (rc = bind_device(s))) return rc;
+    if ((rc = ensure_ref_steps(s))) return rc;
+    HIP_TRY(hipMemcpyAsync(in.steps + first, steps, sizeof(int) * count, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));  // (the caller keeps ownership of its buffer: copied when the call returns)
+    if (in.tracks()) in.mark(first, first + count);
+    return TINYMPC_OK;
+}
+
+// Every instance's step += delta (delta >= 0 here, or validated by the caller), on the handle's stream: no copy, no synchronisation. The
+// rows are rebuilt at the next launch (refresh_inst_tables).
+int advance_ref_steps(tinympc_solver *s, int delta) {
+    InstState &in = s->inst;
+    if (s->batch == 1) {
+        const long v = (long)in.hstep + delta;
+        in.hstep = v < 0 ? 0 : v > 2147483647L ? 2147483647 : (int)v;
+        return forward_track_windows(s);
+    }
+    int rc;
+    if ((rc = ensure_ref_steps(s))) return rc;
+    HIP_TRY(launch_advance_ref_steps(in.steps, s->batch, delta, s->stream));
+    if (in.tracks()) in.mark(0, s->batch);
+    return TINYMPC_OK;
+}
+
+}  // namespace
+
+static int advance_ref_steps_after_tick(tinympc_solver *s) { return advance_ref_steps(s, s->inst.auto_advance); }
+
+int tinympc_set_x_ref_track_batch(tinympc_solver *s, const double *Xtracks, int rows, int T, int first, int count) {
+    return set_ref_track(s, true, Xtracks, false, rows, T, first, count);
+}
+int tinympc_set_u_ref_track_batch(tinympc_solver *s, const double *Utracks, int rows, int T, int first, int count) {
+    return set_ref_track(s, false, Utracks, false, rows, T, first, count);
+}
+int tinympc_set_x_ref_track_batch_device(tinympc_solver *s, const double *d_Xtracks, int rows, int T, int first, int count) {
+    return set_ref_track(s, true, d_Xtracks, true, rows, T, first, count);
+}
+int tinympc_set_u_ref_track_batch_device(tinympc_solver *s, const double *d_Utracks, int rows, int T, int first, int count) {
+    return set_ref_track(s, false, d_Utracks, true, rows, T, first, count);
+}
+int tinympc_set_ref_step_batch(tinympc_solver *s, const int *steps, int first, int count) { return set_ref_steps(s, steps, false, first, count); }
+int tinympc_set_ref_step_batch_device(tinympc_solver *s, const int *d_steps, int first, int count) { return set_ref_steps(s, d_steps, true, first, count); }
+
+int tinympc_advance_ref_step_batch(tinympc_solver *s, int delta) {
+    int rc = check_handle(s);
+    if (rc) return rc;
+    InstState &in = s->inst;
+    if (s->batch == 1) {
+        if ((long)in.hstep + delta < 0)
+            return fail(TINYMPC_ERR_INVALID_INPUT, "advance_ref_step_batch: step %d + delta %d is negative", in.hstep, delta);
+        return advance_ref_steps(s, delta);
+    }
+    if ((rc = bind_device(s))) return rc;
+    if (delta < 0) {  // going back: validated on the device first (one flag read back; an advance by delta >= 0 reads nothing back)
+        if (!in.steps) return fail(TINYMPC_ERR_INVALID_INPUT, "advance_ref_step_batch: delta %d would take a step below 0", delta);
+        if (!in.mflag && (rc = dalloc(s, &in.mflag, (size_t)1))) return rc;
+        int bad = 0;
+        HIP_TRY(hipMemsetAsync(in.mflag, 0, sizeof(int), s->stream));
+        HIP_TRY(launch_check_ref_steps(in.steps, s->batch, delta, in.mflag, s->stream));
+        if ((rc = download(s, &bad, in.mflag, sizeof(int)))) return rc;
+        if (bad) return fail(TINYMPC_ERR_INVALID_INPUT, "advance_ref_step_batch: delta %d would take a step below 0", delta);
+    }
+    return advance_ref_steps(s, delta);
+}
+
+int tinympc_set_ref_auto_advance(tinympc_solver *s, int delta) {
+    int rc = check_handle(s);
+    if (rc) return rc;
+    // (the tick reads nothing back, so it cannot validate: only advances that need no validation)
+    if (delta < 0) return fail(TINYMPC_ERR_INVALID_INPUT, "set_ref_auto_advance: delta must be >= 0 (got %d)", delta);
+    if (delta > 0 && s->batch > 1) {  // (the step array now, not inside the first tick)
+        if ((rc = bind_device(s))) return rc;
+        if ((rc = ensure_ref_steps(s))) return rc;
+    }
+    s->inst.auto_advance = delta;
+    return TINYMPC_OK;
+}
+
+int tinympc_get_ref_step_batch(tinympc_solver *s, int *steps_out, int first, int count) {
+    int rc = check_handle(s);
+    if (rc) return rc;
+    if (!steps_out || first < 0 || count < 0 || first + count > s->batch)
+        return fail(TINYMPC_ERR_INVALID_INPUT, "get_ref_step_batch: range [%d, %d) outside the batch of %d", first, first + count, s->batch);
+    if (count == 0) return TINYMPC_OK;
+    if (s->batch == 1) { steps_out[0] = s->inst.hstep; return TINYMPC_OK; }
+    if (!s->inst.steps) { std::memset(steps_out, 0, sizeof(int) * count); return TINYMPC_OK; }  // (steps start at 0)
+    if ((rc = bind_device(s))) return rc;
+    return download(s, steps_out, s->inst.steps + first, sizeof(int) * count);
 }
 
 namespace {
@@ -1282,14 +1550,6 @@ int rebuild_inst_models(tinympc_solver *s, int first, int count) {
     if ((rc = precompute_inst_models(s, first, count))) return rc;
     in.mark(first, first + count);
     return TINYMPC_OK;
-}
-
-// `p` is device memory of the handle's own GPU (a host pointer or another GPU's memory is not)
-bool on_handles_device(const tinympc_solver *s, const void *p) {
-    hipPointerAttribute_t attr{};
-    const hipError_t e = hipPointerGetAttributes(&attr, p);
-    (void)hipGetLastError();
-    return e == hipSuccess && attr.type == hipMemoryTypeDevice && attr.device == s->device;
 }
 
 // tinympc_set_model_batch (+ _device). The mode enters at the first call: every instance then holds the shared model, cache and

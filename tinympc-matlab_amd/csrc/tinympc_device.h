@@ -291,6 +291,11 @@ struct InstTableParams {
     int en_state_bound, en_input_bound;
     int first, count;                 // instances whose rows are rebuilt
     const double *Xi, *Ui;            // per-instance references, or NULL: that half is the shared one
+    // Reference tracks (tinympc_set_x_ref_track_batch / _u_ref_track_batch): Tx / Tu > 0 makes Xi / Ui the half's track store,
+    // [batch][T][rows], and knot kn of instance b reads its column min(steps[b] + kn, T - 1) -- the last knot is held beyond the end of
+    // the track. 0: Xi / Ui hold the window itself (nx x N / nu x (N-1) per instance) and steps is not read.
+    int Tx, Tu;
+    const int *steps;                 // [batch], each >= 0
     const double *Xref, *Uref, *Pinf;  // shared references, Pinf for pNref
     const double *ops;                // for dg[]
     // per-instance models: instance b's Pinf at Pinf + b * pinf_stride, its operator block at ops + b * ops_stride (0: shared)
@@ -466,6 +471,8 @@ hipError_t launch_fill_inst_models(const InstModelFillParams &p, hipStream_t str
 hipError_t launch_store_inst_diag(const InstDiagParams &p, hipStream_t stream);
 // *flag <- 1 if any of v[0, n) is not a finite number > 0 (per-instance rho from device memory: validated where it lies)
 hipError_t launch_check_positive(const double *v, int n, int *flag, hipStream_t stream);
+hipError_t launch_check_ref_steps(const int *steps, int n, int delta, int *flag, hipStream_t stream);  // *flag = 1 if some steps[i] + delta < 0
+hipError_t launch_advance_ref_steps(int *steps, int n, int delta, hipStream_t stream);                 // steps[i] += delta, saturating in [0, INT_MAX]
 // Layout A: one wavefront per workgroup, all ADMM state in LDS (lowest latency, 2 waves per CU). One kernel body, three
 // variants: the box path (k_admm_solve), plus the cone / linear slack families (k_admm_solve_fam: extra duals and the extra
 // linear-cost term in HBM), plus adaptive rho (k_admm_solve_adapt: per-instance rho, Taylor-updated operators; needs

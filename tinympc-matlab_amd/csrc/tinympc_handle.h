@@ -87,6 +87,21 @@ struct InstState {
     double *ops = nullptr;                   // [batch][ops_doubles(W, KT)]: SolveParams::ops of the InstModels variant
     double *mscratch = nullptr;              // working sets of k_precompute's batched form where they do not fit LDS
     double *mstage = nullptr;                // device staging of the cost diagonals (host input)
+    // Reference tracks (tinympc_set_x_ref_track_batch / _u_ref_track_batch): a half in track mode is a half with per-instance
+    // trajectories (x / u above is on, x_const / u_const off) whose rows are built from a store LONGER than the horizon -- Xt / Ut,
+    // [batch][T][rows], T knots per instance -- and the instance's step: knot kn of instance b is column min(steps[b] + kn, T - 1)
+    // (k_build_inst_tables). One step per instance serves both halves; the step array stays when a half leaves the mode, and the
+    // store of a half that left is kept for the next track (xt_cap / ut_cap doubles). Single-instance handles keep the track on the
+    // host (hXt / hUt, hstep) and forward the current window through the shared reference verbs.
+    bool x_track = false, u_track = false;
+    int Tx = 0, Tu = 0;
+    double *Xt = nullptr, *Ut = nullptr;
+    size_t xt_cap = 0, ut_cap = 0;
+    int *steps = nullptr;
+    int auto_advance = 0;  // tinympc_mpc_step_batch adds this to every step after its solve (0: off)
+    std::vector<double> hXt, hUt;
+    int hstep = 0;
+    bool tracks() const { return x_track || u_track; }
     int dirty_lo = 0, dirty_hi = 0;
     bool refs() const { return x || u; }
     const double *lr_rows() const { return lr + (size_t)tinympc::INST_LR_PAD * 64; }  // SolveParams::iref_lr on layout A

@@ -346,6 +346,9 @@ int refresh_inst_tables(tinympc_solver *s) {
     p.en_state_bound = s->st.en_state_bound; p.en_input_bound = s->st.en_input_bound;
     p.first = in.dirty_lo; p.count = in.dirty_hi - in.dirty_lo;
     p.Xi = in.x ? in.Xi : nullptr; p.Ui = in.u ? in.Ui : nullptr;
+    if (in.x && in.x_track) { p.Xi = in.Xt; p.Tx = in.Tx; }  // (a half in track mode: the window is cut out of the track here)
+    if (in.u && in.u_track) { p.Ui = in.Ut; p.Tu = in.Tu; }
+    p.steps = in.steps;
     p.Xref = s->dXref; p.Uref = s->dUref; p.Pinf = s->dPinf; p.ops = s->dops;
     if (in.models) {  // the rows of instance b from its own cost diagonals and Pinf
         p.Pinf = in.cP; p.pinf_stride = (size_t)s->nx * s->nx;

@@ -3,7 +3,8 @@
 //   k_precompute        P1  tiny_precompute_and_set_cache         (reference tiny_api.cpp:124-190)
 //   k_build_operators       fuses the cache into the two 1-step sweep operators used by the solve
 //   k_build_tables          per-knot clamp bounds / linear-cost reference terms
-//   k_build_inst_tables     the same rows per instance (per-instance references / bounds of a batched handle)
+//   k_build_inst_tables     the same rows per instance (per-instance references / bounds of a batched handle; reference tracks)
+//   k_advance_ref_steps     reference tracks: every instance's step moves on the device (k_check_ref_steps validates device input)
 //   k_build_adapt           adaptive rho: the sensitivity rows of the sweep operators and [A'; B']
 //
 // The solve kernel itself (M1: F1, S1, D1, L1, R1, C1, B1) is in tinympc_solve.hip.
@@ -624,7 +625,8 @@ hipError_t launch_store_inst_refs(const InstRefStoreParams &p, hipStream_t strea
 // of instance g*(64/W) + j. The expressions and the order of the pNref sum are k_build_tables' (an instance whose references and bounds
 // equal the shared ones gets bit-identical values; a disabled bound family is -inf / +inf for every instance); padding rows and lanes of
 // the linref rows are zero. Knot 0's linref and clamp rows also go to lrg / bndg (layout D's goal form); layout A's clamp rows only
-// where bnd is set.
+// where bnd is set. A half in track mode (Tx / Tu > 0) reads knot kn from column min(step + kn, T - 1) of the instance's track instead
+// of column kn of its window: the same values through the same expressions, so a track gives the bits of its window sent by hand.
 __global__ void __launch_bounds__(256) k_build_inst_tables(const InstTableParams p) {
     const int nx = p.nx, nu = p.nu, N = p.N, W = p.W, nxu = nx + nu, TR = N + 2;
     const size_t X = (size_t)nx * N, U = (size_t)nu * (N - 1);
@@ -638,13 +640,17 @@ __global__ void __launch_bounds__(256) k_build_inst_tables(const InstTableParams
         const int e = (int)(idx % per), row = e / W, r = e % W;
         const long grp = inst / (64 / W);
         const int lane = (int)(inst % (64 / W)) * W + r;
-        const double *Xr = p.Xi ? p.Xi + inst * X : p.Xref;
-        const double *Ur = p.Ui ? p.Ui + inst * U : p.Uref;
+        // (reference tracks: the half's block is the instance's whole track, and knot kn is its column min(step + kn, T - 1))
+        const long step = (p.Tx | p.Tu) ? (long)p.steps[inst] : 0;
+        const double *Xr = p.Xi ? p.Xi + inst * (p.Tx ? (size_t)nx * p.Tx : X) : p.Xref;
+        const double *Ur = p.Ui ? p.Ui + inst * (p.Tu ? (size_t)nu * p.Tu : U) : p.Uref;
+        const auto xcol = [&](int kn) -> size_t { return !p.Tx ? (size_t)kn : (size_t)(step + kn < p.Tx ? step + kn : p.Tx - 1); };
+        const auto ucol = [&](int kn) -> size_t { return !p.Tu ? (size_t)kn : (size_t)(step + kn < p.Tu ? step + kn : p.Tu - 1); };
         const double *dg = dg0 + inst * p.ops_stride, *Pinf = p.Pinf + inst * p.pinf_stride;  // (per-instance models: the instance's own)
         if (row == TR) {
             double acc = 0.0;
             if (r < nx) {
-                for (int k = 0; k < nx; ++k) acc += Xr[k + (size_t)(N - 1) * nx] * Pinf[k + (size_t)r * nx];
+                for (int k = 0; k < nx; ++k) acc += Xr[k + xcol(N - 1) * nx] * Pinf[k + (size_t)r * nx];
                 acc = -acc;  // admm.cpp:81
             }
             p.pn[(size_t)grp * 64 + lane] = acc;
@@ -659,14 +665,14 @@ __global__ void __launch_bounds__(256) k_build_inst_tables(const InstTableParams
                     l = p.x_min[bx + r + (size_t)kn * nx];
                     h = p.x_max[bx + r + (size_t)kn * nx];
                 }
-                ref = -(Xr[r + (size_t)kn * nx] * dg[r]);  // admm.cpp:79
+                ref = -(Xr[r + xcol(kn) * nx] * dg[r]);  // admm.cpp:79
             } else if (r < nxu && kn < N - 1) {
                 const int j = r - nx;
                 if (p.en_input_bound) {
                     l = p.u_min[bu + j + (size_t)kn * nu];
                     h = p.u_max[bu + j + (size_t)kn * nu];
                 }
-                ref = -(Ur[j + (size_t)kn * nu] * dg[r]);  // admm.cpp:77
+                ref = -(Ur[j + ucol(kn) * nu] * dg[r]);  // admm.cpp:77
             }
             const size_t o = ((size_t)grp * TR + row) * 64 + lane;
             p.lr[o] = ref;
@@ -731,6 +737,32 @@ hipError_t launch_check_positive(const double *v, int n, int *flag, hipStream_t 
     if (n <= 0) return hipSuccess;
     const int blocks = (n + 255) / 256;
     hipLaunchKernelGGL(k_check_positive, dim3(blocks < 1024 ? blocks : 1024), dim3(256), 0, stream, v, n, flag);
+    return hipGetLastError();
+}
+
+// Reference tracks: every instance's step (its position in its track). The device-side validation of tinympc_set_ref_step_batch_device
+// and of an advance by a negative delta, and the advance itself: a saturating add that cannot wrap (a step beyond the end of the
+// track holds the last knot, so INT_MAX is as good as any larger number).
+__global__ void __launch_bounds__(256) k_check_ref_steps(const int *steps, int n, int delta, int *flag) {
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256)
+        if ((long)steps[i] + delta < 0) *flag = 1;
+}
+hipError_t launch_check_ref_steps(const int *steps, int n, int delta, int *flag, hipStream_t stream) {
+    if (n <= 0) return hipSuccess;
+    const int blocks = (n + 255) / 256;
+    hipLaunchKernelGGL(k_check_ref_steps, dim3(blocks < 1024 ? blocks : 1024), dim3(256), 0, stream, steps, n, delta, flag);
+    return hipGetLastError();
+}
+__global__ void __launch_bounds__(256) k_advance_ref_steps(int *steps, int n, int delta) {
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+        const long v = (long)steps[i] + delta;
+        steps[i] = v < 0 ? 0 : v > 2147483647L ? 2147483647 : (int)v;
+    }
+}
+hipError_t launch_advance_ref_steps(int *steps, int n, int delta, hipStream_t stream) {
+    if (n <= 0) return hipSuccess;
+    const int blocks = (n + 255) / 256;
+    hipLaunchKernelGGL(k_advance_ref_steps, dim3(blocks < 1024 ? blocks : 1024), dim3(256), 0, stream, steps, n, delta);
     return hipGetLastError();
 }
 

@@ -532,11 +532,20 @@ int tinympc_prepare(tinympc_solver *s) {
     return TINYMPC_OK;
 }
 
+static int jit_info_text(tinympc_solver *s, char *buf, int len);
+
 int tinympc_get_jit_info(tinympc_solver *s, char *buf, int len) {
     int rc = check_handle(s);
     if (rc) return rc;
     if (!buf || len < 1) return fail(TINYMPC_ERR_INVALID_INPUT, "get_jit_info: buffer required");
     buf[0] = '\0';
+    if ((rc = jit_info_text(s, buf, len))) return rc;
+    if (s->inst.tracks()) strncat(buf, " reference-track", (size_t)len - strlen(buf) - 1);  // (a half is in track mode)
+    return TINYMPC_OK;
+}
+
+static int jit_info_text(tinympc_solver *s, char *buf, int len) {
+    int rc;
     const LaunchPlan pl = current_plan(s);
     const bool ct = s->tables_const();
     if (pl.inst_refs) {

@@ -328,6 +328,77 @@ class TinyMPC:
         self._set_batch("references", (u_refs,), (self.nu,), (self.N - 1,), self._L.tinympc_set_u_ref_batch,
                         self._L.tinympc_set_u_ref_batch_device, first, self.nu)
 
+    # reference tracks: upload once, step per tick (include/tinympc_hip.h)
+    def set_x_ref_track_batch(self, x_tracks, first: int = 0):
+        """Per-instance state reference TRACKS for instances first, first+1, ...: a numpy array of shape (nx, T, count) -- T >= 1 knots
+        per instance, independent of N; (nx, T) on a single-instance solver -- or a CUDA torch tensor with the same memory layout,
+        (count, T, nx) contiguous float64. Kept on the device: instance b at step k tracks columns min(k+i, T-1), i = 0..N-1, of its
+        track, so a closed-loop tick uploads nothing but x0 (set_ref_step_batch, advance_ref_step, set_ref_auto_advance). The first
+        call must name the whole batch; set_x_ref() / a whole-batch set_x_ref_batch() leave the mode."""
+        self._check_setup()
+        self._set_track(x_tracks, self.nx, self._L.tinympc_set_x_ref_track_batch, self._L.tinympc_set_x_ref_track_batch_device, first)
+
+    def set_u_ref_track_batch(self, u_tracks, first: int = 0):
+        """Per-instance input reference tracks: (nu, T, count); see set_x_ref_track_batch (window columns min(k+i, T-1), i = 0..N-2)."""
+        self._check_setup()
+        self._set_track(u_tracks, self.nu, self._L.tinympc_set_u_ref_track_batch, self._L.tinympc_set_u_ref_track_batch_device, first)
+
+    def _set_track(self, tracks, rows, f_host, f_device, first):
+        if hasattr(tracks, "data_ptr") and getattr(tracks, "is_cuda", False):
+            import torch
+            ok = tracks.dtype == torch.float64 and tracks.is_contiguous() and tracks.shape[-1] == rows and \
+                (tracks.dim() == 3 or (tracks.dim() == 2 and self.batch == 1)) and tracks.shape[-2] >= 1
+            if not ok:
+                raise TinyMPCError(_lib.ERR_INVALID_INPUT, "tracks on the device must be contiguous float64 tensors of shape (count, T, %d) "
+                                   "with T >= 1, got %s %s" % (rows, tracks.dtype, tuple(tracks.shape)))
+            count = int(tracks.shape[0]) if tracks.dim() == 3 else 1
+            torch.cuda.current_stream(tracks.device).synchronize()  # (the set_x0_batch contract)
+            _lib.check(f_device(self._h, C.c_void_p(tracks.data_ptr()), rows, int(tracks.shape[-2]), int(first), count))
+            return
+        a = np.asarray(tracks, dtype=np.float64)
+        if a.ndim == 2 and self.batch == 1:
+            a = a.reshape(a.shape + (1,))
+        if a.ndim != 3 or a.shape[0] != rows or a.shape[1] < 1:
+            raise TinyMPCError(_lib.ERR_INVALID_INPUT, "tracks must be %d x T x count with T >= 1%s, got %s"
+                               % (rows, " (or %d x T)" % rows if self.batch == 1 else "", a.shape))
+        a = _f(a)
+        _lib.check(f_host(self._h, _p(a), rows, int(a.shape[1]), int(first), int(a.shape[2])))
+
+    def set_ref_step_batch(self, steps, first: int = 0):
+        """The steps (positions in their tracks) of instances first, first+1, ...: a vector of `count` integers >= 0, or a contiguous
+        int32 CUDA tensor of `count` elements on the handle's GPU (validated on the device)."""
+        self._check_setup()
+        if hasattr(steps, "data_ptr") and getattr(steps, "is_cuda", False):
+            import torch
+            if steps.dtype != torch.int32 or not steps.is_contiguous() or steps.dim() != 1:
+                raise TinyMPCError(_lib.ERR_INVALID_INPUT, "steps on the device must be a contiguous int32 tensor of shape (count,), got %s %s"
+                                   % (steps.dtype, tuple(steps.shape)))
+            torch.cuda.current_stream(steps.device).synchronize()  # (the set_x0_batch contract)
+            _lib.check(self._L.tinympc_set_ref_step_batch_device(self._h, C.c_void_p(steps.data_ptr()), int(first), int(steps.numel())))
+            return
+        raw = np.atleast_1d(np.asarray(steps))
+        if raw.ndim != 1 or not np.issubdtype(raw.dtype, np.integer) or (raw.size and (raw.min() < -2**31 or raw.max() >= 2**31)):
+            raise TinyMPCError(_lib.ERR_INVALID_INPUT, "steps must be a vector of count 32-bit integers, got %s %s" % (raw.dtype, raw.shape))
+        a = np.ascontiguousarray(raw, dtype=np.int32)
+        _lib.check(self._L.tinympc_set_ref_step_batch(self._h, a.ctypes.data_as(c_int_p), int(first), int(a.size)))
+
+    def advance_ref_step(self, delta: int = 1):
+        """Every instance's step += delta, on the device (no copy, no synchronisation for delta >= 0)."""
+        self._check_setup()
+        _lib.check(self._L.tinympc_advance_ref_step_batch(self._h, int(delta)))
+
+    def set_ref_auto_advance(self, delta: int = 1):
+        """mpc_step() adds delta >= 0 to every instance's step after its solve; 0 switches it off."""
+        self._check_setup()
+        _lib.check(self._L.tinympc_set_ref_auto_advance(self._h, int(delta)))
+
+    def get_ref_step_batch(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        self._check_setup()
+        count = self.batch - first if count is None else count
+        out = np.zeros(max(count, 0), dtype=np.int32)
+        _lib.check(self._L.tinympc_get_ref_step_batch(self._h, out.ctypes.data_as(c_int_p), int(first), int(count)))
+        return out
+
     def set_bound_constraints_batch(self, x_min, x_max, u_min, u_max, first: int = 0):
         """Per-instance box bounds for instances first, first+1, ...: numpy arrays of shape (nx, count) / (nu, count) (one box per
         instance, held over the horizon) or (nx, N, count) / (nu, N-1, count) (bounds per knot), or CUDA torch tensors with the same
