@@ -296,6 +296,36 @@ int tinympc_set_bound_constraints_batch(tinympc_solver *s, const double *x_min, 
 int tinympc_set_bound_constraints_batch_device(tinympc_solver *s, const double *d_x_min, const double *d_x_max,
                                                const double *d_u_min, const double *d_u_max, int cols, int first, int count);
 
+/* Per-instance linear (half-space) constraints for instances [first, first+count) of a batched handle: a_k' x <= b_k, a_k' u <= b_k.
+ * Alin_x: nlx x nx x count, column-major, instance b's block at b*nlx*nx; blin_x: nlx x count; Alin_u: nlu x nu x count, blin_u:
+ * nlu x count likewise. Instance first+b then solves exactly what a single-instance handle would solve after
+ * tinympc_set_linear_constraints(Alin_x_b, blin_x_b, nlx, Alin_u_b, blin_u_b, nlu) -- an instance whose rows are the shared ones, bit
+ * for bit what the shared rows give on layout A. The row COUNTS (nlx, nlu) belong to the batch, the values to the instance: b = +inf
+ * switches one row off for one instance. The first call turns per-instance mode on. It may name a sub-range if the handle holds shared
+ * rows of the same (nlx, nlu) at that moment -- the other instances keep those rows --; otherwise it must name the whole batch (first = 0,
+ * count = batch). A later call on a sub-range must use the mode's counts; a whole-batch call may change them. At most 32 rows per side
+ * (TINYMPC_ERR_UNSUPPORTED beyond). Like the shared verb the call enables the linear family of every non-empty side (a later
+ * tinympc_update_settings can switch either side off again, for every instance) and keeps the ADMM state, the family's duals
+ * included: replacing the rows between two warm-started ticks is the intended use (obstacle half-spaces re-linearised every tick).
+ * tinympc_set_linear_constraints returns every instance to shared rows. reset_workspace, update_settings, the reference, track and
+ * bound verbs (shared and per instance), set_cone_constraints, the solve verbs and mpc_step_batch keep mode and rows.
+ * The mode runs on layout A (tinympc_get_layout 'A', " per-instance-linear" in tinympc_get_jit_info; tinympc_prepare has nothing to
+ * specialise), with shared cones, fdyn, per-instance references (goals, trajectories, tracks) and per-instance bounds (box or per knot)
+ * in any combination: its kernel always reads the reference and clamp rows per instance. With per-instance models or rho, adaptive
+ * rho, nx+nu > 64 or more cones / rounds than the generic kernels hold a solve returns TINYMPC_ERR_UNSUPPORTED (never a solve with
+ * shared rows), and so does tinympc_session_begin. Outside the mode, per-instance references or bounds together with a family stay
+ * refused. Invalid arguments -- a row of A that is all zero or not finite, a b that is NaN or -inf, a NULL pointer for a non-empty side,
+ * negative counts or no row at all, a range that is empty or beyond the batch, a sub-range with other counts, host memory or another
+ * GPU's memory handed to the _device form -- return TINYMPC_ERR_INVALID_INPUT and leave mode, rows, enable flags and ADMM state as
+ * they were: everything is validated (on the device, one flag read back) before anything is written. Single-instance handles: the same
+ * as tinympc_set_linear_constraints, with count 1. The input has been copied when the call returns. */
+int tinympc_set_linear_constraints_batch(tinympc_solver *s, const double *Alin_x, const double *blin_x, int nlx,
+                                         const double *Alin_u, const double *blin_u, int nlu, int first, int count);
+/* Same, from device memory on the handle's GPU (host and device form give the same bits: one builder); same contract as
+ * tinympc_set_x0_batch_device. */
+int tinympc_set_linear_constraints_batch_device(tinympc_solver *s, const double *d_Alin_x, const double *d_blin_x, int nlx,
+                                                const double *d_Alin_u, const double *d_blin_u, int nlu, int first, int count);
+
 /* Per-instance models for instances [first, first+count) of a batched handle.
  * A: nx*nx*count, B: nx*nu*count, fdyn: nx*count (NULL = zeros), Q: nx*nx*count, R: nu*nu*count; column-major, instance b's block
  * at b*(block size); of Q and R only the diagonals are used, as in tinympc_setup. N and the settings stay the handle's; rho is the

@@ -32,6 +32,18 @@ def job_shard(rank: int, world: int, batch_per_gpu: int = 0, global_batch: int =
     return total, first, count, "strong" if strong else "weak"
 
 
+def shard_instances(arrays, rank: int, world: int) -> tuple[int, list]:
+    """A rank's slice of per-instance arrays whose LAST axis is the instance (the layout of the per-instance verbs: set_x_ref_batch,
+    set_bound_constraints_batch, set_linear_constraints_batch, ...): returns (first, [slices]) for `rank`'s contiguous shard of
+    shard_range(). None entries (an empty side) stay None. The rank hands the slices to its own handle with first = 0."""
+    arrays = list(arrays)
+    totals = {np.asarray(a).shape[-1] for a in arrays if a is not None}
+    if len(totals) != 1:
+        raise ValueError("per-instance arrays must share their instance count (last axis)")
+    first, count = shard_range(totals.pop(), rank, world)
+    return first, [None if a is None else np.asarray(a)[..., first:first + count] for a in arrays]
+
+
 def local_summary(iters: np.ndarray, status: np.ndarray, residuals: np.ndarray) -> dict:
     """Per-shard summary: instances, converged, sum of iterations, max primal / dual residual."""
     res = np.asarray(residuals, dtype=np.float64).reshape(4, -1)

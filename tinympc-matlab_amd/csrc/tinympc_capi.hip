@@ -791,6 +791,10 @@ int tinympc_set_linear_constraints(tinympc_solver *s, const double *Alin_x, cons
         if (zero_row(Alin_x, nlx, s->nx, k)) return fail(TINYMPC_ERR_INVALID_INPUT, "Alin_x row %d is all zero", k);
     for (int k = 0; k < nlu; ++k)
         if (zero_row(Alin_u, nlu, s->nu, k)) return fail(TINYMPC_ERR_INVALID_INPUT, "Alin_u row %d is all zero", k);
+    if (s->inst.lin) {  // (per-instance linear rows: every instance is on the shared rows again)
+        s->inst.lin = false;
+        if (s->inst_tables()) s->inst.mark(0, s->batch);
+    }
     s->n_lin_x = nlx;
     s->n_lin_u = nlu;
     s->Alin_x.assign(Alin_x, Alin_x + (size_t)nlx * s->nx);
@@ -1639,7 +1643,150 @@ int set_rho_batch(tinympc_solver *s, const double *rho, bool on_device, int firs
     return TINYMPC_OK;
 }
 
+// tinympc_set_linear_constraints_batch (+ _device): the linear rows of instances [first, first+count). Host input is staged on the device;
+// from there both forms are ONE path -- k_check_inst_lin validates the arrays where they lie (one flag read back), then, and only
+// then, k_build_inst_lin writes the instances' rows into the store the kernel reads. Nothing else is kept.
+int set_lin_batch(tinympc_solver *s, const double *Ax, const double *bx, int nlx, const double *Au, const double *bu, int nlu, bool on_device,
+                  int first, int count) {
+    const char *verb = on_device ? "set_linear_constraints_batch_device" : "set_linear_constraints_batch";
+    int rc = check_handle(s);
+    if (rc) return rc;
+    if (nlx < 0 || nlu < 0) return fail(TINYMPC_ERR_INVALID_INPUT, "%s: negative constraint count", verb);
+    if ((nlx > 0 && (!Ax || !bx)) || (nlu > 0 && (!Au || !bu)))
+        return fail(TINYMPC_ERR_INVALID_INPUT, "%s: NULL array for a non-empty side", verb);
+    if (nlx + nlu == 0)
+        return fail(TINYMPC_ERR_INVALID_INPUT, "%s: no rows on either side (tinympc_set_linear_constraints with no rows clears the family)", verb);
+    if (first < 0 || count < 1 || first + count > s->batch)
+        return fail(TINYMPC_ERR_INVALID_INPUT, "%s: instance range [%d, %d) is empty or outside batch of %d", verb, first, first + count, s->batch);
+    if (nlx > MAX_LIN_ROWS || nlu > MAX_LIN_ROWS)
+        return fail(TINYMPC_ERR_UNSUPPORTED, "%s: at most %d rows per side (got %d state, %d input): per-instance rows run on the generic kernel only",
+                    verb, MAX_LIN_ROWS, nlx, nlu);
+    const size_t nx = s->nx, nu = s->nu, ax = (size_t)nlx * nx, au = (size_t)nlu * nu, n = (size_t)count;
+    if (on_device && ((nlx > 0 && (!on_handles_device(s, Ax) || !on_handles_device(s, bx))) || (nlu > 0 && (!on_handles_device(s, Au) || !on_handles_device(s, bu)))))
+        return fail(TINYMPC_ERR_INVALID_INPUT, "%s: the rows are not device memory of the handle's GPU %d", verb, s->device);
+    InstState &in = s->inst;
+    if (s->batch == 1) {  // the shared verb, after this verb's own checks of the values
+        std::vector<double> h(ax + nlx + au + nlu);
+        double *hAx = h.data(), *hbx = hAx + ax, *hAu = hbx + nlx, *hbu = hAu + au;
+        const double *src[4] = {Ax, bx, Au, bu};
+        double *dst[4] = {hAx, hbx, hAu, hbu};
+        const size_t len[4] = {ax, (size_t)nlx, au, (size_t)nlu};
+        if (on_device && (rc = bind_device(s))) return rc;
+        for (int i = 0; i < 4; ++i) {
+            if (!len[i]) continue;
+            if (on_device) { if ((rc = download(s, dst[i], src[i], sizeof(double) * len[i]))) return rc; }
+            else std::memcpy(dst[i], src[i], sizeof(double) * len[i]);
+        }
+        for (size_t i = 0; i < ax + nlx + au + nlu; ++i) {
+            const bool is_b = (i >= ax && i < ax + nlx) || i >= ax + nlx + au;
+            if (is_b ? !(h[i] >= -1.79769313486231570815e308) : !std::isfinite(h[i]))
+                return fail(TINYMPC_ERR_INVALID_INPUT, "%s: a row of A must be finite and not all zero, b a number or +inf", verb);
+        }
+        return tinympc_set_linear_constraints(s, hAx, hbx, nlx, hAu, hbu, nlu);
+    }
+    // the counts belong to the batch: a sub-range keeps them -- the mode's, or those of the shared rows the other instances stay on
+    const bool whole = first == 0 && count == s->batch;
+    const bool same = in.lin ? (nlx == in.lin_nlx && nlu == in.lin_nlu)
+                             : (nlx == s->n_lin_x && nlu == s->n_lin_u && s->Alin_x.size() == ax && s->Alin_u.size() == au);
+    if (!whole && !same)
+        return fail(TINYMPC_ERR_INVALID_INPUT, "%s: %d state and %d input rows for instances [%d, %d) of %d, but %s %d and %d: name the whole batch "
+                    "(first = 0, count = %d) to %s", verb, nlx, nlu, first, first + count, s->batch,
+                    in.lin ? "the mode's counts are" : "the handle's shared rows are", in.lin ? in.lin_nlx : s->n_lin_x, in.lin ? in.lin_nlu : s->n_lin_u,
+                    s->batch, in.lin ? "change the counts" : "begin the mode with counts of its own");
+    if ((rc = bind_device(s))) return rc;
+    InstLinParams q{};
+    q.nx = s->nx; q.nu = s->nu; q.W = s->W; q.nlx = nlx; q.nlu = nlu; q.nl = nlx > nlu ? nlx : nlu;
+    q.batch = s->batch; q.first = first; q.count = count;
+    q.ax_stride = ax; q.bx_stride = (size_t)nlx; q.au_stride = au; q.bu_stride = (size_t)nlu;
+    const size_t per = ax + nlx + au + nlu;
+    double *old_stage = nullptr, *old_rows = nullptr;
+    if (on_device) {
+        q.Ax = Ax; q.bx = bx; q.Au = Au; q.bu = bu;
+    } else {
+        if (per * n > in.lstage_cap) {
+            old_stage = in.lstage;
+            if ((rc = dalloc(s, &in.lstage, per * n))) return rc;
+            in.lstage_cap = per * n;
+        }
+        double *dAx = in.lstage, *dbx = dAx + ax * n, *dAu = dbx + nlx * n, *dbu = dAu + au * n;
+        if (nlx > 0) {
+            HIP_TRY(hipMemcpyAsync(dAx, Ax, sizeof(double) * ax * n, hipMemcpyHostToDevice, s->stream));
+            HIP_TRY(hipMemcpyAsync(dbx, bx, sizeof(double) * nlx * n, hipMemcpyHostToDevice, s->stream));
+        }
+        if (nlu > 0) {
+            HIP_TRY(hipMemcpyAsync(dAu, Au, sizeof(double) * au * n, hipMemcpyHostToDevice, s->stream));
+            HIP_TRY(hipMemcpyAsync(dbu, bu, sizeof(double) * nlu * n, hipMemcpyHostToDevice, s->stream));
+        }
+        q.Ax = dAx; q.bx = dbx; q.Au = dAu; q.bu = dbu;
+    }
+    if (!in.mflag && (rc = dalloc(s, &in.mflag, (size_t)1))) return rc;
+    int bad = 0;
+    HIP_TRY(hipMemsetAsync(in.mflag, 0, sizeof(int), s->stream));
+    HIP_TRY(launch_check_inst_lin(q, in.mflag, s->stream));
+    if ((rc = download(s, &bad, in.mflag, sizeof(int)))) return rc;  // (host input has been copied when this returns)
+    if (old_stage) dfree(s, old_stage);
+    if (bad)
+        return fail(TINYMPC_ERR_INVALID_INPUT, "%s: a row of A is all zero or not finite, or a b is NaN or -inf (b = +inf switches a row off)", verb);
+    // ---- valid: from here on the call writes
+    if (!s->layout_m) {  // (large systems: no kernel carries the mode -- the next solve refuses until the shared verb clears it)
+        if ((rc = alloc_inst_rows(s, true))) return rc;
+        const size_t need = inst_lin_doubles(s->groups, q.nl);
+        if (need > in.lrows_cap) {
+            old_rows = in.lrows;
+            if ((rc = dalloc(s, &in.lrows, need))) return rc;
+            in.lrows_cap = need;
+        }
+        q.dst = in.lrows;
+        if (!in.lin || q.nl != in.lin_nl || old_rows) {  // the store begins (or changes its row count): every lane absent, padding included ...
+            InstLinParams z = q;
+            z.nlx = z.nlu = 0; z.first = 0; z.count = s->groups * s->IPW;
+            z.Ax = z.bx = z.Au = z.bu = nullptr;
+            HIP_TRY(launch_build_inst_lin(z, s->stream));
+            if (!whole) {  // ... and the instances this call does not name on the shared rows of this moment (same counts: checked above)
+                double *sh = nullptr;
+                if ((rc = dalloc(s, &sh, per))) return rc;
+                std::vector<double> h;
+                h.insert(h.end(), s->Alin_x.begin(), s->Alin_x.end()); h.insert(h.end(), s->blin_x.begin(), s->blin_x.end());
+                h.insert(h.end(), s->Alin_u.begin(), s->Alin_u.end()); h.insert(h.end(), s->blin_u.begin(), s->blin_u.end());
+                HIP_TRY(hipMemcpyAsync(sh, h.data(), sizeof(double) * per, hipMemcpyHostToDevice, s->stream));
+                InstLinParams w = q;
+                w.first = 0; w.count = s->batch;
+                w.Ax = sh; w.bx = sh + ax; w.Au = w.bx + nlx; w.bu = w.Au + au;
+                w.ax_stride = w.bx_stride = w.au_stride = w.bu_stride = 0;
+                HIP_TRY(launch_build_inst_lin(w, s->stream));
+                HIP_TRY(hipStreamSynchronize(s->stream));  // (h and sh end here)
+                dfree(s, sh);
+            }
+        }
+        HIP_TRY(launch_build_inst_lin(q, s->stream));
+    }
+    if (!in.lin) in.mark(0, s->batch);  // (the reference and clamp rows of every instance: this mode's kernel always reads them per instance)
+    in.lin = true;
+    in.lin_nlx = nlx; in.lin_nlu = nlu; in.lin_nl = q.nl;
+    if (nlx != s->n_lin_x || nlu != s->n_lin_u) {  // (the shared rows are not read while the mode is on; they keep the handle's counts consistent)
+        s->n_lin_x = nlx; s->n_lin_u = nlu;
+        s->Alin_x.assign(ax, 0.0); s->blin_x.assign(nlx, std::numeric_limits<double>::infinity());
+        s->Alin_u.assign(au, 0.0); s->blin_u.assign(nlu, std::numeric_limits<double>::infinity());
+    }
+    if (nlx > 0) s->st.en_state_linear = 1;  // as the shared verb
+    if (nlu > 0) s->st.en_input_linear = 1;
+    s->fam_dirty = true;
+    // the caller keeps ownership of its buffers: everything has been read when the call returns (the tinympc_set_x0_batch_device rule)
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    if (old_rows) dfree(s, old_rows);
+    return TINYMPC_OK;
+}
+
 }  // namespace
+
+int tinympc_set_linear_constraints_batch(tinympc_solver *s, const double *Alin_x, const double *blin_x, int nlx, const double *Alin_u,
+                                         const double *blin_u, int nlu, int first, int count) {
+    return set_lin_batch(s, Alin_x, blin_x, nlx, Alin_u, blin_u, nlu, false, first, count);
+}
+int tinympc_set_linear_constraints_batch_device(tinympc_solver *s, const double *d_Alin_x, const double *d_blin_x, int nlx, const double *d_Alin_u,
+                                                const double *d_blin_u, int nlu, int first, int count) {
+    return set_lin_batch(s, d_Alin_x, d_blin_x, nlx, d_Alin_u, d_blin_u, nlu, true, first, count);
+}
 
 int tinympc_set_model_batch(tinympc_solver *s, const double *A, const double *B, const double *fdyn, const double *Q, const double *R,
                             int first, int count) {

@@ -183,14 +183,17 @@ struct SolveParams {
     double *GC, *GL;    // [groups][v_rows(N)][64]  duals gc|yc and gl|yl, persistent across solves
     double *LX;         // [groups][v_rows(N)][64]  -rho*(vcnew-gc) - rho*(vlnew-gl), forward -> backward
     // Adaptive rho (k_admm_solve_adapt only)
-    const double *adapt;  // tables of k_build_adapt, see adapt_doubles()
+    // (ilin: per-instance linear rows, read only by k_admm_solve_ifam, which has no adaptive rho -- see below; shares the slot so that the
+    // kernels' argument layout stays as it was)
+    union { const double *adapt; const double *ilin; };  // adapt: tables of k_build_adapt, see adapt_doubles()
     double *rho_inst;     // [batch] current rho of every instance; persists across solves like the reference's cache->rho
     double rho_min, rho_max;
     int rho_clip;
     // Layout C (k_admm_solve_c): horizon cut into chunk_count chunks of chunk_len steps, see chunk_plan()
     // (iref_lr: per-instance references, layout A only -- see below; shares the slot so that the kernels' argument layout stays as it was)
     union { const double *ctab; const double *iref_lr; };  // ctab: PhiS_l | PsiS_l (l < chunk_levels), each [16][chunk_ks(nx)]: powers S*2^l of the sweeps' state blocks
-    int chunk_len, chunk_count, chunk_levels;
+    union { int chunk_len; int ilin_nl; };  // (ilin_nl: rows per instance of ilin; layout A never reads chunk_len)
+    int chunk_count, chunk_levels;
     int families;         // layout C / the specialised layout D: run the cone / linear families too (the other layouts use k_admm_solve_fam)
     int adaptive;         // the specialised layout D: adaptive rho (the other layouts use k_admm_solve_adapt)
     int const_tables;     // bounds and references are the same at every knot (layout B keeps them in registers)
@@ -250,6 +253,9 @@ struct SolveParams {
     // bounds only): lo [groups][N+2][64] | hi [groups][N+2][64] (row k+1 = knot k, hi at inst_bnd_hi_offset()), followed by INST_LR_PAD
     // padding rows (the forward sweep reads that many knots ahead). Layout D's goal form (always): knot 0's rows lo [instance][W] |
     // hi [instance][W], hi at groups*64.
+    // Per-instance linear rows (tinympc_set_linear_constraints_batch; layout A's InstFamilies variant, k_admm_solve_ifam): ilin is
+    // [groups][3 * ilin_nl][64] -- per wavefront and row k the three vectors a_k | b_k | ||a_k||^2 of the shared description (fam_doubles()),
+    // one 512-byte line each, in the solve kernel's lane order; ilin_nl = max(rows per side) of the mode. Built by k_build_inst_lin.
 };
 
 // Per-instance references and bounds of a batched handle (k_store_inst_refs, k_build_inst_tables; tinympc_kernels.hip). The references
@@ -286,6 +292,19 @@ struct InstDiagParams {
     const double *add_inst;
     double *dst;
 };
+// Per-instance linear rows: the store SolveParams::ilin of instances [first, first+count) from the verb's arrays (k_build_inst_lin).
+// Ax: nlx x nx x count column-major, instance b's block at b * ax_stride; bx: nlx per instance at b * bx_stride; Au / bu likewise
+// (a stride of 0: one block for every instance -- the shared rows). Row k < nlx of a state lane: a = Ax[k, r], b = bx[k], the norm summed in
+// ascending column order with separate multiply and add (refresh_families does the same on the host: the same bits); rows the side does
+// not have, and lanes that are no row, are filled as the shared description fills them: a = 0, b = +inf, norm 1.
+struct InstLinParams {
+    int nx, nu, W, nl, nlx, nlu;
+    int batch, first, count;  // (first + count may reach into the last group's padding, up to groups * (64 / W): filled as absent)
+    const double *Ax, *bx, *Au, *bu;
+    size_t ax_stride, bx_stride, au_stride, bu_stride;
+    double *dst;
+};
+__host__ __device__ inline size_t inst_lin_doubles(int groups, int nl) { return (size_t)groups * 3 * (nl > 0 ? nl : 1) * 64; }
 struct InstTableParams {
     int nx, nu, N, W, KT, groups;
     int en_state_bound, en_input_bound;
@@ -471,6 +490,10 @@ hipError_t launch_fill_inst_models(const InstModelFillParams &p, hipStream_t str
 hipError_t launch_store_inst_diag(const InstDiagParams &p, hipStream_t stream);
 // *flag <- 1 if any of v[0, n) is not a finite number > 0 (per-instance rho from device memory: validated where it lies)
 hipError_t launch_check_positive(const double *v, int n, int *flag, hipStream_t stream);
+// Per-instance linear rows: the store's rows of p's instances, and the validation of the verb's input where it lies -- *flag <- 1 if a
+// row of A is all zero or holds a value that is not finite, or a b is NaN or -inf (the strides of p; dst is not touched)
+hipError_t launch_build_inst_lin(const InstLinParams &p, hipStream_t stream);
+hipError_t launch_check_inst_lin(const InstLinParams &p, int *flag, hipStream_t stream);
 hipError_t launch_check_ref_steps(const int *steps, int n, int delta, int *flag, hipStream_t stream);  // *flag = 1 if some steps[i] + delta < 0
 hipError_t launch_advance_ref_steps(int *steps, int n, int delta, hipStream_t stream);                 // steps[i] += delta, saturating in [0, INT_MAX]
 // Layout A: one wavefront per workgroup, all ADMM state in LDS (lowest latency, 2 waves per CU). One kernel body, three
@@ -482,7 +505,9 @@ hipError_t launch_advance_ref_steps(int *steps, int n, int delta, hipStream_t st
 // (k_admm_solve_ibnd, tinympc_solve.hip).
 // A sixth, InstModels, is InstBounds with every instance's own operator block (k_admm_solve_imod, tinympc_imod_a.hip):
 // SolveParams::ops then is [batch][ops_doubles(W, KT)].
-enum class SolveExt { Box, Families, Adaptive, InstRefs, InstBounds, InstModels };
+// A seventh, InstFamilies, is Families with every instance's own linear rows (k_admm_solve_ifam, tinympc_ifam_a.hip: SolveParams::ilin)
+// on the per-instance reference and clamp rows of InstBounds.
+enum class SolveExt { Box, Families, Adaptive, InstRefs, InstBounds, InstModels, InstFamilies };
 hipError_t launch_solve_a(const SolveParams &p, SolveExt ext, int W, int KT, size_t lds_bytes, hipStream_t stream);
 // Layout B: four wavefronts per workgroup sharing the tables in LDS, G and D in LDS, V as an
 // L2-resident ping-pong pair in HBM (4 waves per CU). Only W = 16, N >= 8.

@@ -102,6 +102,18 @@ struct InstState {
     std::vector<double> hXt, hUt;
     int hstep = 0;
     bool tracks() const { return x_track || u_track; }
+    // Per-instance linear rows (tinympc_set_linear_constraints_batch): on from the first call until tinympc_set_linear_constraints. The row
+    // COUNTS (lin_nlx, lin_nlu; also the handle's n_lin_x / n_lin_u while the mode is on) belong to the batch, the values to the
+    // instance: lrows is the store the kernel reads, SolveParams::ilin, [group][3 lin_nl][64] with lin_nl = max(lin_nlx, lin_nlu)
+    // (k_build_inst_lin; instances the verb never named hold the shared rows of the moment the mode began). Nothing else is kept: the
+    // store IS the rows, written inside the call. The mode runs on layout A's InstFamilies variant, always with the per-instance
+    // reference and clamp rows.
+    bool lin = false;
+    int lin_nlx = 0, lin_nlu = 0, lin_nl = 0;
+    double *lrows = nullptr;
+    size_t lrows_cap = 0;                    // doubles lrows was allocated for
+    double *lstage = nullptr;                // device staging of host input (the shared rows of a sub-range first call: a block of their own, freed in the call)
+    size_t lstage_cap = 0;
     int dirty_lo = 0, dirty_hi = 0;
     bool refs() const { return x || u; }
     const double *lr_rows() const { return lr + (size_t)tinympc::INST_LR_PAD * 64; }  // SolveParams::iref_lr on layout A
@@ -248,7 +260,7 @@ struct tinympc_solver {
     bool fam_dirty = true;
     // Per-instance references and bounds (tinympc_set_x_ref_batch / _u_ref_batch / _bound_constraints_batch; batched handles): InstState.
     InstState inst;
-    bool inst_tables() const { return inst.refs() || inst.bounds || inst.models; }  // the per-instance table rows are in use
+    bool inst_tables() const { return inst.refs() || inst.bounds || inst.models || inst.lin; }  // the per-instance table rows are in use
     // Goal form (every instance's references AND bounds constant over the horizon): layout D's constant-table kernel carries it, with
     // knot 0's rows per instance; everything else runs on layout A.
     bool iref_goal() const {
@@ -351,6 +363,7 @@ struct LaunchPlan {
     bool inst_refs = false;                  // ... per-instance references (layout A's InstRefs variant) or bounds (see inst_bounds)
     bool inst_bounds = false;                // ... per-instance bounds (layout A's InstBounds variant)
     bool inst_models = false;                // ... per-instance models (layout A's InstModels variant; inst_refs and inst_bounds are set with it)
+    bool inst_lin = false;                   // ... per-instance linear rows (layout A's InstFamilies variant; inst_refs and inst_bounds are set with it)
     bool jit = false;                        // a run-time specialisation (tinympc_jit.hip) rather than a compiled-in kernel
     bool host_exchange = false;              // the kernel serves the pinned-host paths (x0 in, solution / completion stamp out)
     int workgroups = 0;

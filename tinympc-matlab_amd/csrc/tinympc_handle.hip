@@ -358,7 +358,7 @@ int refresh_inst_tables(tinympc_solver *s) {
     p.x_min = in.bounds ? in.xmin : s->dxmin; p.x_max = in.bounds ? in.xmax : s->dxmax;
     p.u_min = in.bounds ? in.umin : s->dumin; p.u_max = in.bounds ? in.umax : s->dumax;
     p.lr = const_cast<double *>(in.lr_rows()); p.pn = in.pn; p.lrg = in.lrg; p.bndg = in.bndg;
-    p.bnd = (in.bounds || in.models) ? in.bnd : nullptr;  // (the models' kernel always reads per-instance clamp rows: shared bounds are copied)
+    p.bnd = (in.bounds || in.models || in.lin) ? in.bnd : nullptr;  // (the models' and the linear rows' kernels always read per-instance clamp rows: shared bounds are copied)
     HIP_TRY(launch_build_inst_tables(p, s->stream));
     in.dirty_lo = in.dirty_hi = 0;
     return TINYMPC_OK;
@@ -537,7 +537,10 @@ int refresh_families(tinympc_solver *s) {
     }
     (void)cone_x;
     (void)cone_u;
-    const int nlx = lin_x ? s->n_lin_x : 0, nlu = lin_u ? s->n_lin_u : 0;
+    // (per-instance linear rows: the rows live in InstState::lrows, k_admm_solve_ifam reads the enable flags above and nothing of the
+    // block below; the shared vectors may not even have the mode's counts)
+    const bool shared_rows = !s->inst.lin;
+    const int nlx = lin_x && shared_rows ? s->n_lin_x : 0, nlu = lin_u && shared_rows ? s->n_lin_u : 0;
     const int nl = nlx > nlu ? nlx : nlu;
     lin[0] = (double)nl;
     const double inf = std::numeric_limits<double>::infinity();

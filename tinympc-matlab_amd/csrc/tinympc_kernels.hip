@@ -4,6 +4,7 @@
 //   k_build_operators       fuses the cache into the two 1-step sweep operators used by the solve
 //   k_build_tables          per-knot clamp bounds / linear-cost reference terms
 //   k_build_inst_tables     the same rows per instance (per-instance references / bounds of a batched handle; reference tracks)
+//   k_build_inst_lin        per-instance linear rows: the store layout A's InstFamilies variant reads (k_check_inst_lin validates the input)
 //   k_advance_ref_steps     reference tracks: every instance's step moves on the device (k_check_ref_steps validates device input)
 //   k_build_adapt           adaptive rho: the sensitivity rows of the sweep operators and [A'; B']
 //
@@ -737,6 +738,84 @@ hipError_t launch_check_positive(const double *v, int n, int *flag, hipStream_t 
     if (n <= 0) return hipSuccess;
     const int blocks = (n + 255) / 256;
     hipLaunchKernelGGL(k_check_positive, dim3(blocks < 1024 ? blocks : 1024), dim3(256), 0, stream, v, n, flag);
+    return hipGetLastError();
+}
+
+// Per-instance linear rows (tinympc_set_linear_constraints_batch): the store k_admm_solve_ifam reads, SolveParams::ilin
+// [group][3 nl][64], for instances [first, first+count) -- one thread per (instance, row k, lane of the instance). The values are the
+// shared description's (refresh_families): a_k[r], b_k and ||a_k||^2 of the lane's side, the norm summed over the columns in ascending
+// order with a separate multiply and add (no contraction: the host's sum, bit for bit); a row the side does not have, a lane that is no
+// row and an instance beyond the batch (the last group's padding) get a = 0, b = +inf, norm 1.
+// (acc + v * v with the product rounded on its own. __dmul_rn / __dadd_rn alone do not keep the two apart here: they are plain operators
+// to this compiler, which contracts them into v_fmac_f64 whatever the contraction pragma says -- the norm of a 24-column row then
+// differed from the host's in the last bit. The empty asm hides the product's origin from the combiner.)
+__device__ __forceinline__ double add_square_unfused(double acc, double v) {
+    double sq = __dmul_rn(v, v);
+    asm volatile("" : "+v"(sq));
+    return __dadd_rn(acc, sq);
+}
+__global__ void __launch_bounds__(256) k_build_inst_lin(const InstLinParams p) {
+    const int W = p.W, IPW = 64 / W, nx = p.nx, nu = p.nu;
+    const size_t per = (size_t)p.nl * W, total = per * p.count;
+    const double inf = __longlong_as_double(0x7FF0000000000000LL);
+    for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
+        const size_t b = idx / per;
+        const int k = (int)((idx % per) / W), r = (int)(idx % W);
+        const size_t inst = (size_t)p.first + b;
+        double a = 0.0, bv = inf, nrm = 1.0;
+        if (inst < (size_t)p.batch && r < nx && k < p.nlx) {
+            const double *A = p.Ax + b * p.ax_stride;
+            nrm = 0.0;
+            for (int c = 0; c < nx; ++c) { const double v = A[k + (size_t)c * p.nlx]; nrm = add_square_unfused(nrm, v); }
+            a = A[k + (size_t)r * p.nlx];
+            bv = p.bx[b * p.bx_stride + k];
+        } else if (inst < (size_t)p.batch && r >= nx && r < nx + nu && k < p.nlu) {
+            const double *A = p.Au + b * p.au_stride;
+            nrm = 0.0;
+            for (int c = 0; c < nu; ++c) { const double v = A[k + (size_t)c * p.nlu]; nrm = add_square_unfused(nrm, v); }
+            a = A[k + (size_t)(r - nx) * p.nlu];
+            bv = p.bu[b * p.bu_stride + k];
+        }
+        double *row = p.dst + ((inst / IPW) * 3 * p.nl + (size_t)3 * k) * 64 + (inst % IPW) * W + r;
+        row[0] = a;
+        row[64] = bv;
+        row[128] = nrm;
+    }
+}
+hipError_t launch_build_inst_lin(const InstLinParams &p, hipStream_t stream) {
+    const size_t total = (size_t)p.nl * p.W * p.count;
+    if (total == 0) return hipSuccess;
+    const size_t blocks = (total + 255) / 256;
+    hipLaunchKernelGGL(k_build_inst_lin, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, stream, p);
+    return hipGetLastError();
+}
+// ... and the validation of the verb's arrays where they lie, one thread per (instance, row): *flag <- 1 if a row of A is all zero or
+// holds a value that is not finite, or its b is NaN or -inf (+inf switches the row off)
+__global__ void __launch_bounds__(256) k_check_inst_lin(const InstLinParams p, int *flag) {
+    const int rows = p.nlx + p.nlu;
+    const size_t total = (size_t)rows * p.count;
+    const double big = 1.79769313486231570815e308;
+    for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
+        const size_t b = idx / rows;
+        const int q = (int)(idx % rows);
+        const bool x = q < p.nlx;
+        const int k = x ? q : q - p.nlx, n = x ? p.nlx : p.nlu, cols = x ? p.nx : p.nu;
+        const double *A = x ? p.Ax + b * p.ax_stride : p.Au + b * p.au_stride;
+        const double bv = x ? p.bx[b * p.bx_stride + k] : p.bu[b * p.bu_stride + k];
+        bool any = false, finite = true;
+        for (int c = 0; c < cols; ++c) {
+            const double v = A[k + (size_t)c * n];
+            any = any || v != 0.0;
+            finite = finite && fabs(v) <= big;  // (NaN fails)
+        }
+        if (!any || !finite || !(bv >= -big)) *flag = 1;  // (NaN and -inf fail; +inf passes)
+    }
+}
+hipError_t launch_check_inst_lin(const InstLinParams &p, int *flag, hipStream_t stream) {
+    const size_t total = (size_t)(p.nlx + p.nlu) * p.count;
+    if (total == 0) return hipSuccess;
+    const size_t blocks = (total + 255) / 256;
+    hipLaunchKernelGGL(k_check_inst_lin, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(256), 0, stream, p, flag);
     return hipGetLastError();
 }
 

@@ -157,8 +157,14 @@ bool d_is_jit(const tinympc_solver *s, bool fam, bool adaptive) {
 // where the handle runs layout D, 16 lanes per instance (wider operators do not fit a wavefront's LDS share), references and bounds
 // constant over the horizon, box path. Whether the kernel exists is inst.d_models (resolve_plan).
 bool models_want_d(const tinympc_solver *s) {
-    return s->inst.models && s->specialise_asked && s->layout_d && !s->layout_m && s->W == 16 && s->iref_goal() && !s->families_active() &&
+    return s->inst.models && !s->inst.lin && s->specialise_asked && s->layout_d && !s->layout_m && s->W == 16 && s->iref_goal() && !s->families_active() &&
            !s->st.adaptive_rho;
+}
+
+// Per-instance linear rows (tinympc_set_linear_constraints_batch): ONE kernel, layout A's InstFamilies variant. What it cannot carry is
+// refused at the launch (lin_refusal), never solved with shared rows.
+bool lin_runs(const tinympc_solver *s) {
+    return s->inst.lin && !s->layout_m && !s->inst.models && !s->st.adaptive_rho && !family_structure(s).beyond_generic();
 }
 
 }  // namespace
@@ -175,12 +181,17 @@ namespace host {
 //   per-instance models                D's model form (only after tinympc_prepare: 16 lanes, references and bounds constant over the horizon,
 //                                      a horizon its per-wavefront operator plan holds)  >  A (the same refusals)
 //                                      (the mode of tinympc_set_model_batch AND tinympc_set_rho_batch: one form, rho always read per instance)
+//   per-instance linear rows           A's InstFamilies variant, whatever else is per instance (references, bounds) or shared (cones); with
+//                                      per-instance models / rho, adaptive rho, layout M or a cone structure beyond the generic kernels, launch() refuses
 LaunchPlan current_plan(const tinympc_solver *s) {
     LaunchPlan pl;
     const bool fam = s->families_active(), adaptive = s->st.adaptive_rho != 0, d = s->use_layout_d();
     pl.families = fam;
     pl.adaptive = adaptive;
-    if (s->inst_tables() && !s->layout_m && !fam && !adaptive) {
+    if (lin_runs(s)) {
+        pl.kernel = KernelId::A;
+        pl.inst_lin = pl.inst_refs = pl.inst_bounds = true;  // (the variant always runs on per-instance reference and clamp rows)
+    } else if (s->inst_tables() && !s->inst.lin && !s->layout_m && !fam && !adaptive) {
         // goals, where the handle runs layout D: its constant-table kernel (compiled in for the 16-lane shapes that are, run-time
         // specialised otherwise -- wide systems included); trajectories, and goals without such a kernel: layout A. "Goal" means that
         // references AND bounds are constant over the horizon, each per instance or shared
@@ -265,7 +276,7 @@ int resolve_plan(tinympc_solver *s) {
     int rc;
     if (s->inst_tables()) {  // layout A or D's goal form, or a refusal: only the goal form's specialisation to decide
         int &known = s->inst.d_goal;
-        if (known < 0 && s->layout_d && s->iref_goal() && !s->inst.models && !(s->W == 16 && !s->d_jit && solve_d_supported(s->nx, s->nu, s->N, true)) &&
+        if (known < 0 && !s->inst.lin && s->layout_d && s->iref_goal() && !s->inst.models && !(s->W == 16 && !s->d_jit && solve_d_supported(s->nx, s->nu, s->N, true)) &&
             !s->families_active() && !s->st.adaptive_rho)
             known = solve_jit_supported(s->W, s->nx, s->nu, s->N, true, false, false, true) ? 1 : 0;
         // ... and the model form's (compiled in for the quadrotor N=50, specialised now otherwise; a refusal leaves the mode on layout A)
@@ -344,6 +355,15 @@ int launch(tinympc_solver *s, bool timed) {
     if ((rc = resolve_plan(s))) return rc;
     const LaunchPlan pl = current_plan(s);
     const bool fam = pl.families, adaptive = pl.adaptive;
+    if (s->inst.lin && !pl.inst_lin) {  // never a solve with shared rows in their place
+        const char *why = s->layout_m ? "for systems with nx+nu > 64"
+                          : s->inst.models ? (s->inst.rho_verb ? "with per-instance models or rho (set_model_batch / set_rho_batch); tinympc_clear_model_batch returns to the shared model and rho"
+                                                               : "with per-instance models (set_model_batch); tinympc_clear_model_batch returns to the shared model")
+                          : adaptive ? "with adaptive rho"
+                                     : "with more cones or rounds of overlapping cones than the generic kernel holds";
+        return fail(TINYMPC_ERR_UNSUPPORTED, "per-instance linear constraints (set_linear_constraints_batch) are not supported %s; "
+                    "tinympc_set_linear_constraints returns to shared rows", why);
+    }
     if (s->inst_tables() && !pl.inst_refs) {  // never a solve with the shared references / bounds / model in their place
         const bool r = s->inst.refs(), b = s->inst.bounds, m = s->inst.models;
         const char *what[3], *back[3];
@@ -382,7 +402,7 @@ int launch(tinympc_solver *s, bool timed) {
         a.A = s->dA; a.B = s->dB; a.Pinf = s->dPinf; a.dK = s->ddK; a.dP = s->ddP; a.Xref = s->dXref; a.out = s->dadapt;
         HIP_TRY(launch_build_adapt(a, s->stream));
     }
-    if (fam && (rc = refresh_families(s))) return rc;
+    if ((fam || pl.inst_lin) && (rc = refresh_families(s))) return rc;  // (per-instance linear rows: the kernel reads cones and enable flags there)
     if (pl.inst_refs && (rc = refresh_inst_tables(s))) return rc;
     SolveParams p{};
     p.nx = s->nx; p.nu = s->nu; p.N = s->N; p.batch = s->batch;
@@ -395,7 +415,7 @@ int launch(tinympc_solver *s, bool timed) {
     p.istats = s->distats; p.dstats = s->ddstats;
     p.tables_in_lds = pl.tables_in_lds ? 1 : 0;
     p.fam = s->dfam; p.GC = s->dGC; p.GL = s->dGL; p.LX = s->dLX;
-    p.families = fam ? 1 : 0;
+    p.families = (fam || pl.inst_lin) ? 1 : 0;
     p.adaptive = adaptive ? 1 : 0;
     p.scratch = s->state_in_global ? s->dscratch_state : nullptr;
     if (s->layout_m && fam) {  // layout M with families: the forward sweep leaves its rollout x | u here for the families' phase
@@ -432,6 +452,7 @@ int launch(tinympc_solver *s, bool timed) {
         s->refs_on_host = false;  // the kernel brings the tables and the device copies up to date
     }
     p.adapt = s->dadapt; p.rho_inst = s->drho_inst;
+    if (pl.inst_lin) { p.ilin = s->inst.lrows; p.ilin_nl = s->inst.lin_nl; }  // (share the slots of adapt / chunk_len, which this kernel never reads)
     if (pl.inst_models) p.rho_inst = s->inst.mrho;  // (the model kernels read rho per instance: the handle's, or what tinympc_set_rho_batch set)
     if (pl.inst_refs) {
         p.iref_lr = pl.kernel == KernelId::A ? s->inst.lr_rows() : s->inst.lrg;
@@ -490,7 +511,7 @@ int launch(tinympc_solver *s, bool timed) {
         case KernelId::FAM_A:  // (the families and adaptive rho share the persistent state -- G, canonical V, D -- with every other kernel)
         case KernelId::ADAPT_A: {
             const SolveExt ext = pl.kernel == KernelId::FAM_A ? SolveExt::Families : pl.kernel == KernelId::ADAPT_A ? SolveExt::Adaptive
-                                 : pl.inst_models ? SolveExt::InstModels : pl.inst_bounds ? SolveExt::InstBounds : pl.inst_refs ? SolveExt::InstRefs : SolveExt::Box;
+                                 : pl.inst_lin ? SolveExt::InstFamilies : pl.inst_models ? SolveExt::InstModels : pl.inst_bounds ? SolveExt::InstBounds : pl.inst_refs ? SolveExt::InstRefs : SolveExt::Box;
             HIP_TRY(launch_solve_a(p, ext, s->W, s->KT, s->lds_bytes_a, s->stream));
             break;
         }
@@ -541,6 +562,7 @@ int tinympc_get_jit_info(tinympc_solver *s, char *buf, int len) {
     buf[0] = '\0';
     if ((rc = jit_info_text(s, buf, len))) return rc;
     if (s->inst.tracks()) strncat(buf, " reference-track", (size_t)len - strlen(buf) - 1);  // (a half is in track mode)
+    if (s->inst.lin) strncat(buf, " per-instance-linear", (size_t)len - strlen(buf) - 1);
     return TINYMPC_OK;
 }
 

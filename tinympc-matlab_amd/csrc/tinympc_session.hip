@@ -177,6 +177,9 @@ int tinympc_session_begin(tinympc_solver *s) {
     if (s->inst.models)
         return fail(TINYMPC_ERR_UNSUPPORTED, "session: per-instance models (set_model_batch)%s are not supported; tinympc_clear_model_batch returns to the shared model",
                     s->inst.rho_verb ? " with per-instance rho (set_rho_batch)" : "");
+    if (s->inst.lin)
+        return fail(TINYMPC_ERR_UNSUPPORTED, "session: per-instance linear constraints (set_linear_constraints_batch) are not supported; "
+                    "tinympc_set_linear_constraints returns to shared rows");
     if (s->st.max_iter < 1) return fail(TINYMPC_ERR_INVALID_INPUT, "session: max_iter must be >= 1");
     // Which resident kernel: layout F's (round 4) where the handle's launches run on layout F -- then the session's ticks are bit-identical
     // to launched ticks --, else the latency kernel's SESSION variant (layout C: box path, families up to N = 65 with disjoint cones).

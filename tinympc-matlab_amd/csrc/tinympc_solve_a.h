@@ -3,7 +3,7 @@
 // in its own source, as before: k_admm_solve (tinympc_solve.hip, the box path), k_admm_solve_fam (tinympc_solve_fam.hip, the
 // cone / linear slack families), k_admm_solve_adapt (tinympc_solve_adapt.hip, adaptive rho), k_admm_solve_iref
 // (tinympc_solve.hip, per-instance references), k_admm_solve_ibnd (tinympc_solve.hip, per-instance bounds) and k_admm_solve_imod
-// (tinympc_imod_a.hip, per-instance models). Each source instantiates
+// (tinympc_imod_a.hip, per-instance models) and k_admm_solve_ifam (tinympc_ifam_a.hip, per-instance linear rows). Each source instantiates
 // launch_solve_a_e for its variant; launch_solve_a (tinympc_solve.hip) dispatches to them.
 // (The body is not a __device__ __forceinline__ function: the compiler optimises such a function on its own before inlining
 // it, and the box kernel's generated code then changes even for a verbatim move.)
@@ -31,6 +31,8 @@ template <int W, int KT, bool TLDS, bool GMEM = false>
 __global__ void __launch_bounds__(64) k_admm_solve_ibnd(const SolveParams p);
 template <int W, int KT, bool TLDS, bool GMEM = false>
 __global__ void __launch_bounds__(64) k_admm_solve_imod(const SolveParams p);
+template <int W, int KT, bool TLDS, bool GMEM = false>
+__global__ void __launch_bounds__(64) k_admm_solve_ifam(const SolveParams p);
 
 template <SolveExt E, int W, int KT, bool TLDS, bool GMEM>
 void (*kernel_a())(const SolveParams) {
@@ -39,7 +41,8 @@ void (*kernel_a())(const SolveParams) {
     else if constexpr (E == SolveExt::Adaptive) return k_admm_solve_adapt<W, KT, TLDS, GMEM>;
     else if constexpr (E == SolveExt::InstRefs) return k_admm_solve_iref<W, KT, TLDS, GMEM>;
     else if constexpr (E == SolveExt::InstBounds) return k_admm_solve_ibnd<W, KT, TLDS, GMEM>;
-    else return k_admm_solve_imod<W, KT, TLDS, GMEM>;
+    else if constexpr (E == SolveExt::InstModels) return k_admm_solve_imod<W, KT, TLDS, GMEM>;
+    else return k_admm_solve_ifam<W, KT, TLDS, GMEM>;
 }
 
 template <SolveExt E, int W, int KT>
@@ -74,5 +77,6 @@ extern template hipError_t launch_solve_a_e<SolveExt::Adaptive>(const SolveParam
 extern template hipError_t launch_solve_a_e<SolveExt::InstRefs>(const SolveParams &, int, int, size_t, hipStream_t);  // tinympc_solve.hip
 extern template hipError_t launch_solve_a_e<SolveExt::InstBounds>(const SolveParams &, int, int, size_t, hipStream_t);  // tinympc_solve.hip
 extern template hipError_t launch_solve_a_e<SolveExt::InstModels>(const SolveParams &, int, int, size_t, hipStream_t);  // tinympc_imod_a.hip
+extern template hipError_t launch_solve_a_e<SolveExt::InstFamilies>(const SolveParams &, int, int, size_t, hipStream_t);  // tinympc_ifam_a.hip
 
 }  // namespace tinympc

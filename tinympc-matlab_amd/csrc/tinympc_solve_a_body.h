@@ -1,16 +1,20 @@
 // tinympc_solve_a_body.h -- the body of layout A's three solve kernels (k_admm_solve, k_admm_solve_fam, k_admm_solve_adapt;
-// tinympc_solve_a.h; and k_admm_solve_iref, k_admm_solve_ibnd, k_admm_solve_imod). Included INSIDE each kernel, with the kernel's template parameters W, KT,
+// tinympc_solve_a.h; and k_admm_solve_iref, k_admm_solve_ibnd, k_admm_solve_imod, k_admm_solve_ifam). Included INSIDE each kernel, with the kernel's template parameters W, KT,
 // TLDS, GMEM, its parameter p and the variant E (SolveExt) in scope; the families', adaptive rho's and per-instance references' and
 // bounds' additions are compiled only into their variant.
 // No include guard: it is meant to be included once per kernel.
-    constexpr bool FAM = E == SolveExt::Families, ADAPT = E == SolveExt::Adaptive;
+    // per-instance linear rows (with the per-instance rows of both kinds): the families' variant whose linear rows a_k | b_k | ||a_k||^2 are
+    // this lane's INSTANCE's, from p.ilin, [group][3 nl][64] -- one 512-byte line per row vector and wavefront -- instead of the shared
+    // description's; cones, enable flags and everything else as in the families' variant
+    constexpr bool IFAM = E == SolveExt::InstFamilies;
+    constexpr bool FAM = E == SolveExt::Families || IFAM, ADAPT = E == SolveExt::Adaptive;
     // per-instance references: this instance's linref rows and pNref from p.iref_lr / iref_pn (HBM / L2, the lane's own 512-byte line
     // per knot) instead of the shared tables; everything else as on the box path
     // per-instance bounds (with the per-instance references' rows): this instance's clamp rows from p.ibnd, streamed like the linref rows
     // per-instance models (with the per-instance rows of both kinds): this lane's operator rows and constants from its INSTANCE's block
     // of p.ops, [batch][ops_doubles(W, KT)] -- loads at the start of the solve only; the sweeps are InstBounds' sweeps
     constexpr bool IMOD = E == SolveExt::InstModels;
-    constexpr bool IBND = E == SolveExt::InstBounds || IMOD;
+    constexpr bool IBND = E == SolveExt::InstBounds || IMOD || IFAM;
     constexpr bool IREF = E == SolveExt::InstRefs || IBND;
     extern __shared__ __attribute__((aligned(16))) double smem[];
     refresh_reference_tables(p, W, KT);  // references handed over in pinned host memory (single-instance handles; adaptive rho: never)
@@ -133,16 +137,22 @@
     const double mu = FAM ? p.fam[W + r] : 0.0;
     const double inv_mu = (mu != 0.0) ? 1.0 / mu : 0.0;  // (mu = 0: row in no cone)
     const bool famc = FAM && p.fam[2 * W + r] != 0.0, faml = FAM && p.fam[3 * W + r] != 0.0;
-    const double *lin_rows = p.fam + 4 * W + 3 * M;
-    const int nl = FAM ? (int)lin_rows[0] : 0;
+    // (per-instance rows: row vector v of this wavefront at ilin + (grp 3 nl + v) 64, this lane's entry at + lane = j W + r; the shared
+    // description keeps its count in front of the vectors: base LB, vector stride LW -- lin_rows[LB + v LW + r] serves both)
+    constexpr int LW = IFAM ? 64 : W, LB = IFAM ? 0 : 1;
+    const double *lin_shared = p.fam + 4 * W + 3 * M;
+    const int nl = IFAM ? p.ilin_nl : FAM ? (int)lin_shared[0] : 0;
+    const double *lin_rows = IFAM ? p.ilin + ((size_t)grp * 3 * nl * 64 + j * W) : lin_shared;
     // the first FAM_REG_ROWS rows' coefficients in registers; problems with more rows (an equality constraint of five rows is
     // ten) read the rest from the family buffer (L2) where they are used
     double ak[FAM_REG_ROWS], bk[FAM_REG_ROWS], ink[FAM_REG_ROWS];  // ink = 1 / ||a_k||^2
 #pragma unroll
     for (int k = 0; k < (FAM && !RED ? FAM_REG_ROWS : 0); ++k) {
-        ak[k] = lin_rows[1 + (size_t)(3 * k + 0) * W + r];
-        bk[k] = lin_rows[1 + (size_t)(3 * k + 1) * W + r];
-        ink[k] = 1.0 / lin_rows[1 + (size_t)(3 * k + 2) * W + r];
+        // (the per-instance store holds nl >= 1 rows, not the shared description's capacity: a register beyond nl repeats row 0, never used)
+        const int kr = IFAM ? (k < nl ? k : 0) : k;
+        ak[k] = lin_rows[LB + (size_t)(3 * kr + 0) * LW + r];
+        bk[k] = lin_rows[LB + (size_t)(3 * kr + 1) * LW + r];
+        ink[k] = 1.0 / lin_rows[LB + (size_t)(3 * kr + 2) * LW + r];
     }
     // rounds of the cone list beyond the first (cones that share rows are projected one after another, as upstream does)
     const int nround = FAM ? (int)p.fam[fam_nround_offset(W, KT)] : 0;
@@ -168,8 +178,11 @@
     }
     // per-instance references: the first four rows the backward sweep reads (knots N-2 .. N-5) stay in registers for the whole solve, so
     // that no sweep starts waiting for HBM; the ring below keeps the rest of the rows four knots ahead
+    // (per-instance linear rows at 64 lanes per instance: with two operator rows of 64 doubles a wavefront has no registers left for the
+    // twelve -- the kernel lived in scratch, 120 bytes --; there every sweep fetches its first four rows when it starts)
+    constexpr bool TOP_PER_SWEEP = IFAM && W == 64;
     double lr_top[IREF ? 4 : 1];
-    if constexpr (IREF) {
+    if constexpr (IREF && !TOP_PER_SWEEP) {
         const double *t = p.iref_lr + ((size_t)grp * table_rows(N) + (N - 1)) * 64 + lane;
 #pragma unroll
         for (int k = 0; k < 4; ++k) lr_top[k] = t[-64 * k];
@@ -184,7 +197,7 @@
         bhi0 = t[bhi];
         t += (is_x ? 1 : 0) * 64;  // (koff, below: the first row a state lane's sweep reads is knot 1's)
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
+        for (int k = 0; k < (TOP_PER_SWEEP ? 0 : 4); ++k) {
             blo_top[k] = t[64 * k];
             bhi_top[k] = t[bhi + 64 * k];
         }
@@ -231,8 +244,8 @@
                 double sv = s0;
 #pragma unroll 1
                 for (int k = 0; k < nl; ++k) {  // (uniform trip count; the rows' coefficients from the family buffer in L2)
-                    const double a_k = lin_rows[1 + (size_t)(3 * k + 0) * W + r], b_k = lin_rows[1 + (size_t)(3 * k + 1) * W + r];
-                    const double in_k = 1.0 / lin_rows[1 + (size_t)(3 * k + 2) * W + r];
+                    const double a_k = lin_rows[LB + (size_t)(3 * k + 0) * LW + r], b_k = lin_rows[LB + (size_t)(3 * k + 1) * LW + r];
+                    const double in_k = 1.0 / lin_rows[LB + (size_t)(3 * k + 2) * LW + r];
                     const double prod = a_k * sv;
                     const double dx = group_sum<W>(is_x ? prod : 0.0), du = group_sum<W>(is_u ? prod : 0.0);  // a_k' x | a_k' u
                     sv = halfspace_project_element(sv, is_x ? dx : du, a_k, b_k, in_k);
@@ -283,8 +296,8 @@
             }
 #pragma unroll 1
             for (int k = FAM_REG_ROWS; k < nl; ++k) {                    // (uniform trip count)
-                const double a_k = lin_rows[1 + (size_t)(3 * k + 0) * W + r], b_k = lin_rows[1 + (size_t)(3 * k + 1) * W + r];
-                const double in_k = 1.0 / lin_rows[1 + (size_t)(3 * k + 2) * W + r];
+                const double a_k = lin_rows[LB + (size_t)(3 * k + 0) * LW + r], b_k = lin_rows[LB + (size_t)(3 * k + 1) * LW + r];
+                const double in_k = 1.0 / lin_rows[LB + (size_t)(3 * k + 2) * LW + r];
                 const double dot = group_matvec<W, KT>(ty, a_k * sv, 0.0);
                 sv = halfspace_project_element(sv, dot, a_k, b_k, in_k);
             }
@@ -353,6 +366,10 @@
             double *pgv = gV + (st ? koff * 64 + lane : gdummy);
             const int inc = st ? 64 : 0;
             double xcur = x0v;
+            if constexpr (TOP_PER_SWEEP) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) { blo_top[k] = pt[64 * k]; bhi_top[k] = pt[bhi + 64 * k]; }
+            }
             FwdOperands A{pg[0], pg[VOFF], IBND ? blo_top[0] : pt[0], IBND ? bhi_top[0] : pt[TOFF], pd[0]}, B;
             // per-instance rows come from HBM / L2, not LDS: three more rows of each in flight (reads past the last group's rows land in
             // the hi rows or in the padding behind them, INST_LR_PAD; never used)
@@ -484,6 +501,10 @@
             const double *pl = IREF ? p.iref_lr + ((size_t)grp * table_rows(N) + (N - 1)) * 64 + lane : t_lr + (N - 1) * W + r;
             double *pdst = sD + (stb ? (N - 2) * dstride + dIdx : dsize + lane);
             const int ddec = stb ? dstride : 0;
+            if constexpr (TOP_PER_SWEEP) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) lr_top[k] = pl[-64 * k];
+            }
             BwdOperands A{pb[0], pb[VOFF], IREF ? lr_top[0] : pl[0]}, B;
             // per-instance rows come from HBM / L2, not LDS: three more rows in flight (rows below row 0 are the previous group's or the
             // buffer's padding, INST_LR_PAD; never used)

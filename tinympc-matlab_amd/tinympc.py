@@ -410,6 +410,57 @@ class TinyMPC:
         self.settings["en_state_bound"] = True
         self.settings["en_input_bound"] = True
 
+    def set_linear_constraints_batch(self, Alin_x, blin_x, Alin_u, blin_u, first: int = 0):
+        """Per-instance linear constraints a'x <= b / a'u <= b for instances first, first+1, ...: numpy arrays of shape (nlx, nx, count),
+        (nlx, count), (nlu, nu, count), (nlu, count) -- or contiguous float64 CUDA tensors with the same memory layout, (count, nx, nlx),
+        (count, nlx), (count, nu, nlu), (count, nlu); an empty side is None (or an array without elements). On a single-instance solver
+        the arrays may lack the count axis. The row counts belong to the batch, the values to the instance; b = +inf switches one row
+        off for one instance. The first call names the whole batch unless the solver holds shared rows of the same counts (the other
+        instances then keep those); set_linear_constraints() returns every instance to shared rows. Enables the linear family of every
+        non-empty side, as set_linear_constraints does, and keeps the ADMM state: re-send the rows between two mpc_step() ticks."""
+        self._check_setup()
+        sides = []
+        for A, b, cols, name in ((Alin_x, blin_x, self.nx, "x"), (Alin_u, blin_u, self.nu, "u")):
+            empty = A is None or (hasattr(A, "numel") and A.numel() == 0) or (not hasattr(A, "numel") and np.asarray(A).size == 0)
+            if empty:
+                sides.append((None, None, 0, None, False))
+                continue
+            if hasattr(A, "data_ptr") and getattr(A, "is_cuda", False):
+                import torch
+                if not (hasattr(b, "data_ptr") and getattr(b, "is_cuda", False)):
+                    raise TinyMPCError(_lib.ERR_INVALID_INPUT, "linear rows: all must be CUDA tensors, or none")
+                if A.dim() == 2 and self.batch == 1:
+                    A, b = A.reshape((1,) + tuple(A.shape)), b.reshape(1, -1)
+                ok = A.dtype == torch.float64 and b.dtype == torch.float64 and A.is_contiguous() and b.is_contiguous() and A.dim() == 3 and \
+                    b.dim() == 2 and A.shape[1] == cols and tuple(b.shape) == (A.shape[0], A.shape[2])
+                if not ok:
+                    raise TinyMPCError(_lib.ERR_INVALID_INPUT, "linear rows on the device must be contiguous float64 tensors of shape (count, %d, nl%s) "
+                                       "and (count, nl%s), got %s and %s" % (cols, name, name, tuple(A.shape), tuple(b.shape)))
+                sides.append((C.c_void_p(A.data_ptr()), C.c_void_p(b.data_ptr()), int(A.shape[2]), int(A.shape[0]), True, (A, b)))
+            else:
+                A, b = np.asarray(A, dtype=np.float64), np.asarray(b, dtype=np.float64)
+                if A.ndim == 2 and self.batch == 1:
+                    A, b = A.reshape(A.shape + (1,)), b.reshape(-1, 1)
+                if A.ndim != 3 or A.shape[1] != cols or b.shape != (A.shape[0], A.shape[2]):
+                    raise TinyMPCError(_lib.ERR_INVALID_INPUT, "linear rows must be nl%s x %d x count and nl%s x count, got %s and %s"
+                                       % (name, cols, name, A.shape, b.shape))
+                A, b = _f(A), _f(b)
+                sides.append((_p(A), _p(b), int(A.shape[0]), int(A.shape[2]), False, (A, b)))
+        (pax, pbx, nlx, cx, dx, *keep_x), (pau, pbu, nlu, cu, du, *keep_u) = sides
+        if nlx and nlu and (cx != cu or dx != du):
+            raise TinyMPCError(_lib.ERR_INVALID_INPUT, "linear rows: both sides must have the same count and be on the same side of the bus")
+        on_device = dx if nlx else du
+        count = cx if nlx else cu if nlu else 0
+        if on_device:
+            import torch
+            torch.cuda.current_stream((keep_x or keep_u)[0][0].device).synchronize()  # (the set_x0_batch contract)
+        f = self._L.tinympc_set_linear_constraints_batch_device if on_device else self._L.tinympc_set_linear_constraints_batch
+        _lib.check(f(self._h, pax, pbx, nlx, pau, pbu, nlu, int(first), int(count)))
+        if nlx:
+            self.settings["en_state_linear"] = True
+        if nlu:
+            self.settings["en_input_linear"] = True
+
     def set_model_batch(self, A, B, Q, R, fdyn=None, first: int = 0):
         """Per-instance models for instances first, first+1, ...: numpy arrays of shape (nx, nx, count), (nx, nu, count), (nx, nx, count),
         (nu, nu, count) and, optionally, fdyn (nx, count) -- or contiguous float64 CUDA tensors with the same memory layout, (count, nx, nx)

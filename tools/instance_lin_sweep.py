@@ -1,0 +1,165 @@
+"""Per-instance linear rows at bench size.
+
+Kernel milliseconds (HIP events, tinympc_solve_timed) of the same forced-iteration solve of `--batch` quadrotors (N = `--N`, `--iters`
+iterations, one state row plus one input row) with
+  shared-A   the rows shared (tinympc_set_linear_constraints), the handle forced to layout A (TINYMPC_LAYOUT=A): k_admm_solve_fam --
+             the yardstick: the same inner loop, the rows from the shared description
+  per-inst   the SAME rows sent per instance (tinympc_set_linear_constraints_batch): k_admm_solve_ifam
+Every measurement is a fresh process; the two legs alternate, `--rounds` times each, so they share the call's noise. Reported: each
+round's median of `--reps` launches, the legs' medians and spreads, and whether per-inst's median lies inside shared-A's spread.
+Beside the legs: the same shared-row handle on the layout it picks by default (context), and the wall time of
+set_linear_constraints_batch and of its _device form for the whole batch (first call, which allocates the store, and repeats).
+    python tools/instance_lin_sweep.py [--batch 8192] [--N 20] [--iters 100] [--rounds 4] [--reps 5]"""
+import argparse
+import ctypes as C
+import json
+import os
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+LEGS = ["shared-A", "per-inst"]
+
+
+def rows(prob, batch, seed=7):
+    """One state row and one input row, the same for every instance: (Ax (1, nx), bx (1,), Au (1, nu), bu (1,)) and x0s."""
+    rng = np.random.default_rng(seed)
+    ax, au = rng.standard_normal((1, prob.nx)), rng.standard_normal((1, prob.nu))
+    ax, au = ax / np.linalg.norm(ax), au / np.linalg.norm(au)
+    return ax, np.array([float(ax[0] @ prob.x0) + 0.3]), au, np.array([0.2])
+
+
+def make(pkg, leg, a):
+    prob = pkg.problems.quadrotor(a.N)
+    if leg == "shared-A":
+        os.environ["TINYMPC_LAYOUT"] = "A"
+    else:
+        os.environ.pop("TINYMPC_LAYOUT", None)
+    s = pkg.TinyMPC()
+    s.setup(prob.A, prob.B, prob.Q, prob.R, prob.N, batch=a.batch, rho=prob.rho, abs_pri_tol=0.0, abs_dua_tol=0.0, max_iter=a.iters)
+    s.set_bound_constraints(prob.x_min, prob.x_max, prob.u_min, prob.u_max)
+    ax, bx, au, bu = rows(prob, a.batch)
+    if leg == "per-inst":
+        s.set_linear_constraints_batch(*(np.repeat(m[..., None], a.batch, axis=-1) for m in (ax, bx, au, bu)))
+    else:
+        s.set_linear_constraints(ax, bx, au, bu)
+    s.set_x0_batch(pkg.problems.quadrotor_batch_x0(a.batch))
+    return s
+
+
+def device_copy(pkg, arrays):
+    """Device copies of `arrays` through the HIP runtime the library itself uses, or None where that runtime cannot be found."""
+    pkg.load_library()
+    with open("/proc/self/maps") as f:
+        paths = sorted({line.split()[-1] for line in f if "libamdhip64" in line and "/torch/" not in line})
+    if not paths:
+        return None
+    hip = C.CDLL(paths[0])
+    hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
+    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    out = []
+    for h in arrays:
+        p = C.c_void_p()
+        if hip.hipMalloc(C.byref(p), h.nbytes) != 0 or hip.hipMemcpy(p, C.c_void_p(h.ctypes.data), h.nbytes, 1) != 0:
+            return None
+        out.append(p)
+    return out
+
+
+def child(pkg, a):
+    """One process: one leg's kernel time; the per-inst leg also times the verbs, the shared leg also the default layout. One line."""
+    s = make(pkg, a.child, a)
+    s.solve_timed()  # warm-up: first launch, table builds
+    out = dict(leg=a.child, kernel_ms=float(np.median([s.solve_timed() for _ in range(a.reps)])),
+               kernel="%s %s" % (s.launch_info()["layout"], s.jit_info()))
+    if a.child == "per-inst":
+        prob = pkg.problems.quadrotor(a.N)
+        L, dp = pkg.load_library(), pkg._lib.c_double_p
+        host = [np.asfortranarray(np.repeat(m[..., None], a.batch, axis=-1)) for m in rows(prob, a.batch)]
+        dev = device_copy(pkg, host)
+        fresh = pkg.TinyMPC()
+        fresh.setup(prob.A, prob.B, prob.Q, prob.R, prob.N, batch=a.batch, rho=prob.rho)
+        wall, wall_dev = [], []
+        for _ in range(1 + a.reps):
+            t0 = time.perf_counter()
+            rc = L.tinympc_set_linear_constraints_batch(fresh._h, host[0].ctypes.data_as(dp), host[1].ctypes.data_as(dp), 1,
+                                                        host[2].ctypes.data_as(dp), host[3].ctypes.data_as(dp), 1, 0, a.batch)
+            wall.append(1e3 * (time.perf_counter() - t0))
+            assert rc == 0, pkg._lib.last_error()
+        for _ in range(a.reps if dev else 0):
+            t0 = time.perf_counter()
+            rc = L.tinympc_set_linear_constraints_batch_device(fresh._h, dev[0], dev[1], 1, dev[2], dev[3], 1, 0, a.batch)
+            wall_dev.append(1e3 * (time.perf_counter() - t0))
+            assert rc == 0, pkg._lib.last_error()
+        out.update(verb_host_ms=wall, verb_device_ms=wall_dev)
+        fresh.reset()
+    else:  # context: the same shared rows on the layout the handle picks by default
+        s.reset()
+        os.environ.pop("TINYMPC_LAYOUT", None)
+        s = make(pkg, "shared-default", a)
+        s.solve_timed()
+        out.update(default_ms=float(np.median([s.solve_timed() for _ in range(a.reps)])),
+                   default_kernel="%s %s" % (s.launch_info()["layout"], s.jit_info()))
+    s.reset()
+    print("LIN-CHILD " + json.dumps(out), flush=True)
+
+
+def sweep(a):
+    """Starts the children (it never opens the GPU itself) and prints the table."""
+    recs = {leg: [] for leg in LEGS}
+    for rnd in range(a.rounds):
+        for leg in LEGS if rnd % 2 == 0 else LEGS[::-1]:
+            env = dict(os.environ)
+            env.pop("TINYMPC_LAYOUT", None)
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", leg, "--batch", str(a.batch), "--N", str(a.N),
+                                "--iters", str(a.iters), "--reps", str(a.reps)], env=env, capture_output=True, text=True, timeout=300)
+            line = [l for l in r.stdout.splitlines() if l.startswith("LIN-CHILD ")]
+            if r.returncode != 0 or not line:
+                raise SystemExit("round %d (%s) failed with %d:\n%s\n%s" % (rnd, leg, r.returncode, r.stdout[-2000:], r.stderr[-2000:]))
+            recs[leg].append(json.loads(line[0][len("LIN-CHILD "):]))
+            print("# round %d %-9s %.4f ms" % (rnd, leg, recs[leg][-1]["kernel_ms"]), flush=True)
+    print("per-instance linear rows: %d quadrotors N=%d x %d forced iterations, 1 state row + 1 input row; kernel ms (median of %d launches per "
+          "round, %d rounds, a fresh process each, legs alternating)" % (a.batch, a.N, a.iters, a.reps, a.rounds))
+    ms = {leg: [r["kernel_ms"] for r in recs[leg]] for leg in LEGS}
+    for leg in LEGS:
+        print("%-9s | %s | median %.4f | spread %.4f - %.4f | %s" % (leg, " ".join("%.4f" % v for v in ms[leg]), float(np.median(ms[leg])),
+                                                                    min(ms[leg]), max(ms[leg]), recs[leg][0]["kernel"]))
+    med, lo, hi = float(np.median(ms["per-inst"])), min(ms["shared-A"]), max(ms["shared-A"])
+    print("per-inst median inside shared-A's spread: %s (%.4f against %.4f - %.4f; ratio of medians %.3f)"
+          % ("yes" if lo <= med <= hi else "NO", med, lo, hi, med / float(np.median(ms["shared-A"]))))
+    d = [r["default_ms"] for r in recs["shared-A"]]
+    print("context, shared rows on the default layout: %s | median %.4f | %s" % (" ".join("%.4f" % v for v in d), float(np.median(d)),
+                                                                                 recs["shared-A"][0]["default_kernel"]))
+    for key, name in (("verb_host_ms", "set_linear_constraints_batch"), ("verb_device_ms", "set_linear_constraints_batch_device")):
+        first = [r[key][0] for r in recs["per-inst"] if r[key]]
+        rest = [v for r in recs["per-inst"] for v in (r[key][1:] if key == "verb_host_ms" else r[key])]
+        if not rest:
+            print("%-36s not measured (no device memory could be filled)" % name)
+            continue
+        print("%-36s %d instances, wall ms: %s median %.3f (min %.3f, max %.3f)"
+              % (name, a.batch, ("first call %s | repeats" % " ".join("%.3f" % v for v in first)) if key == "verb_host_ms" else "calls",
+                 float(np.median(rest)), min(rest), max(rest)))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=8192)
+    ap.add_argument("--N", type=int, default=20)
+    ap.add_argument("--iters", type=int, default=100)
+    ap.add_argument("--rounds", type=int, default=4)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--child", default="", help=argparse.SUPPRESS)
+    a = ap.parse_args()
+    if not a.child:
+        return sweep(a)
+    import __graft_entry__ as ge
+    child(ge.load_package(), a)
+
+
+if __name__ == "__main__":
+    main()
