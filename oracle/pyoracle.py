@@ -54,6 +54,28 @@ def ref_available() -> bool:
     return os.path.exists(REF_LIB)
 
 
+def project_soc(sv, mu: float):
+    """orc_test_project_soc: the restatement's own cone projection of one vector (t last) -> (projected copy, outcome 0 / 1 / 2)."""
+    L = C.CDLL(PORT_LIB)
+    L.orc_test_project_soc.argtypes = [_dp, C.c_int, C.c_double]
+    a = np.array(sv, dtype=np.float64).ravel().copy()
+    took = int(L.orc_test_project_soc(_p(a), a.size, float(mu)))
+    return a, took
+
+
+def project_halfspaces(sv, Alin, blin):
+    """orc_test_project_halfspaces: the restatement's own row-after-row projection onto Alin s <= blin -> (projected copy,
+    number of violated rows)."""
+    L = C.CDLL(PORT_LIB)
+    L.orc_test_project_halfspaces.argtypes = [_dp, C.c_int, C.c_int, _dp, _dp]
+    a = np.array(sv, dtype=np.float64).ravel().copy()
+    A = _f(np.asarray(Alin, dtype=np.float64).reshape(-1, a.size))
+    b = _f(np.asarray(blin, dtype=np.float64).ravel())
+    assert A.shape[0] == b.size
+    hit = int(L.orc_test_project_halfspaces(_p(a), a.size, b.size, _p(A), _p(b)))
+    return a, hit
+
+
 class _Base:
     nx: int
     nu: int
@@ -138,6 +160,7 @@ class OraclePort(_Base):
         self._settings = dict(abs_pri_tol=1e-3, abs_dua_tol=1e-3, max_iter=1000, check_termination=1,
                               en_state_bound=1, en_input_bound=1, en_state_soc=0, en_input_soc=0,
                               en_state_linear=0, en_input_linear=0)
+        self._family_counts = [0, 0, 0, 0]  # state cones, input cones, state rows, input rows (the census's last axes)
         if prob.cones:
             self.set_cone_constraints(**prob.cones)
         if prob.linear:
@@ -184,6 +207,7 @@ class OraclePort(_Base):
             self._settings["en_state_soc"] = 1
         if au.size:
             self._settings["en_input_soc"] = 1
+        self._family_counts[0:2] = [int(ax.size), int(au.size)]
         return self.L.orc_set_cone_constraints(
             self.h, ax.size, ax.ctypes.data_as(_ip), qx.ctypes.data_as(_ip), _p(cxa),
             au.size, au.ctypes.data_as(_ip), qu.ctypes.data_as(_ip), _p(cua))
@@ -196,6 +220,7 @@ class OraclePort(_Base):
             self._settings["en_state_linear"] = 1
         if nlu:
             self._settings["en_input_linear"] = 1
+        self._family_counts[2:4] = [int(nlx), int(nlu)]
         return self.L.orc_set_linear_constraints(self.h, nlx, _p(ax), _p(bx), nlu, _p(au), _p(bu))
 
     def update_settings(self, **kw):
@@ -225,6 +250,31 @@ class OraclePort(_Base):
 
     def solve(self) -> int:
         return self.L.orc_solve(self.h)
+
+    def enable_census(self, max_iterations: int) -> None:
+        """Record, from the next solve() on, which outcome every cone / half-space projection takes (0 switches it off)."""
+        self.L.orc_enable_census.argtypes = [C.c_void_p, C.c_int]
+        if self.L.orc_enable_census(self.h, int(max_iterations)) != 0:
+            raise MemoryError("orc_enable_census")
+
+    def family_census(self) -> dict:
+        """The last solve()'s record: cone_x [iterations, N, state cones] and cone_u [iterations, N-1, input cones] hold
+        0 apex / 1 inside / 2 surface, lin_x [iterations, N, state rows] and lin_u [iterations, N-1, input rows] hold
+        0 not violated / 1 violated (255: no projection ran there, e.g. a family switched off)."""
+        L = self.L
+        L.orc_get_census.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_ubyte), C.c_int]
+        L.orc_census_iterations.argtypes = [C.c_void_p]
+        its = int(L.orc_census_iterations(self.h))
+        s = self._family_counts
+        out = {}
+        for name, knots, count in (("cone_x", self.N, s[0]), ("cone_u", self.N - 1, s[1]),
+                                   ("lin_x", self.N, s[2]), ("lin_u", self.N - 1, s[3])):
+            a = np.zeros((its, knots, count), dtype=np.uint8)
+            n = L.orc_get_census(self.h, name.encode(), a.ctypes.data_as(C.POINTER(C.c_ubyte)), a.size)
+            if n != a.size:
+                raise KeyError(f"{name}: census returned {n}, expected {a.size}")
+            out[name] = a
+        return out
 
     def forward_pass(self):
         self.L.orc_forward_pass(self.h)

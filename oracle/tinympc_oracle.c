@@ -212,6 +212,7 @@ void orc_free(orc_solver *s) {
                       s->yl, s->sol_x, s->sol_u, s->dKinf_drho, s->dPinf_drho};
     for (size_t i = 0; i < sizeof(ptrs) / sizeof(ptrs[0]); ++i) free(ptrs[i]);
     free(s->Acx); free(s->qcx); free(s->Acu); free(s->qcu);
+    free(s->cen_cone_x); free(s->cen_cone_u); free(s->cen_lin_x); free(s->cen_lin_u);
     free(s);
 }
 
@@ -273,6 +274,7 @@ int orc_set_cone_constraints(orc_solver *s, int ncx, const int *Acx, const int *
     s->n_cone_u = ncu; s->Acu = icopy(Acu, ncu); s->qcu = icopy(qcu, ncu); s->cu = dcopy(cu, ncu);
     if (ncx > 0) s->en_state_soc = 1;
     if (ncu > 0) s->en_input_soc = 1;
+    if (s->census_cap) return orc_enable_census(s, s->census_cap); /* the record is sized by the lists */
     return 0;
 }
 
@@ -284,6 +286,7 @@ int orc_set_linear_constraints(orc_solver *s, int nlx, const double *Alin_x, con
     s->n_lin_u = nlu; s->Alin_u = dcopy(Alin_u, (size_t)nlu * s->nu); s->blin_u = dcopy(blin_u, nlu);
     if (nlx > 0) s->en_state_linear = 1;
     if (nlu > 0) s->en_input_linear = 1;
+    if (s->census_cap) return orc_enable_census(s, s->census_cap);
     return 0;
 }
 
@@ -345,25 +348,30 @@ void orc_forward_pass(orc_solver *s) {
     }
 }
 
-/* UNPINNED: upstream project_soc -- cone { (w, t) : ||w||_2 <= mu * t }, t = last entry. */
-static void project_soc(double *sv, int n, double mu) {
+/* UNPINNED: upstream project_soc -- cone { (w, t) : ||w||_2 <= mu * t }, t = last entry.
+ * Returns which of the three outcomes it took (region census; the arithmetic does not depend on it). */
+static int project_soc(double *sv, int n, double mu) {
     double u0 = sv[n - 1] * mu;
     double a = 0.0;
     for (int i = 0; i < n - 1; ++i) a += sv[i] * sv[i];
     a = sqrt(a);
     if (a <= -u0) {
         for (int i = 0; i < n; ++i) sv[i] = 0.0;
+        return ORC_SOC_APEX;
     } else if (a <= u0) {
-        /* inside */
+        return ORC_SOC_INSIDE;
     } else {
         double scale = 0.5 * (1.0 + u0 / a);
         for (int i = 0; i < n - 1; ++i) sv[i] = scale * sv[i];
         sv[n - 1] = scale * (a / mu);
+        return ORC_SOC_SURFACE;
     }
 }
 
-/* UNPINNED: half-space projection a's <= b, rows applied one after another. */
-static void project_halfspaces(double *sv, int n, int rows, const double *Alin, const double *blin) {
+/* UNPINNED: half-space projection a's <= b, rows applied one after another. `took` (region census; may be NULL)
+ * receives 0 / 1 per row: not violated / violated. Returns the number of violated rows. */
+static int project_halfspaces(double *sv, int n, int rows, const double *Alin, const double *blin, unsigned char *took) {
+    int violated = 0;
     for (int k = 0; k < rows; ++k) {
         double dot = 0.0, nrm = 0.0;
         for (int c = 0; c < n; ++c) {
@@ -371,12 +379,89 @@ static void project_halfspaces(double *sv, int n, int rows, const double *Alin, 
             dot += a * sv[c];
             nrm += a * a;
         }
-        if (dot > blin[k]) {
+        const int hit = dot > blin[k];
+        if (hit) {
             double dist = (dot - blin[k]) / nrm;
             for (int c = 0; c < n; ++c) sv[c] -= dist * Alin[k + (size_t)c * rows];
+            ++violated;
         }
+        if (took) took[k] = (unsigned char)hit;
+    }
+    return violated;
+}
+
+int orc_test_project_soc(double *sv, int n, double mu) { return project_soc(sv, n, mu); }
+int orc_test_project_halfspaces(double *sv, int n, int rows, const double *Alin, const double *blin) {
+    return project_halfspaces(sv, n, rows, Alin, blin, NULL);
+}
+
+/* ---------------------------------------------------------------- region census
+ * One byte per projection of the iteration s->iter (orc_solve counts it up after the slack update, so the first
+ * iteration of a solve is 0). Off (census_cap == 0) or beyond its capacity, census_at returns NULL and nothing is written. */
+static size_t census_stride(const orc_solver *s, int side) { /* bytes per iteration of one side */
+    switch (side) {
+    case 0: return (size_t)s->N * s->n_cone_x;
+    case 1: return (size_t)(s->N - 1) * s->n_cone_u;
+    case 2: return (size_t)s->N * s->n_lin_x;
+    default: return (size_t)(s->N - 1) * s->n_lin_u;
     }
 }
+
+static unsigned char **census_side(orc_solver *s, int side) {
+    return side == 0 ? &s->cen_cone_x : side == 1 ? &s->cen_cone_u : side == 2 ? &s->cen_lin_x : &s->cen_lin_u;
+}
+
+static unsigned char *census_at(orc_solver *s, int side) {
+    unsigned char *base = *census_side(s, side);
+    if (!base || s->iter < 0 || s->iter >= s->census_cap) return NULL;
+    return base + (size_t)s->iter * census_stride(s, side);
+}
+
+static void census_clear(orc_solver *s) {
+    for (int side = 0; side < 4; ++side) {
+        unsigned char *base = *census_side(s, side);
+        if (base) memset(base, ORC_NOT_EVALUATED, (size_t)s->census_cap * census_stride(s, side));
+    }
+    s->census_iters = 0;
+}
+
+int orc_enable_census(orc_solver *s, int max_iterations) {
+    for (int side = 0; side < 4; ++side) {
+        unsigned char **p = census_side(s, side);
+        free(*p);
+        *p = NULL;
+    }
+    s->census_cap = 0;
+    s->census_iters = 0;
+    if (max_iterations <= 0) return 0;
+    for (int side = 0; side < 4; ++side) {
+        size_t n = (size_t)max_iterations * census_stride(s, side);
+        unsigned char *p = (unsigned char *)malloc(n ? n : 1);
+        if (!p) return orc_enable_census(s, 0), 1;
+        *census_side(s, side) = p;
+    }
+    s->census_cap = max_iterations;
+    census_clear(s);
+    return 0;
+}
+
+static int census_index(const char *name) {
+    static const char *names[] = {"cone_x", "cone_u", "lin_x", "lin_u"};
+    for (int i = 0; i < 4; ++i)
+        if (!strcmp(name, names[i])) return i;
+    return -1;
+}
+
+int orc_get_census(orc_solver *s, const char *name, unsigned char *out, int capacity) {
+    const int side = census_index(name);
+    if (side < 0) return -1;
+    const size_t n = (size_t)s->census_iters * census_stride(s, side);
+    if ((size_t)capacity < n) return -2;
+    if (n) memcpy(out, *census_side(s, side), n);
+    return (int)n;
+}
+
+int orc_census_iterations(orc_solver *s) { return s->census_iters; }
 
 /* S1: admm.cpp:43-59 */
 void orc_update_slack(orc_solver *s) {
@@ -397,25 +482,35 @@ void orc_update_slack(orc_solver *s) {
     /* UNPINNED below */
     if (s->en_state_soc && s->n_cone_x > 0) {
         for (size_t i = 0; i < X; ++i) s->vcnew[i] = s->x[i] + s->gc[i];
+        unsigned char *cen = s->census_cap ? census_at(s, 0) : NULL;
         for (int i = 0; i < N; ++i)
-            for (int k = 0; k < s->n_cone_x; ++k)
-                project_soc(s->vcnew + (size_t)i * nx + s->Acx[k], s->qcx[k], s->cx[k]);
+            for (int k = 0; k < s->n_cone_x; ++k) {
+                const int took = project_soc(s->vcnew + (size_t)i * nx + s->Acx[k], s->qcx[k], s->cx[k]);
+                if (cen) cen[(size_t)i * s->n_cone_x + k] = (unsigned char)took;
+            }
     }
     if (s->en_input_soc && s->n_cone_u > 0) {
         for (size_t i = 0; i < U; ++i) s->zcnew[i] = s->u[i] + s->yc[i];
+        unsigned char *cen = s->census_cap ? census_at(s, 1) : NULL;
         for (int i = 0; i < N - 1; ++i)
-            for (int k = 0; k < s->n_cone_u; ++k)
-                project_soc(s->zcnew + (size_t)i * nu + s->Acu[k], s->qcu[k], s->cu[k]);
+            for (int k = 0; k < s->n_cone_u; ++k) {
+                const int took = project_soc(s->zcnew + (size_t)i * nu + s->Acu[k], s->qcu[k], s->cu[k]);
+                if (cen) cen[(size_t)i * s->n_cone_u + k] = (unsigned char)took;
+            }
     }
     if (s->en_state_linear && s->n_lin_x > 0) {
         for (size_t i = 0; i < X; ++i) s->vlnew[i] = s->x[i] + s->gl[i];
+        unsigned char *cen = s->census_cap ? census_at(s, 2) : NULL;
         for (int i = 0; i < N; ++i)
-            project_halfspaces(s->vlnew + (size_t)i * nx, nx, s->n_lin_x, s->Alin_x, s->blin_x);
+            project_halfspaces(s->vlnew + (size_t)i * nx, nx, s->n_lin_x, s->Alin_x, s->blin_x,
+                               cen ? cen + (size_t)i * s->n_lin_x : NULL);
     }
     if (s->en_input_linear && s->n_lin_u > 0) {
         for (size_t i = 0; i < U; ++i) s->zlnew[i] = s->u[i] + s->yl[i];
+        unsigned char *cen = s->census_cap ? census_at(s, 3) : NULL;
         for (int i = 0; i < N - 1; ++i)
-            project_halfspaces(s->zlnew + (size_t)i * nu, nu, s->n_lin_u, s->Alin_u, s->blin_u);
+            project_halfspaces(s->zlnew + (size_t)i * nu, nu, s->n_lin_u, s->Alin_u, s->blin_u,
+                               cen ? cen + (size_t)i * s->n_lin_u : NULL);
     }
 }
 
@@ -500,9 +595,11 @@ int orc_termination_condition(orc_solver *s) {
 int orc_solve(orc_solver *s) {
     const size_t X = (size_t)s->nx * s->N, U = (size_t)s->nu * (s->N - 1);
     s->solved = 0; s->sol_iter = 0; s->status = 11; s->iter = 0; /* :112-115 */
+    if (s->census_cap) census_clear(s);
     for (int i = 0; i < s->max_iter; ++i) {
         orc_forward_pass(s);        /* :132 */
         orc_update_slack(s);        /* :135 */
+        if (s->census_cap && s->iter < s->census_cap) s->census_iters = s->iter + 1;
         orc_update_dual(s);         /* :138 */
         orc_update_linear_cost(s);  /* :141 */
         s->iter += 1;               /* :143 */

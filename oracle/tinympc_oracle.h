@@ -70,7 +70,19 @@ typedef struct orc_solver {
     /* TinySolution (types.hpp:32-37) */
     int sol_iter, solved;
     double *sol_x, *sol_u;
+
+    /* Region census (test instrumentation, off unless orc_enable_census): which outcome every projection of the last
+     * orc_solve took. census_cap = iterations the arrays hold (0: off, arrays NULL), census_iters = iterations recorded. */
+    int census_cap, census_iters;
+    unsigned char *cen_cone_x, *cen_cone_u; /* [iteration][knot][cone]: ORC_SOC_APEX / _INSIDE / _SURFACE */
+    unsigned char *cen_lin_x, *cen_lin_u;   /* [iteration][knot][row]:  0 not violated / 1 violated */
 } orc_solver;
+
+/* outcome of one second-order-cone projection; ORC_NOT_EVALUATED fills census entries no projection wrote */
+#define ORC_SOC_APEX 0
+#define ORC_SOC_INSIDE 1
+#define ORC_SOC_SURFACE 2
+#define ORC_NOT_EVALUATED 255
 
 /* tiny_setup (tiny_api.cpp:21-122); fdyn may be NULL (zeros). Bounds start at -/+1e17 with the
  * core's default flags (tiny_api_constants.hpp:5-10). Returns NULL on allocation failure. */
@@ -129,6 +141,23 @@ int orc_set_sensitivity(orc_solver *s, const double *dKinf_drho, const double *d
 /* benchmark_rho_adaptation (rho_benchmark.cpp:200-249) on the current workspace; returns the new rho */
 double orc_rho_adaptation(orc_solver *s);
 void orc_set_iter(orc_solver *s, int iter);
+
+/* Region census. orc_enable_census allocates the record for up to `max_iterations` iterations of the constraint lists the
+ * solver holds (setting new lists afterwards re-allocates it); 0 switches it off again. Every orc_solve then records, per
+ * iteration, knot and cone / row, the outcome of the projection (iterations beyond max_iterations are not recorded).
+ * orc_get_census copies one side out -- name "cone_x", "cone_u", "lin_x" or "lin_u" -- as
+ * [census_iters][knots][count] (C order; knots = N on the state side, N-1 on the input side) and returns the element
+ * count, -1 for an unknown name, -2 if `capacity` is too small. Returns 0 elements while the census is off. */
+int orc_enable_census(orc_solver *s, int max_iterations);
+int orc_get_census(orc_solver *s, const char *name, unsigned char *out, int capacity);
+int orc_census_iterations(orc_solver *s);
+
+/* The two projections of the UNPINNED families as test entry points: the same static functions orc_update_slack calls.
+ * orc_test_project_soc projects sv (n entries, t last) onto { ||w|| <= mu t } in place and returns the outcome code;
+ * orc_test_project_halfspaces applies the rows of Alin (rows x n, column-major) s <= blin one after another in place and
+ * returns how many rows were violated. */
+int orc_test_project_soc(double *sv, int n, double mu);
+int orc_test_project_halfspaces(double *sv, int n, int rows, const double *Alin, const double *blin);
 
 #ifdef __cplusplus
 }
