@@ -345,8 +345,18 @@ static bool lean_trim_applies() {
     const char *env = getenv("TINYMPC_LEAN_TRIM");
     return lean_start_applies() && (!env || atoi(env) != 0);
 }
+// ... with d and the slack sharing the register slots inside a run of lean rounds (tinympc_lshare_d.hip; bit-identical again).
+// TINYMPC_LEAN_SHARE=0 selects the kernels of tinympc_ltrim_d.hip.
+static bool lean_share_applies() {
+    const char *env = getenv("TINYMPC_LEAN_SHARE");
+    return lean_trim_applies() && (!env || atoi(env) != 0);
+}
 static const char *lean_words(const tinympc_solver *s, const LaunchPlan &pl) {
-    return !lean_applies(s, pl) ? "" : lean_trim_applies() ? " lean lds-start trim" : lean_start_applies() ? " lean lds-start" : " lean";
+    return !lean_applies(s, pl)   ? ""
+           : lean_share_applies() ? " lean lds-start trim share"
+           : lean_trim_applies()  ? " lean lds-start trim"
+           : lean_start_applies() ? " lean lds-start"
+                                  : " lean";
 }
 
 int launch(tinympc_solver *s, bool timed) {
@@ -485,7 +495,8 @@ int launch(tinympc_solver *s, bool timed) {
             break;
         case KernelId::D_COMPILED:
             if (lean_applies(s, pl) && !p.x0_mirror && !p.u0_host && !p.refill_next)
-                HIP_TRY(lean_trim_applies()    ? launch_solve_d_lean_trim(p, s->stream)
+                HIP_TRY(lean_share_applies()   ? launch_solve_d_lean_share(p, s->stream)
+                        : lean_trim_applies()  ? launch_solve_d_lean_trim(p, s->stream)
                         : lean_start_applies() ? launch_solve_d_lean_start(p, s->stream)
                                                : launch_solve_d_lean(p, s->stream));
             else HIP_TRY(s->W == 64 ? launch_solve_dx(p, s->stream) : s->W == 32 ? launch_solve_dw(p, s->stream) : launch_solve_d(p, s->stream));

@@ -127,6 +127,37 @@
 #else
 #define TINY_TRIM_DSTORE 0
 #endif
+// ... and the trimmed kernels have a textual variant once more (TINY_LEAN_SHARE: tinympc_lshare_d.hip sets it with the three above; new
+// symbols k_admm_solve_d_lean_share, k_admm_solve_d_gbnd_lean_share, launch_solve_d_lean_share). In a lean round the two values a slot
+// stores are never alive together: d_s lives from backward step s to forward step s of the NEXT round, the slack v_s from forward step s
+// (which writes it; a lean step does not read the old one) to the tail of backward step s+2 (t = v - g). A backward step leaves d_s on
+// the input lanes of its accumulator [p_s | d_s], the lanes the forward chain's input columns read. So for the NVR slots whose slack is a
+// register, that register holds a_s and v_s in turn:
+//   backward  the block of a register slot accumulates in Vr[s-VL] itself -- the previous block's tail writes the start value there, two
+//             blocks after the tail that consumed v_s --, the next block reads its state operand from it, and d_s is not stored;
+//   forward   the step of a register slot takes Vr[q-VL] as its d operand and writes the clamp into it behind the chain's last read
+//             (fwd_reg_start's text, one register for both operands); no d read is issued for it.
+//   waits     the backward blocks of the register slots down to VL+3 (constant tables) have no LDS instruction around them and would need
+//             no s_waitcnt. A form without it was built and is NOT in: between two asm statements with nothing in between the compiler
+//             puts an `s_nop 0` of its own (one wait state between an asm statement's results and the next one's operands), so the block
+//             trades its wait for a nop, and the A/B could not tell the two builds apart (docs/NOTEBOOK.md section 18).
+// A run of n lean rounds is: load d_s of the register slots from LDS into Vr[] (the old slack is dead: the first forward sweep overwrites
+// it unread, and the control block in front of the run has done every pending write-back); n-1 shared rounds; one round with the
+// shared forward and the trimmed kernels' backward sweep (scratch accumulator, every d_s stored through the dstore addresses, Vr[]
+// untouched), after which Vr[] is the slack and LDS holds all of d, as the iteration with residuals and the final write-back expect.
+// Instances that are not live: inside a run their lanes' Vr[] change (they hold what a zombie's backward sweep computed), where the
+// trimmed kernels kept re-reading the frozen d from LDS. Nothing reads those registers: a zombie's state was written back by the control
+// block in front of the run (pending is false inside it, `active` is fixed for it), the stale copy and the dual residual are taken only
+// in iterations with residuals and only for live instances, and the final write-back stores live or pending instances only. Their d in
+// LDS is never written: the last round's stores go through aDw like every lean round's. The arithmetic of a live instance keeps every
+// instruction, its operands' values and its order (one exception on a dead value: with VL = 0 the tail of backward block 1 forms its
+// "any finite t" from rhom instead of v_0, whose register is the block's output).
+#ifndef TINY_LEAN_SHARE
+#define TINY_LEAN_SHARE 0
+#endif
+#if TINY_LEAN_SHARE && !(TINY_LEAN_TRIM && TINY_TRIM_DSTORE)
+#error "TINY_LEAN_SHARE: a variant of the trimmed lean kernels (with their dstore addresses)"
+#endif
 
 #define TINY_STR2(x) #x
 #define TINY_STR(x) TINY_STR2(x)
@@ -659,6 +690,11 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
         // (2: the control of a run of lean rounds alone -- write-back of what the last iteration with residuals left pending, then
         // "is anything still iterating"; the lean rounds proper, 1, have neither)
         constexpr bool LEANI = decltype(LEAN_)::value != 0, CTL_ONLY = decltype(LEAN_)::value == 2, NO_CTL = LEANI && !CTL_ONLY;
+#if TINY_LEAN_SHARE
+        // (3: the shared round -- forward AND backward sweep on the shared registers; 4: the last round of a run -- the shared forward
+        // sweep with the unshared backward sweep; see TINY_LEAN_SHARE at the top of the file. The unshared lean round, 1, is not used.)
+        constexpr bool SH_F = decltype(LEAN_)::value >= 3, SH_B = decltype(LEAN_)::value == 3;
+#endif
 #else
         constexpr bool LEANI = decltype(LEAN_)::value;
 #endif
@@ -905,7 +941,13 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
         // LDS operands of a step (its d, and vold of its slot if that lives in LDS) are requested right before the
         // PREVIOUS step's block and retired by the wait behind that block (lds_reads_landed, inside the Step functions).
         double xcur = x0v;
+#if TINY_LEAN_SHARE
+        // (a shared step of a register slot has its d in the slot's register: no read is issued for it)
+        double dcur = 0.0, vcur = 0.0;
+        if constexpr (!(SH_F && VL == 0)) dcur = lds_read_async<0>(aD);
+#else
         double dcur = lds_read_async<0>(aD), vcur = 0.0;
+#endif
 #if TINY_LEAN
         // (a lean step does not read vold: the read is not issued -- an issued asynchronous read must be consumed behind its wait)
         if constexpr (VL > 0 && !LEANI) vcur = lds_read_async<0>(aV);
@@ -925,7 +967,11 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
         auto fstep = [&](auto S) {
             constexpr int q = decltype(S)::value;
             double dn = 0.0, vn = 0.0, lon = lo_c, hin = hi_c;
+#if TINY_LEAN_SHARE
+            if constexpr (q + 1 < NS && !(SH_F && q + 1 >= VL)) dn = lds_read_async<(q + 1) * DS * 8>(aD);
+#else
             if constexpr (q + 1 < NS) dn = lds_read_async<(q + 1) * DS * 8>(aD);
+#endif
 #if TINY_LEAN
             if constexpr (q + 1 < VL && !LEANI) vn = lds_read_async<(q + 1) * 512>(aV);
 #else
@@ -946,6 +992,12 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
 #if TINY_LEAN
             if constexpr (LEANI) {  // S1 + D1 without R1's maxima: the clamp goes straight into the slot
                 if constexpr (q >= VL) {
+#if TINY_LEAN_SHARE
+                    // (shared: the slot's register is the d operand and takes the clamp behind the chain's last read of it)
+                    if constexpr (SH_F && K0 && q == 0) xcur = Step::fwd_reg0_nores(Vr[q - VL], m, c0, locur, hicur, G[q], Vr[q - VL]);
+                    else if constexpr (SH_F) xcur = Step::fwd_reg_start(xcur, Vr[q - VL], m, acur, locur, hicur, G[q], Vr[q - VL]);
+                    else
+#endif
                     if constexpr (K0 && q == 0) xcur = Step::fwd_reg0_nores(dcur, m, c0, locur, hicur, G[q], Vr[q - VL]);
 #if TINY_LDS_START
                     else xcur = Step::fwd_reg_start(xcur, dcur, m, acur, locur, hicur, G[q], Vr[q - VL]);
@@ -1138,6 +1190,28 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
                 const double lrmc2 = is_x ? lr2 + cb : cb;
                 const double v1 = vget(std::integral_constant<int, NS - 1>{}), v2 = vget(std::integral_constant<int, NS - 2>{});
                 double t;
+#if TINY_LEAN_SHARE
+                // (shared: the start value of block NS-1 goes into the register v_{NS-1} was just read from; the same instructions)
+                static_assert(NVR >= 3, "the first three slots of the backward sweep are register slots");
+                if constexpr (SH_B && FOLD) {
+                    asm("v_add_f64 %[t], %[acc], -%[g1]\n\t"
+                        "v_fma_f64 %[px], %[sc], %[t], %[lrT]\n\t"
+                        "v_add_f64 %[rn], %[v2], -%[g2]\n\t"
+                        "v_fma_f64 %[acc], %[rhom], %[rn], %[lrmc]"
+                        : [t] "=&v"(t), [px] "=&v"(px), [acc] "+v"(Vr[NS - 1 - VL]), [rn] "=&v"(rnext)
+                        : [g1] "v"(G[NS - 1]), [v2] "v"(v2), [g2] "v"(G[NS - 2]), [sc] "v"(is_x ? nrho : 1.0),
+                          [lrT] "v"(is_x ? pnref : 0.0), [rhom] "v"(rhom), [lrmc] "v"(lrmc_f));
+                } else if constexpr (SH_B) {
+                    asm("v_add_f64 %[t], %[acc], -%[g1]\n\t"
+                        "v_fma_f64 %[px], %[nrho], %[t], %[lrT]\n\t"
+                        "v_add_f64 %[t], %[v2], -%[g2]\n\t"
+                        "v_fma_f64 %[acc], %[rhom], %[t], %[lrmc]\n\t"
+                        "v_fma_f64 %[rn], %[nrho], %[t], %[lr]"
+                        : [t] "=&v"(t), [px] "=&v"(px), [acc] "+v"(Vr[NS - 1 - VL]), [rn] "=&v"(rnext)
+                        : [g1] "v"(G[NS - 1]), [v2] "v"(v2), [g2] "v"(G[NS - 2]), [nrho] "s"(nrho), [lrT] "v"(lrT),
+                          [rhom] "v"(rhom), [lrmc] "v"(lrmc2), [lr] "v"(lr2));
+                } else
+#endif
                 if constexpr (ADAPT) {  // (rho is a lane variable here: vector operand)
                     asm("v_add_f64 %[t], %[v1], -%[g1]\n\t"
                         "v_fma_f64 %[px], %[nrho], %[t], %[lrT]\n\t"
@@ -1195,6 +1269,28 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
                 if constexpr (s >= 2) v2n = vreq(std::integral_constant<int, s3>{});
                 const double lr2 = lr_of(std::integral_constant<int, s2>{});
                 const double lrmc2 = is_x ? lr2 + cb : cb;
+#if TINY_LEAN_SHARE
+                if constexpr (SH_B && s >= VL) {
+                    // The shared block of a register slot: Vr[s-VL] holds the start value (its v_s was consumed two blocks ago) and
+                    // becomes [p_s | d_s]; the tail's start value for block s-1 goes into that slot's register where it has one. No d
+                    // store. (The blocks down to VL+3 issue no LDS instruction and keep their wait all the same: see the top of the file.)
+                    constexpr bool AN_REG = s - 1 >= VL;
+                    double &an_s = Vr[AN_REG ? s - 1 - VL : 0];
+                    double an_l, rn;
+                    // (s = 1 with a register slot 0: v2cur is v_0, whose register is this block's `an`; any finite t will do)
+                    const double v2op = (s == 1 && AN_REG) ? rhom : v2cur;
+                    if constexpr (FOLD && AN_REG) Step::bwd_fold(Vr[s - VL], px, rcur, m, v2op, G[s2], rhom, lrmc_f, an_s, rn);
+                    else if constexpr (FOLD) Step::bwd_fold(Vr[s - VL], px, rcur, m, v2op, G[s2], rhom, lrmc_f, an_l, rn);
+                    else if constexpr (AN_REG) Step::bwd(Vr[s - VL], px, rcur, m, v2op, G[s2], rhom, lrmc2, nrho, lr2, an_s, rn);
+                    else Step::bwd(Vr[s - VL], px, rcur, m, v2op, G[s2], rhom, lrmc2, nrho, lr2, an_l, rn);
+                    if constexpr (!AN_REG) acc = an_l;
+                    px = Vr[s - VL];
+                    rcur = rnext;
+                    rnext = rn;
+                    v2cur = v2n;
+                    return;
+                }
+#endif
                 double a = acc, an, rn;
                 if constexpr (ADAPT) Step::bwd_v(a, px, rcur, m, v2cur, G[s2], rhom_lin, lrmc2, nrho_lin, lr2, an, rn);
                 else if constexpr (FOLD) Step::bwd_fold(a, px, rcur, m, v2cur, G[s2], rhom, lrmc_f, an, rn);
@@ -1211,6 +1307,10 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
                 acc = an;
                 v2cur = v2n;
             });
+#if TINY_LEAN_SHARE
+            if constexpr (SH_B && VL == 0) Step::bwd_last(Vr[0], px, rcur, m);  // (slot 0 is a register slot: d_0 stays in it)
+            else
+#endif
             {
                 double a = acc;
                 Step::bwd_last(a, px, rcur, m);
@@ -1253,7 +1353,21 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
                 aDw = (is_u && active) ? aD : dump;
             }
 #endif
+#if TINY_LEAN_SHARE
+            // Entry of a run: d_s of the register slots from LDS into the slots' registers (the old slack is dead, see the top of the
+            // file), once per run; then the shared rounds and, last, the round whose backward sweep puts everything back in place.
+            static_for<0, NVR>([&](auto S) { Vr[S.value] = lds_read_async<(VL + S.value) * DS * 8>(aD); });
+            lds_wait();
+            static_for<0, NVR>([&](auto S) {  // (the reads are consumed behind their wait)
+                double &vr = Vr[decltype(S)::value];
+                asm volatile("" : "+v"(vr));
+            });
+            for (; it < lean_end - 1; ++it) (void)iteration(std::integral_constant<int, 3>{}, it);
+            (void)iteration(std::integral_constant<int, 4>{}, it);
+            ++it;
+#else
             for (; it < lean_end; ++it) (void)iteration(std::true_type{}, it);
+#endif
             if (active) it_done = __builtin_amdgcn_readfirstlane(it);  // admm.cpp:143, for the whole run
         }
         if (iteration(std::false_type{}, it)) break;
@@ -1329,7 +1443,13 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
 #if TINY_LEAN
 // (the lean translation unit, tinympc_lean_d.hip: the plain kernel and its per-instance goal form with lean sweeps; tinympc_plan.hip
 // decides when -- lean_applies; tinympc_lstart_d.hip: the same under the names of its variant)
-#if TINY_LEAN_TRIM
+#if TINY_LEAN_SHARE
+#define k_admm_solve_d_lean k_admm_solve_d_lean_share
+#define k_admm_solve_d_gbnd_lean k_admm_solve_d_gbnd_lean_share
+#define launch_solve_d_lean launch_solve_d_lean_share
+// (the LDS plan is the trimmed kernels': the slack slots and every row of d keep their places, fewer instructions touch them)
+static_assert(d_vl(4, 50, true, 4) == 25, "quadrotor N=50: 25 slack slots in LDS with four wavefronts per workgroup");
+#elif TINY_LEAN_TRIM
 #define k_admm_solve_d_lean k_admm_solve_d_lean_trim
 #define k_admm_solve_d_gbnd_lean k_admm_solve_d_gbnd_lean_trim
 #define launch_solve_d_lean launch_solve_d_lean_trim

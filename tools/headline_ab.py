@@ -52,7 +52,7 @@ if __name__ == "__main__":
             out = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "--batch", str(a.batch)], env=env, capture_output=True, text=True)
             if out.returncode != 0:
                 print(n, "FAILED", out.stderr[-400:], flush=True)
-                continue
+                sys.exit(1)  # (nothing more is started on a GPU after a child that did not end well)
             d = json.loads(out.stdout.strip().splitlines()[-1])
             res[n].append(d["median"])
             print(f"round {r} {n:12s} median {d['median']:.4f} ms  min {d['min']:.4f}  mean {d['mean']:.4f}", flush=True)

@@ -15,7 +15,10 @@ tinympc_lstart_d.hip: what the headline runs now) has the third, RECORD_LEAN_STA
     python tools/headline_code_hash.py --record-lean-start   write RECORD_LEAN_START (after the A/B)
 The lean-start kernel with the d stores of its lean rounds going through a per-lane address instead of a narrowed EXEC
 (k_admm_solve_d_lean_trim<12, 4, 50, true, 4, 25>, tinympc_ltrim_d.hip: what the headline runs now) has the fourth, RECORD_LEAN_TRIM.
-    python tools/headline_code_hash.py --record-lean-trim    write RECORD_LEAN_TRIM (after the A/B)"""
+    python tools/headline_code_hash.py --record-lean-trim    write RECORD_LEAN_TRIM (after the A/B)
+The trimmed kernel with d and the slack sharing the register slots inside a run of lean rounds (k_admm_solve_d_lean_share<12, 4, 50, true, 4, 25>,
+tinympc_lshare_d.hip: what the headline runs now) has the fifth, RECORD_LEAN_SHARE.
+    python tools/headline_code_hash.py --record-lean-share   write RECORD_LEAN_SHARE (after the A/B)"""
 import hashlib
 import json
 import os
@@ -52,6 +55,14 @@ LEAN_TRIM_MEASURED = ("kernel 1.384 ms avg (8,192 x 200 iterations, bench.py on 
                       "the parent build's lean-start kernel (7,152 instructions, headline_kernel_code_d_lean_start.json): 1.3822 vs 1.3991 ms (-1.2 %), and 1.3791 vs "
                       "1.3945 ms at TINY_D_PAD=1, four interleaved rounds each, ranges disjoint; 4.0 M against 43.9 M scalar and 763.7 M against 764.5 M VALU "
                       "instructions per launch; profiles/d_lean_trim_headline_ab.txt")
+KERNEL_LEAN_SHARE = "_ZN7tinympc25k_admm_solve_d_lean_shareILi12ELi4ELi50ELb1ELi4ELi25EEEvNS_11SolveParamsE"
+SOURCE_LEAN_SHARE = "tinympc_lshare_d.hip"
+RECORD_LEAN_SHARE = os.path.join(ROOT, "tests", "golden", "headline_kernel_code_d_lean_share.json")
+# what was measured for its recorded code (profiles/d_lean_share_headline_ab.txt)
+LEAN_SHARE_MEASURED = ("kernel 1.375 ms avg (8,192 x 200 iterations, bench.py on MI355X; profiles/d_lean_share_kernel_stats.csv); tools/headline_ab.py, one box, against "
+                       "the parent build's trimmed kernel (7,091 instructions, headline_kernel_code_d_lean_trim.json): 1.3689 vs 1.3844 ms (-1.1 %), and 1.3707 vs "
+                       "1.3888 ms at TINY_D_PAD=1, four interleaved rounds each, ranges disjoint; 68.0 M against 87.5 M LDS and 763.7 M against 763.7 M VALU "
+                       "instructions per launch; profiles/d_lean_share_headline_ab.txt")
 
 
 def compiler_version() -> str:
@@ -98,6 +109,9 @@ if __name__ == "__main__":
     trim = current_hash(KERNEL_LEAN_TRIM, SOURCE_LEAN_TRIM)
     if trim is not None:
         print(json.dumps(trim, indent=1))
+    share = current_hash(KERNEL_LEAN_SHARE, SOURCE_LEAN_SHARE)
+    if share is not None:
+        print(json.dumps(share, indent=1))
     if "--record" in sys.argv:
         h["measured"] = ("kernel 1.647 ms avg (8,192 x 200 iterations, bench.py on MI355X; profiles/d_fold_kernel_stats.csv); tools/headline_ab.py, one box, "
                          "against the build before knot 0 and the backward tail were folded (4,257 instructions): 1.6350 vs 1.6733 ms (-2.3 %), and "
@@ -130,3 +144,11 @@ if __name__ == "__main__":
             json.dump(trim, f, indent=1)
             f.write("\n")
         print("recorded", RECORD_LEAN_TRIM)
+    if "--record-lean-share" in sys.argv:
+        if share is None:
+            sys.exit("no assembly of the shared lean kernel: run __graft_entry__.build() first")
+        share["measured"] = LEAN_SHARE_MEASURED
+        with open(RECORD_LEAN_SHARE, "w") as f:
+            json.dump(share, f, indent=1)
+            f.write("\n")
+        print("recorded", RECORD_LEAN_SHARE)
