@@ -309,9 +309,16 @@ int tinympc_set_bound_constraints_batch_device(tinympc_solver *s, const double *
  * included: replacing the rows between two warm-started ticks is the intended use (obstacle half-spaces re-linearised every tick).
  * tinympc_set_linear_constraints returns every instance to shared rows. reset_workspace, update_settings, the reference, track and
  * bound verbs (shared and per instance), set_cone_constraints, the solve verbs and mpc_step_batch keep mode and rows.
- * The mode runs on layout A (tinympc_get_layout 'A', " per-instance-linear" in tinympc_get_jit_info; tinympc_prepare has nothing to
- * specialise), with shared cones, fdyn, per-instance references (goals, trajectories, tracks) and per-instance bounds (box or per knot)
- * in any combination: its kernel always reads the reference and clamp rows per instance. With per-instance models or rho, adaptive
+ * The mode runs on layout A (tinympc_get_layout 'A', " per-instance-linear" in tinympc_get_jit_info) unless tinympc_prepare was
+ * called on the handle (before or after this verb): then batches that run the register-resident throughput kernel (layout D) keep it
+ * -- every wavefront holds its four instances' rows -- where nx+nu <= 16, references and bounds are constant over the horizon (shared
+ * or per instance), no two cones share a row and the horizon and row count fit that kernel's plan (N <= 22); the kernel is compiled in
+ * for the quadrotor at N = 20 with one row, specialised at run time otherwise. Trajectories, tracks, per-knot bounds, wider systems,
+ * longer horizons and a refused specialisation (tinympc_get_jit_info then reads "refused(<reason>) per-instance-linear") stay on
+ * layout A, and a handle moves between the two from one launch to the next as its configuration changes; the ADMM state, the family's
+ * duals included, is shared, so a warm start carries over. Either way the mode takes shared cones, fdyn, per-instance references
+ * (goals, trajectories, tracks) and per-instance bounds (box or per knot)
+ * in any combination: its kernels always read the reference and clamp rows per instance. With per-instance models or rho, adaptive
  * rho, nx+nu > 64 or more cones / rounds than the generic kernels hold a solve returns TINYMPC_ERR_UNSUPPORTED (never a solve with
  * shared rows), and so does tinympc_session_begin. Outside the mode, per-instance references or bounds together with a family stay
  * refused. Invalid arguments -- a row of A that is all zero or not finite, a b that is NaN or -inf, a NULL pointer for a non-empty side,
@@ -503,7 +510,9 @@ int tinympc_get_jit_info(tinympc_solver *s, char *buf, int len);
  * a single instance / small batch of a shape that is not compiled in then runs on the structure-specialised latency kernel (layout
  * F: 5-25 % fewer microseconds per iteration than the generic latency kernel, resident session included) instead of staying on the
  * generic one, which needs no compiler; and a batch with per-instance models (tinympc_set_model_batch, in either order) runs on layout
- * D's per-instance model form where one exists instead of layout A. No reference counterpart (the reference has one code path). */
+ * D's per-instance model form where one exists instead of layout A, and a batch with per-instance linear rows
+ * (tinympc_set_linear_constraints_batch, in either order) on layout D's per-instance linear-row form likewise. No reference
+ * counterpart (the reference has one code path). */
 int tinympc_prepare(tinympc_solver *s);
 
 /* The HIP stream of the handle as an opaque pointer (hipStream_t). */

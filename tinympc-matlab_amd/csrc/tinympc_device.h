@@ -443,7 +443,7 @@ bool solve_e_supported(int nx, int nu, int N, bool const_tables, bool families, 
 hipError_t launch_solve_e(const SolveParams &p, const FamilyStructure &fs, hipStream_t stream);
 void solve_e_describe(int nx, int nu, int N, bool const_tables, bool families, const FamilyStructure &fs, char *buf, size_t len);
 void solve_jit_describe(int W, int nx, int nu, int N, bool const_tables, bool families, bool adaptive, char *buf, size_t len, bool goal = false,
-                        bool models = false);
+                        bool models = false, int ilin = 0);
 // Layout F (tinympc_solve_f.hip, run-time specialised only): the latency kernel with compile-time shape and structure
 bool solve_f_plan(int nx, int nu, int N, bool const_tables, bool families, const FamilyStructure &fs, int *chunk_len, int *chunks, int *wpg, size_t *lds_bytes);
 bool solve_f_supported(int nx, int nu, int N, bool const_tables, bool families, const FamilyStructure &fs);  // plans AND compiles
@@ -581,15 +581,17 @@ hipError_t launch_solve_m(const SolveParams &p, hipStream_t stream);
 // goal: the per-instance goal form (-DTINY_JIT_IGOAL=1; constant tables, box path)
 // models: the per-instance model form (-DTINY_JIT_IMOD=1: the goal form with every instance's own operator block, SolveParams::ops
 // [batch][ops_doubles(W, KT)], staged per wavefront; 16 lanes, constant tables, box path). With TINYMPC_JIT=0 only a compiled-in one.
+// ilin: the per-instance linear-row form (-DTINY_JIT_ILIN=<nl> with families and goal: the families' variant reading every instance's own
+// rows, SolveParams::ilin, staged per wavefront; 16 lanes, constant tables; 0: off). With TINYMPC_JIT=0 only a compiled-in one.
 bool solve_jit_supported(int W, int nx, int nu, int N, bool const_tables, bool families = false, bool adaptive = false, bool goal = false,
-                         bool models = false);
-hipError_t launch_solve_jit(const SolveParams &p, int W, hipStream_t stream, bool models = false);
+                         bool models = false, int ilin = 0);
+hipError_t launch_solve_jit(const SolveParams &p, int W, hipStream_t stream, bool models = false, int ilin = 0);
 bool solve_jit_refill_supported(int W, int nx, int nu, int N, bool const_tables);   // (compiles the slot-refill variant on first use)
 int solve_jit_resident_wavefronts(int W, int nx, int nu, int N, bool const_tables);  // wavefronts of the shape's plan the device holds at once
 int solve_jit_workgroups(int W, int nx, int nu, int N, bool const_tables, int groups, bool families = false, bool adaptive = false, bool goal = false,
-                         bool models = false);
+                         bool models = false, int ilin = 0);
 size_t solve_jit_lds_bytes(int W, int nx, int nu, int N, bool const_tables, bool families = false, bool adaptive = false, bool goal = false,
-                           bool models = false);  // per workgroup, from the plan  // 8 wavefronts per workgroup, 4 on the long-horizon plan
+                           bool models = false, int ilin = 0);  // per workgroup, from the plan  // 8 wavefronts per workgroup, 4 on the long-horizon plan
 #endif  // !__HIPCC_RTC__
 
 // Doubles of working state per group in layout A (G and V with N+2 rows, D with 64 dummy slots).

@@ -107,9 +107,14 @@ struct InstState {
     // instance: lrows is the store the kernel reads, SolveParams::ilin, [group][3 lin_nl][64] with lin_nl = max(lin_nlx, lin_nlu)
     // (k_build_inst_lin; instances the verb never named hold the shared rows of the moment the mode began). Nothing else is kept: the
     // store IS the rows, written inside the call. The mode runs on layout A's InstFamilies variant, always with the per-instance
-    // reference and clamp rows.
+    // reference and clamp rows -- or, once the caller has asked for specialised kernels (tinympc_prepare), references and bounds are
+    // constant over the horizon and the cones are ones layout D's families kernel takes, on layout D's ILIN form (lin_wants_d).
     bool lin = false;
     int lin_nlx = 0, lin_nlu = 0, lin_nl = 0;
+    // layout D's per-instance linear-row form (16 lanes; compiled in or run-time specialised on the shape AND lin_nl): -1 not asked yet,
+    // 0 no, 1 yes -- the answer for d_lin_nl rows; another count (a whole-batch call) makes it unknown again (resolve_plan). The cones are
+    // no part of the specialisation: whether their structure is one the form takes is asked at every launch (lin_wants_d).
+    int d_lin = -1, d_lin_nl = 0;
     double *lrows = nullptr;
     size_t lrows_cap = 0;                    // doubles lrows was allocated for
     double *lstage = nullptr;                // device staging of host input (the shared rows of a sub-range first call: a block of their own, freed in the call)
@@ -363,7 +368,7 @@ struct LaunchPlan {
     bool inst_refs = false;                  // ... per-instance references (layout A's InstRefs variant) or bounds (see inst_bounds)
     bool inst_bounds = false;                // ... per-instance bounds (layout A's InstBounds variant)
     bool inst_models = false;                // ... per-instance models (layout A's InstModels variant; inst_refs and inst_bounds are set with it)
-    bool inst_lin = false;                   // ... per-instance linear rows (layout A's InstFamilies variant; inst_refs and inst_bounds are set with it)
+    bool inst_lin = false;                   // ... per-instance linear rows (layout A's InstFamilies variant, or layout D's ILIN form: D_JIT; inst_refs and inst_bounds are set with it)
     bool jit = false;                        // a run-time specialisation (tinympc_jit.hip) rather than a compiled-in kernel
     bool host_exchange = false;              // the kernel serves the pinned-host paths (x0 in, solution / completion stamp out)
     int workgroups = 0;

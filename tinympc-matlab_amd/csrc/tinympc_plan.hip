@@ -161,11 +161,19 @@ bool models_want_d(const tinympc_solver *s) {
            !s->st.adaptive_rho;
 }
 
-// Per-instance linear rows (tinympc_set_linear_constraints_batch): ONE kernel, layout A's InstFamilies variant. What it cannot carry is
-// refused at the launch (lin_refusal), never solved with shared rows.
+// Per-instance linear rows (tinympc_set_linear_constraints_batch): layout A's InstFamilies variant, or layout D's ILIN form (below). What
+// neither can carry is refused at the launch (lin_refusal), never solved with shared rows.
 bool lin_runs(const tinympc_solver *s) {
     return s->inst.lin && !s->layout_m && !s->inst.models && !s->st.adaptive_rho && !family_structure(s).beyond_generic();
 }
+// ... on layout D: opt-in like the models' form (tinympc_prepare -- without it the mode stays on layout A, which needs no specialisation),
+// where the handle runs layout D, 16 lanes per instance, references and bounds constant over the horizon (shared or per instance: no
+// trajectories, tracks or per-knot bounds), and a cone structure layout D's shared families kernel takes (decide_layout_d_variants: no
+// rounds of overlapping cones). Whether the kernel exists for the mode's row count is inst.d_lin (resolve_plan).
+bool lin_wants_d(const tinympc_solver *s) {
+    return lin_runs(s) && s->specialise_asked && s->layout_d && s->W == 16 && s->iref_goal() && family_structure(s).nround <= 1;
+}
+bool lin_on_d(const tinympc_solver *s) { return lin_wants_d(s) && s->inst.d_lin == 1 && s->inst.d_lin_nl == s->inst.lin_nl; }
 
 }  // namespace
 
@@ -181,7 +189,9 @@ namespace host {
 //   per-instance models                D's model form (only after tinympc_prepare: 16 lanes, references and bounds constant over the horizon,
 //                                      a horizon its per-wavefront operator plan holds)  >  A (the same refusals)
 //                                      (the mode of tinympc_set_model_batch AND tinympc_set_rho_batch: one form, rho always read per instance)
-//   per-instance linear rows           A's InstFamilies variant, whatever else is per instance (references, bounds) or shared (cones); with
+//   per-instance linear rows           D's ILIN form (only after tinympc_prepare: 16 lanes, references and bounds constant over the horizon, cones
+//                                      without rounds, a horizon and row count its per-wavefront plan holds)  >  A's InstFamilies variant,
+//                                      whatever else is per instance (references, bounds) or shared (cones); with
 //                                      per-instance models / rho, adaptive rho, layout M or a cone structure beyond the generic kernels, launch() refuses
 LaunchPlan current_plan(const tinympc_solver *s) {
     LaunchPlan pl;
@@ -189,8 +199,8 @@ LaunchPlan current_plan(const tinympc_solver *s) {
     pl.families = fam;
     pl.adaptive = adaptive;
     if (lin_runs(s)) {
-        pl.kernel = KernelId::A;
-        pl.inst_lin = pl.inst_refs = pl.inst_bounds = true;  // (the variant always runs on per-instance reference and clamp rows)
+        pl.kernel = lin_on_d(s) ? KernelId::D_JIT : KernelId::A;
+        pl.inst_lin = pl.inst_refs = pl.inst_bounds = true;  // (both kernels always run on per-instance reference and clamp rows)
     } else if (s->inst_tables() && !s->inst.lin && !s->layout_m && !fam && !adaptive) {
         // goals, where the handle runs layout D: its constant-table kernel (compiled in for the 16-lane shapes that are, run-time
         // specialised otherwise -- wide systems included); trajectories, and goals without such a kernel: layout A. "Goal" means that
@@ -220,12 +230,14 @@ LaunchPlan current_plan(const tinympc_solver *s) {
             pl.workgroups = s->groups;
             pl.lds_bytes = 0;  // (static LDS: see the kernel)
             break;
-        case KernelId::D_JIT:
+        case KernelId::D_JIT: {
             pl.layout = 'D';
             pl.jit = true;
-            pl.workgroups = solve_jit_workgroups(s->W, s->nx, s->nu, s->N, ct, s->groups, fam, adaptive, pl.inst_refs, pl.inst_models);
-            pl.lds_bytes = solve_jit_lds_bytes(s->W, s->nx, s->nu, s->N, ct, fam, adaptive, pl.inst_refs, pl.inst_models);
+            const int ilin = pl.inst_lin ? s->inst.lin_nl : 0;  // (the ILIN form: the families' kernel whichever sides are enabled)
+            pl.workgroups = solve_jit_workgroups(s->W, s->nx, s->nu, s->N, ct, s->groups, fam || ilin, adaptive, pl.inst_refs, pl.inst_models, ilin);
+            pl.lds_bytes = solve_jit_lds_bytes(s->W, s->nx, s->nu, s->N, ct, fam || ilin, adaptive, pl.inst_refs, pl.inst_models, ilin);
             break;
+        }
         case KernelId::D_COMPILED:
             pl.layout = 'D';
             pl.host_exchange = s->W == 16 && !pl.inst_refs;  // (the compiled-in 16-lane shapes have a variant that reads x0 from / writes the first controls to pinned host memory)
@@ -282,6 +294,13 @@ int resolve_plan(tinympc_solver *s) {
         // ... and the model form's (compiled in for the quadrotor N=50, specialised now otherwise; a refusal leaves the mode on layout A)
         if (s->inst.d_models < 0 && models_want_d(s))
             s->inst.d_models = solve_jit_supported(s->W, s->nx, s->nu, s->N, true, false, false, false, true) ? 1 : 0;
+        // ... and the linear-row form's, for the mode's row count (compiled in for the quadrotor N=20 with one row, specialised now
+        // otherwise; a refusal leaves the mode on layout A). Another count is another specialisation: asked again.
+        if (s->inst.lin && s->inst.d_lin_nl != s->inst.lin_nl) s->inst.d_lin = -1;
+        if (s->inst.d_lin < 0 && lin_wants_d(s)) {
+            s->inst.d_lin_nl = s->inst.lin_nl;
+            s->inst.d_lin = solve_jit_supported(s->W, s->nx, s->nu, s->N, true, true, false, true, false, s->inst.lin_nl) ? 1 : 0;
+        }
         return TINYMPC_OK;
     }
     decide_layout_d_variants(s);
@@ -491,7 +510,7 @@ int launch(tinympc_solver *s, bool timed) {
             HIP_TRY(launch_solve_m(p, s->stream));
             break;
         case KernelId::D_JIT:  // (box path, families with everything in registers, or adaptive rho per lane)
-            HIP_TRY(launch_solve_jit(p, s->W, s->stream, pl.inst_models));
+            HIP_TRY(launch_solve_jit(p, s->W, s->stream, pl.inst_models, pl.inst_lin ? s->inst.lin_nl : 0));
             break;
         case KernelId::D_COMPILED:
             if (lean_applies(s, pl) && !p.x0_mirror && !p.u0_host && !p.refill_next)
@@ -588,9 +607,14 @@ static int jit_info_text(tinympc_solver *s, char *buf, int len) {
         const char *words = w.c_str();
         if (pl.kernel == KernelId::D_JIT) {
             if ((rc = bind_device(s))) return rc;
-            solve_jit_describe(s->W, s->nx, s->nu, s->N, true, false, false, buf, (size_t)len, true, pl.inst_models);
+            const int ilin = pl.inst_lin ? s->inst.lin_nl : 0;
+            solve_jit_describe(s->W, s->nx, s->nu, s->N, true, ilin != 0, false, buf, (size_t)len, true, pl.inst_models, ilin);
             strncat(buf, words, (size_t)len - strlen(buf) - 1);
             strncat(buf, " goal", (size_t)len - strlen(buf) - 1);
+        } else if (pl.inst_lin && lin_wants_d(s) && s->inst.d_lin == 0 && s->inst.d_lin_nl == s->inst.lin_nl) {  // asked for and refused: layout A, and why
+            if ((rc = bind_device(s))) return rc;
+            solve_jit_describe(s->W, s->nx, s->nu, s->N, true, true, false, buf, (size_t)len, true, false, s->inst.lin_nl);
+            strncat(buf, words, (size_t)len - strlen(buf) - 1);
         } else if (pl.inst_models && models_want_d(s) && s->inst.d_models == 0) {  // asked for and refused: layout A, and why
             if ((rc = bind_device(s))) return rc;
             solve_jit_describe(s->W, s->nx, s->nu, s->N, true, false, false, buf, (size_t)len, false, true);

@@ -230,25 +230,27 @@ constexpr int D_IMOD_STRIDE = D_OPS_DOUBLES + 16;
 constexpr int D_IMOD_WAVE_DOUBLES = 4 * D_IMOD_STRIDE;
 // number of slack slots in LDS; -1 if the shape does not fit the plan (cu_waves wavefronts per CU: 8, or 4 for the
 // long-horizon plan with one wavefront per SIMD and 512 registers)
-__host__ __device__ constexpr int d_vl(int nu, int N, bool ct, int wpg, int cu_waves = 8, bool fam = false, bool adapt = false, bool imod = false) {
+// (ilin: the row count of the per-instance linear-row form, 0 otherwise -- 3 ilin vectors of 64 doubles per WAVEFRONT in place of the
+// workgroup's D_FAM_DOUBLES)
+__host__ __device__ constexpr int d_vl(int nu, int N, bool ct, int wpg, int cu_waves = 8, bool fam = false, bool adapt = false, bool imod = false, int ilin = 0) {
     const int ns = N - 1;
-    const int wg_doubles = D_LDS_PER_CU / 8 * wpg / cu_waves - (imod ? 0 : D_OPS_DOUBLES + D_START_DOUBLES) - (ct ? 0 : d_tab_doubles(N)) - (fam ? D_FAM_DOUBLES : 0) - (adapt ? D_ADAPT_DOUBLES : 0);
+    const int wg_doubles = D_LDS_PER_CU / 8 * wpg / cu_waves - (imod ? 0 : D_OPS_DOUBLES + D_START_DOUBLES) - (ct ? 0 : d_tab_doubles(N)) - (fam && !ilin ? D_FAM_DOUBLES : 0) - (adapt ? D_ADAPT_DOUBLES : 0);
 #if TINY_TRIM_DSTORE
     const int wave_doubles = wg_doubles / wpg - d_d_doubles(nu, N) - D_DUMP_DOUBLES(nu) - (imod ? D_IMOD_WAVE_DOUBLES : 0);
 #else
-    const int wave_doubles = wg_doubles / wpg - d_d_doubles(nu, N) - (imod ? D_IMOD_WAVE_DOUBLES : 0);
+    const int wave_doubles = wg_doubles / wpg - d_d_doubles(nu, N) - (imod ? D_IMOD_WAVE_DOUBLES : 0) - 3 * ilin * 64;
 #endif
     if (wave_doubles < 0) return -1;
     const int vlmax = wave_doubles / 64;
     const int want = ns > D_VREG_MAX ? ns - D_VREG_MAX : 0;
     return want <= vlmax ? want : -1;
 }
-__host__ __device__ constexpr size_t d_lds_bytes(int nu, int N, bool ct, int wpg, int vl, bool fam = false, bool adapt = false, bool imod = false) {
-    return sizeof(double) * ((size_t)(imod ? 0 : D_OPS_DOUBLES + D_START_DOUBLES) + (ct ? 0 : d_tab_doubles(N)) + (fam ? D_FAM_DOUBLES : 0) + (adapt ? D_ADAPT_DOUBLES : 0) +
+__host__ __device__ constexpr size_t d_lds_bytes(int nu, int N, bool ct, int wpg, int vl, bool fam = false, bool adapt = false, bool imod = false, int ilin = 0) {
+    return sizeof(double) * ((size_t)(imod ? 0 : D_OPS_DOUBLES + D_START_DOUBLES) + (ct ? 0 : d_tab_doubles(N)) + (fam && !ilin ? D_FAM_DOUBLES : 0) + (adapt ? D_ADAPT_DOUBLES : 0) +
 #if TINY_TRIM_DSTORE
                              (size_t)wpg * (vl * 64 + D_DUMP_DOUBLES(nu) + d_d_doubles(nu, N) + (imod ? D_IMOD_WAVE_DOUBLES : 0)));
 #else
-                             (size_t)wpg * (vl * 64 + d_d_doubles(nu, N) + (imod ? D_IMOD_WAVE_DOUBLES : 0)));
+                             (size_t)wpg * (vl * 64 + d_d_doubles(nu, N) + (imod ? D_IMOD_WAVE_DOUBLES : 0) + 3 * ilin * 64));
 #endif
 }
 
@@ -311,6 +313,16 @@ __device__ __forceinline__ bool wave_may_converge_d(unsigned long long bad, unsi
     }
     return any != 0;
 }
+// The same test on the 32-bit halves of the two ballots (the per-instance linear-row form: the 64-bit form above compares two of its
+// rows against 64-bit constants in the VALU, which the allocator keeps in vector registers across the iteration loop -- with the
+// families' register pairs per knot they ended up in its spill slots; here every compare is a 32-bit scalar one).
+__device__ __forceinline__ bool wave_may_converge_d32(unsigned long long bad, unsigned long long live) {
+    unsigned b0 = (unsigned)bad, b1 = (unsigned)(bad >> 32), l0 = (unsigned)live, l1 = (unsigned)(live >> 32);
+    asm("" : "+s"(b0), "+s"(b1), "+s"(l0), "+s"(l1));  // (opaque halves: the optimiser otherwise folds the tests back into 64-bit compares)
+    const int any = ((int)((l0 & 0xffffu) != 0u) & (int)((b0 & 0xffffu) == 0u)) | ((int)((l0 >> 16) != 0u) & (int)((b0 >> 16) == 0u)) |
+                    ((int)((l1 & 0xffffu) != 0u) & (int)((b1 & 0xffffu) == 0u)) | ((int)((l1 >> 16) != 0u) & (int)((b1 >> 16) == 0u));
+    return any != 0;
+}
 // Branches that are almost never taken (write-back, stale copies): the compiler moves their bodies out of the sweep's
 // straight line. A TAKEN branch costs a wavefront ~110 cycles of instruction fetch (tools/microbench_fp64_step.hip, loops
 // against straight-line code), so the common path should be the fall-through.
@@ -338,7 +350,7 @@ __device__ __forceinline__ bool wave_may_converge_d(unsigned long long bad, unsi
 // arithmetic of an instance is that of the plain kernel (bit-identical results: tests/test_hip_parity.py); what changes is that
 // a wavefront's time is the sum of what its rows worked, not four times its slowest instance.
 template <int NX, int NU, int N, bool CT, int WPG, int VL, bool FAM = false, bool ADAPT = false, bool TWO_PER_SIMD = true, bool HOSTX = false,
-          bool REFILL = false, bool IGOAL = false, bool IMOD = false>
+          bool REFILL = false, bool IGOAL = false, bool IMOD = false, int ILIN = 0>
 #else
 // IGOAL: the per-instance goal form (every instance's references and bounds constant over the horizon; k_admm_solve_d_gbnd) -- the
 // four table constants lr_c, pNref, lo_c and hi_c come per lane from SolveParams::iref_lr / iref_pn / ibnd ([instance][16], ibnd's hi
@@ -346,13 +358,20 @@ template <int NX, int NU, int N, bool CT, int WPG, int VL, bool FAM = false, boo
 // IMOD: the per-instance model form (tinympc_set_model_batch; the goal form with SolveParams::ops [batch][ops_doubles(W, KT)]) -- the
 // two sweep operators a lane reads its rows from are its INSTANCE's, staged by its wavefront into the wavefront's own LDS region, and
 // cf, cb, c0 and the folded start value come from the instance's block. The per-lane arithmetic is the goal kernel's.
+// ILIN: the per-instance linear-row form of the families (tinympc_set_linear_constraints_batch after tinympc_prepare; ILIN = the mode's
+// row count nl, 0: off) -- the families' code reads a_k | b_k | 1/||a_k||^2 of the lane's own INSTANCE from SolveParams::ilin,
+// [group][3 nl][64], which every wavefront stages into an LDS region of its own; the shared sLin block does not exist. Cones, rounds,
+// role / mu and the enable flags stay those of the shared description, the four table constants come per lane as in the goal form
+// (layout A's variant of the mode always runs on per-instance reference and clamp rows). The per-element arithmetic is FAM's.
 template <int NX, int NU, int N, bool CT, int WPG, int VL, bool FAM = false, bool ADAPT = false, bool TWO_PER_SIMD = true, bool HOSTX = false,
-          bool REFILL = false, bool IGOAL = false, bool IMOD = false>
+          bool REFILL = false, bool IGOAL = false, bool IMOD = false, int ILIN = 0>
 #endif
 __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double *smem) {
     static_assert(!(FAM && ADAPT), "adaptive rho and the constraint families exclude each other (as in the C ABI)");
     static_assert(!IMOD || (IGOAL && CT && !FAM && !ADAPT && !REFILL && !HOSTX && !TINY_LEAN),
                   "per-instance models: the goal form of the box path (its rows are always built per instance), plain sweeps");
+    static_assert(ILIN == 0 || (ILIN > 0 && ILIN <= MAX_LIN_ROWS && FAM && IGOAL && CT && !ADAPT && !IMOD && !REFILL && !HOSTX && !TINY_LEAN),
+                  "per-instance linear rows: the families' variant in the goal form (references and bounds constant over the horizon), plain sweeps");
 #if TINY_REFILL
     static_assert(!REFILL || (!FAM && !ADAPT && !HOSTX), "slot refill: box-constrained path only");
 #endif
@@ -394,16 +413,17 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
     double *sT = smem + (IMOD ? 0 : D_OPS_DOUBLES);
 #endif
     double *sLin = sT + (CT ? 0 : d_tab_doubles(N));  // FAM
-    double *sAd = sLin + (FAM ? D_FAM_DOUBLES : 0);   // ADAPT: [5][16 k][16 r]
+    double *sAd = sLin + (FAM && !ILIN ? D_FAM_DOUBLES : 0);   // ADAPT: [5][16 k][16 r]
 #if TINY_TRIM_DSTORE
     static_assert(!IMOD, "the dump rows: lean kernels only");
     double *sV = sAd + (ADAPT ? D_ADAPT_DOUBLES : 0) + (size_t)wv * (VL * 64 + D_DUMP_DOUBLES(NU) + d_d_doubles(NU, N));
     double *sD = sV + VL * 64 + D_DUMP_DOUBLES(NU);  // (rows -1 and -2 of d: written by the dump lanes of the lean backward sweeps, never read)
 #else
-    double *sV = sAd + (ADAPT ? D_ADAPT_DOUBLES : 0) + (size_t)wv * (VL * 64 + d_d_doubles(NU, N) + (IMOD ? D_IMOD_WAVE_DOUBLES : 0));
+    double *sV = sAd + (ADAPT ? D_ADAPT_DOUBLES : 0) + (size_t)wv * (VL * 64 + d_d_doubles(NU, N) + (IMOD ? D_IMOD_WAVE_DOUBLES : 0) + 3 * ILIN * 64);
     double *sD = sV + VL * 64;
 #endif
     double *sOpsW = sD + d_d_doubles(NU, N);  // IMOD: [4 instances][D_IMOD_STRIDE]
+    double *sLinW = sD + d_d_doubles(NU, N);  // ILIN: [3 nl][64], this wavefront's group of SolveParams::ilin (never together with IMOD)
 
     // ---- workgroup-shared: the two sweep operators, transposed to [k][r] (conflict-free row reads), and the tables
     if constexpr (IMOD) {
@@ -438,7 +458,17 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
             sAd[i] = (k < KT) ? p.adapt[(size_t)tbl * W * KT + (size_t)rr * KT + k] : 0.0;
         }
     }
-    if constexpr (FAM) {  // layout of fam_doubles(): ... | nl | per linear row k: a_k[W] b_k[W] ||a_k||^2[W]
+    if constexpr (ILIN > 0) {
+        // ... per wavefront: the 3 nl vectors of its own group, in the kernel's lane order as k_build_inst_lin wrote them (lanes beyond the
+        // batch: a = 0, b = +inf, norm 1 -- the row is off); the third vector as its reciprocal, like the shared copy below
+        if (grp_ok) {
+            const double *const rows_g = p.ilin + (size_t)grp * (3 * ILIN * 64);
+            for (int i = lane; i < 3 * ILIN * 64; i += 64) {
+                const double v = rows_g[i];
+                sLinW[i] = ((i >> 6) % 3 == 2) ? 1.0 / v : v;  // 1 / ||a_k||^2
+            }
+        }
+    } else if constexpr (FAM) {  // layout of fam_doubles(): ... | nl | per linear row k: a_k[W] b_k[W] ||a_k||^2[W]
         const double *lin_rows = p.fam + 4 * W + (size_t)3 * W * KT;
         for (int i = threadIdx.x; i < D_FAM_DOUBLES; i += 64 * WPG) {
             const int k3 = i / W, rr = i % W;
@@ -519,7 +549,7 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
         inv_mu = (mu != 0.0) ? 1.0 / mu : 0.0;  // (mu = 0: row in no cone)
         famc = p.fam[2 * W + r] != 0.0;
         faml = p.fam[3 * W + r] != 0.0;
-        nl = (int)p.fam[4 * W + (size_t)3 * W * KT];
+        nl = ILIN ? ILIN : (int)p.fam[4 * W + (size_t)3 * W * KT];  // (ILIN: the mode's count, SolveParams::ilin_nl, a constant of the specialisation)
         any_cone = __ballot(famc) != 0ull;  // the same in every 16-lane row
         any_lin = __ballot(faml) != 0ull;
     }
@@ -534,7 +564,7 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
             // that the scheduler interleaves the three independent mat-vec chains and the two projection sequences -- a lone
             // wavefront issues a dependent FP64 instruction every ~7 cycles, an independent one every ~5.
             const double svc = val + gc_old, s0 = val + gl_old;
-            const double a_k = sLin[r], b_k = sLin[W + r], in_k = sLin[2 * W + r];
+            const double a_k = ILIN ? sLinW[lane] : sLin[r], b_k = ILIN ? sLinW[64 + lane] : sLin[W + r], in_k = ILIN ? sLinW[2 * 64 + lane] : sLin[2 * W + r];
             const double a2 = group_matvec<W, KT>(cn, svc * svc, 0.0);
             const double t = group_matvec<W, KT>(ct_, svc, 0.0);
             const double dot = group_matvec<W, KT>(ty, a_k * s0, 0.0);
@@ -567,7 +597,9 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
             double sv = s0;
 #pragma unroll 1
             for (int k = 0; k < nl; ++k) {  // (uniform trip count)
-                const double a_k = sLin[(3 * k + 0) * W + r], b_k = sLin[(3 * k + 1) * W + r], in_k = sLin[(3 * k + 2) * W + r];
+                const double a_k = ILIN ? sLinW[(3 * k + 0) * 64 + lane] : sLin[(3 * k + 0) * W + r];
+                const double b_k = ILIN ? sLinW[(3 * k + 1) * 64 + lane] : sLin[(3 * k + 1) * W + r];
+                const double in_k = ILIN ? sLinW[(3 * k + 2) * 64 + lane] : sLin[(3 * k + 2) * W + r];
                 const double dot = group_matvec<W, KT>(ty, a_k * sv, 0.0);
                 sv = halfspace_project_element(sv, dot, a_k, b_k, in_k);
             }
@@ -919,7 +951,7 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
 #if TINY_REFILL
                 may = __builtin_amdgcn_readfirstlane((int)wave_may_converge_d(__ballot(bad), __ballot(REFILL ? chk : active))) != 0;
 #else
-                may = __builtin_amdgcn_readfirstlane((int)wave_may_converge_d(__ballot(bad), __ballot(active))) != 0;
+                may = __builtin_amdgcn_readfirstlane((int)(ILIN ? wave_may_converge_d32(__ballot(bad), __ballot(active)) : wave_may_converge_d(__ballot(bad), __ballot(active)))) != 0;
 #endif
             }
 #if TINY_REFILL
@@ -1079,7 +1111,7 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
 #if TINY_REFILL
                         may = __builtin_amdgcn_readfirstlane((int)wave_may_converge_d(__ballot(bad), __ballot(REFILL ? chk : active))) != 0;
 #else
-                        may = __builtin_amdgcn_readfirstlane((int)wave_may_converge_d(__ballot(bad), __ballot(active))) != 0;
+                        may = __builtin_amdgcn_readfirstlane((int)(ILIN ? wave_may_converge_d32(__ballot(bad), __ballot(active)) : wave_may_converge_d(__ballot(bad), __ballot(active)))) != 0;
 #endif
                     }
                 }
@@ -1562,6 +1594,12 @@ __global__ void __launch_bounds__(64 * WPG) __attribute__((amdgpu_waves_per_eu(2
 #if TINY_JIT_IMOD && TINY_REFILL
 #error "per-instance models: no slot-refill variant"
 #endif
+#ifndef TINY_JIT_ILIN
+#define TINY_JIT_ILIN 0
+#endif
+#if TINY_JIT_ILIN && TINY_REFILL
+#error "per-instance linear rows: no slot-refill variant"
+#endif
 extern "C" __global__ void __launch_bounds__(64 * TINY_JIT_WPG) __attribute__((amdgpu_waves_per_eu(TINY_JIT_WPS, TINY_JIT_WPS)))
 TINY_KERNEL_NAME(const tinympc::SolveParams p) {
 #ifndef TINY_JIT_CT
@@ -1578,9 +1616,10 @@ TINY_KERNEL_NAME(const tinympc::SolveParams p) {
 #endif
     constexpr bool ADJ = TINY_JIT_ADAPT != 0;  // adaptive rho
     constexpr bool IMJ = TINY_JIT_IMOD != 0;  // per-instance models (implies the goal form)
-    constexpr int VLJ = tinympc::d_vl(TINY_JIT_NU, TINY_JIT_N, CTJ, WPGJ, 4 * TINY_JIT_WPS, FAMJ, ADJ, IMJ);
+    constexpr int ILJ = TINY_JIT_ILIN;  // per-instance linear rows: the mode's row count (with -DTINY_JIT_FAM=1 -DTINY_JIT_IGOAL=1); 0: off
+    constexpr int VLJ = tinympc::d_vl(TINY_JIT_NU, TINY_JIT_N, CTJ, WPGJ, 4 * TINY_JIT_WPS, FAMJ, ADJ, IMJ, ILJ);
     static_assert(VLJ >= 0, "shape does not fit the layout-D plan");
-    __shared__ __attribute__((aligned(16))) double smem_jit[tinympc::d_lds_bytes(TINY_JIT_NU, TINY_JIT_N, CTJ, WPGJ, VLJ, FAMJ, ADJ, IMJ) / sizeof(double)];
+    __shared__ __attribute__((aligned(16))) double smem_jit[tinympc::d_lds_bytes(TINY_JIT_NU, TINY_JIT_N, CTJ, WPGJ, VLJ, FAMJ, ADJ, IMJ, ILJ) / sizeof(double)];
 #if TINY_REFILL
 #ifndef TINY_JIT_REFILL
 #define TINY_JIT_REFILL 0
@@ -1591,7 +1630,7 @@ TINY_KERNEL_NAME(const tinympc::SolveParams p) {
 #define TINY_JIT_IGOAL 0
 #endif
     tinympc::k_admm_solve_d_body<TINY_JIT_NX, TINY_JIT_NU, TINY_JIT_N, CTJ, WPGJ, VLJ, FAMJ, ADJ, TINY_JIT_WPS == 2, false, false,
-                                 TINY_JIT_IGOAL != 0 || IMJ, IMJ>(p, smem_jit);
+                                 TINY_JIT_IGOAL != 0 || IMJ, IMJ, ILJ>(p, smem_jit);
 #endif
 }
 namespace tinympc {

@@ -721,8 +721,9 @@ class TinyMPC:
         """Choose (and, if needed, specialise) the solve kernel for the current constraints / settings now, instead of at the
         first solve that needs it (seconds the first time a shape is seen). It also says that run-time specialisation is welcome on this
         handle: a batch with per-instance models (set_model_batch, before or after this call) then runs on layout D's per-instance
-        model form -- nx+nu <= 16, references and bounds constant over the horizon, a horizon that form holds -- instead of layout A
-        (launch_info()["layout"] and jit_info() say which)."""
+        model form -- nx+nu <= 16, references and bounds constant over the horizon, a horizon that form holds -- instead of layout A,
+        and a batch with per-instance linear rows (set_linear_constraints_batch, before or after this call) on layout D's per-instance
+        linear-row form under the same conditions (launch_info()["layout"] and jit_info() say which)."""
         self._check_setup()
         self._push_settings()
         _lib.check(self._L.tinympc_prepare(self._h))

@@ -9,7 +9,19 @@ Every measurement is a fresh process; the two legs alternate, `--rounds` times e
 round's median of `--reps` launches, the legs' medians and spreads, and whether per-inst's median lies inside shared-A's spread.
 Beside the legs: the same shared-row handle on the layout it picks by default (context), and the wall time of
 set_linear_constraints_batch and of its _device form for the whole batch (first call, which allocates the store, and repeats).
-    python tools/instance_lin_sweep.py [--batch 8192] [--N 20] [--iters 100] [--rounds 4] [--reps 5]"""
+    python tools/instance_lin_sweep.py [--batch 8192] [--N 20] [--iters 100] [--rounds 4] [--reps 5]
+
+Layout D (--d --parent-lib PATH): the same workload on a handle that called prepare(), with
+  parent-A    the rows per instance on the library of the parent commit at PATH (built from a checkout of the parent): layout A's
+              k_admm_solve_ifam, where the mode ran before layout D had a form for it -- the yardstick
+  inst-D      the rows per instance on this tree's library: layout D's per-instance linear-row form
+  shared-D    the same rows shared (tinympc_set_linear_constraints) on the layout the handle picks, layout D's families kernel -- the
+              floor; context, not a condition
+  parent-A-4, inst-D-4   a second point with four state rows and four input rows (where the form's plan accepts it): what the
+              per-wavefront LDS term does to the plan
+Every measurement is a fresh process; the legs alternate, `--rounds` times each. The bar: inst-D lies below parent-A in EVERY round;
+the margin is reported against the spread of parent-A's rounds.
+    python tools/instance_lin_sweep.py --d --parent-lib /path/to/parent/libtinympc_hip.so"""
 import argparse
 import ctypes as C
 import json
@@ -24,14 +36,15 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 LEGS = ["shared-A", "per-inst"]
+D_LEGS = ["parent-A", "inst-D", "shared-D", "parent-A-4", "inst-D-4"]
 
 
-def rows(prob, batch, seed=7):
-    """One state row and one input row, the same for every instance: (Ax (1, nx), bx (1,), Au (1, nu), bu (1,)) and x0s."""
+def rows(prob, batch, seed=7, n=1):
+    """n state rows and n input rows (one each by default), the same for every instance: (Ax (n, nx), bx (n,), Au (n, nu), bu (n,))."""
     rng = np.random.default_rng(seed)
-    ax, au = rng.standard_normal((1, prob.nx)), rng.standard_normal((1, prob.nu))
-    ax, au = ax / np.linalg.norm(ax), au / np.linalg.norm(au)
-    return ax, np.array([float(ax[0] @ prob.x0) + 0.3]), au, np.array([0.2])
+    ax, au = rng.standard_normal((n, prob.nx)), rng.standard_normal((n, prob.nu))
+    ax, au = ax / np.linalg.norm(ax, axis=1, keepdims=True), au / np.linalg.norm(au, axis=1, keepdims=True)
+    return ax, ax @ prob.x0 + 0.3, au, np.full(n, 0.2)
 
 
 def make(pkg, leg, a):
@@ -50,6 +63,71 @@ def make(pkg, leg, a):
         s.set_linear_constraints(ax, bx, au, bu)
     s.set_x0_batch(pkg.problems.quadrotor_batch_x0(a.batch))
     return s
+
+
+def make_d(pkg, leg, a):
+    """The --d legs: the handle as setup makes it (layout D at this batch size), the rows per instance or shared, then prepare()."""
+    prob = pkg.problems.quadrotor(a.N)
+    os.environ.pop("TINYMPC_LAYOUT", None)
+    s = pkg.TinyMPC()
+    s.setup(prob.A, prob.B, prob.Q, prob.R, prob.N, batch=a.batch, rho=prob.rho, abs_pri_tol=0.0, abs_dua_tol=0.0, max_iter=a.iters)
+    s.set_bound_constraints(prob.x_min, prob.x_max, prob.u_min, prob.u_max)
+    ax, bx, au, bu = rows(prob, a.batch, n=4 if leg.endswith("-4") else 1)
+    if leg.startswith("shared"):
+        s.set_linear_constraints(ax, bx, au, bu)
+    else:
+        s.set_linear_constraints_batch(*(np.repeat(m[..., None], a.batch, axis=-1) for m in (ax, bx, au, bu)))
+    s.prepare()
+    s.set_x0_batch(pkg.problems.quadrotor_batch_x0(a.batch))
+    return s
+
+
+def child_d(pkg, a):
+    """One process of the --d sweep: one leg's kernel time on whatever library this process loaded. One line."""
+    s = make_d(pkg, a.child, a)
+    s.solve_timed()  # warm-up: first launch, table builds
+    out = dict(leg=a.child, kernel_ms=float(np.median([s.solve_timed() for _ in range(a.reps)])),
+               kernel="%s %s" % (s.launch_info()["layout"], s.jit_info()), lds_bytes=s.launch_info()["lds_bytes"],
+               workgroups=s.launch_info()["workgroups"])
+    s.reset()
+    print("LIN-CHILD " + json.dumps(out), flush=True)
+
+
+def sweep_d(a):
+    """Starts the children of the --d sweep (it never opens the GPU itself) and prints the table."""
+    if not a.parent_lib or not os.path.exists(a.parent_lib):
+        raise SystemExit("--d needs --parent-lib: libtinympc_hip.so built from the parent commit")
+    recs = {leg: [] for leg in D_LEGS}
+    for rnd in range(a.rounds):
+        for leg in D_LEGS if rnd % 2 == 0 else D_LEGS[::-1]:
+            env = dict(os.environ)
+            env.pop("TINYMPC_LAYOUT", None)
+            env.pop("TINYMPC_HIP_LIBRARY", None)
+            if leg.startswith("parent"):
+                env["TINYMPC_HIP_LIBRARY"] = os.path.abspath(a.parent_lib)
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--d", "--child", leg, "--batch", str(a.batch), "--N", str(a.N),
+                                "--iters", str(a.iters), "--reps", str(a.reps)], env=env, capture_output=True, text=True, timeout=300)
+            line = [l for l in r.stdout.splitlines() if l.startswith("LIN-CHILD ")]
+            if r.returncode != 0 or not line:
+                raise SystemExit("round %d (%s) failed with %d:\n%s\n%s" % (rnd, leg, r.returncode, r.stdout[-2000:], r.stderr[-2000:]))
+            recs[leg].append(json.loads(line[0][len("LIN-CHILD "):]))
+            print("# round %d %-10s %.4f ms" % (rnd, leg, recs[leg][-1]["kernel_ms"]), flush=True)
+    print("per-instance linear rows on layout D: %d quadrotors N=%d x %d forced iterations, n state rows + n input rows (n = 1; the -4 legs: "
+          "n = 4), every handle after prepare(); kernel ms (median of %d launches per round, %d rounds, a fresh process each, legs alternating)"
+          % (a.batch, a.N, a.iters, a.reps, a.rounds))
+    ms = {leg: [r["kernel_ms"] for r in recs[leg]] for leg in D_LEGS}
+    for leg in D_LEGS:
+        print("%-10s | %s | median %.4f | spread %.4f - %.4f | %d workgroups, %d bytes of LDS each | %s"
+              % (leg, " ".join("%.4f" % v for v in ms[leg]), float(np.median(ms[leg])), min(ms[leg]), max(ms[leg]), recs[leg][0]["workgroups"],
+                 recs[leg][0]["lds_bytes"], recs[leg][0]["kernel"]))
+    for new, old in (("inst-D", "parent-A"), ("inst-D-4", "parent-A-4")):
+        on_d = recs[new][0]["kernel"].startswith("D ")
+        below = all(n < o for n, o in zip(ms[new], ms[old]))
+        print("%s on layout D: %s; below %s in every round: %s (largest %.4f against smallest %.4f, %s's spread %.4f; ratio of medians %.3f)"
+              % (new, "yes" if on_d else "NO", old, "yes" if below else "NO", max(ms[new]), min(ms[old]), old, max(ms[old]) - min(ms[old]),
+                 float(np.median(ms[new])) / float(np.median(ms[old]))))
+    print("distance to the floor: inst-D median %.4f against shared-D median %.4f (ratio %.3f)"
+          % (float(np.median(ms["inst-D"])), float(np.median(ms["shared-D"])), float(np.median(ms["inst-D"])) / float(np.median(ms["shared-D"]))))
 
 
 def device_copy(pkg, arrays):
@@ -154,11 +232,13 @@ def main():
     ap.add_argument("--rounds", type=int, default=4)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--child", default="", help=argparse.SUPPRESS)
+    ap.add_argument("--d", action="store_true")
+    ap.add_argument("--parent-lib", default="")
     a = ap.parse_args()
     if not a.child:
-        return sweep(a)
+        return sweep_d(a) if a.d else sweep(a)
     import __graft_entry__ as ge
-    child(ge.load_package(), a)
+    (child_d if a.d else child)(ge.load_package(), a)
 
 
 if __name__ == "__main__":
