@@ -316,7 +316,8 @@ int tinympc_set_bound_constraints_batch_device(tinympc_solver *s, const double *
  * for the quadrotor at N = 20 with one row, specialised at run time otherwise. Trajectories, tracks, per-knot bounds, wider systems,
  * longer horizons and a refused specialisation (tinympc_get_jit_info then reads "refused(<reason>) per-instance-linear") stay on
  * layout A, and a handle moves between the two from one launch to the next as its configuration changes; the ADMM state, the family's
- * duals included, is shared, so a warm start carries over. Either way the mode takes shared cones, fdyn, per-instance references
+ * duals included, is shared, so a warm start carries over. Either way the mode takes cones -- shared, or with every instance's own
+ * slopes (tinympc_set_cone_slopes_batch below: the other half of the same mode) --, fdyn, per-instance references
  * (goals, trajectories, tracks) and per-instance bounds (box or per knot)
  * in any combination: its kernels always read the reference and clamp rows per instance. With per-instance models or rho, adaptive
  * rho, nx+nu > 64 or more cones / rounds than the generic kernels hold a solve returns TINYMPC_ERR_UNSUPPORTED (never a solve with
@@ -332,6 +333,38 @@ int tinympc_set_linear_constraints_batch(tinympc_solver *s, const double *Alin_x
  * tinympc_set_x0_batch_device. */
 int tinympc_set_linear_constraints_batch_device(tinympc_solver *s, const double *d_Alin_x, const double *d_blin_x, int nlx,
                                                 const double *d_Alin_u, const double *d_blin_u, int nlu, int first, int count);
+
+/* Per-instance cone slopes for instances [first, first+count) of a batched handle. The cone STRUCTURE (Acx, qcx, Acu, qcu) is the one the
+ * handle holds from tinympc_set_cone_constraints and belongs to the batch; the slope values belong to the instance. cx: ncx x count,
+ * column-major, instance first+b's slopes at b*ncx in the order of the shared cone list; cu: ncu x count likewise. ncx and ncu must
+ * equal the structure's counts; a side without cones takes NULL. Instance first+b then solves exactly what a single-instance handle
+ * would solve after tinympc_set_cone_constraints(Acx, qcx, cx_b, ncx, Acu, qcu, cu_b, ncu) -- an instance whose slopes are the shared
+ * ones, bit for bit what the shared cones give on the same kernel. The first call turns the slopes' half of the per-instance families
+ * mode on; it may name any sub-range: the other instances keep the shared slopes of that moment. The call changes no enable flag (the
+ * shared verb enabled the sides; tinympc_update_settings may switch a side off for every instance) and keeps the ADMM state, the
+ * cones' duals included: re-sending slopes between two warm-started tinympc_mpc_step_batch ticks is an intended use. A later
+ * tinympc_set_cone_constraints installs a new structure and returns every instance to shared slopes. reset_workspace,
+ * update_settings, every reference, track and bound verb, both linear verbs, the solve verbs, mpc_step_batch and prepare keep the half
+ * and its values.
+ * Per-instance slopes and per-instance linear rows (tinympc_set_linear_constraints_batch) are two halves of ONE mode, in either order
+ * and each alone: the shared tinympc_set_linear_constraints ends the rows' half only, the shared tinympc_set_cone_constraints the
+ * slopes' half only, and the mode ends when both are off. Layout A's kernel of the mode always reads rows and slopes per instance:
+ * the half that is off holds the shared values for every instance (one absent row on a handle without linear rows); layout D's form
+ * is specialised on the row count and on whether the slopes' half is on. So the mode runs where the rows'
+ * mode runs -- layout A (" per-instance-cones" in tinympc_get_jit_info, beside " per-instance-linear" when both halves are on), or,
+ * after tinympc_prepare, layout D under the conditions stated above (the kernel is compiled in for the rocket landing nx=6 nu=3 N=10
+ * with one row, specialised at run time otherwise; cones that share rows stay on layout A) -- and is refused where that mode is
+ * refused: with per-instance models or rho, adaptive rho, nx+nu > 64 or more cones / rounds than the generic kernels hold a solve
+ * returns TINYMPC_ERR_UNSUPPORTED (never a solve with shared slopes), and so does tinympc_session_begin.
+ * Invalid arguments -- a slope that is NaN, infinite or <= 0, a count that differs from the structure's, no cones on the handle, NULL
+ * for a non-empty side, a range that is empty or beyond the batch, host memory or another GPU's memory handed to the _device form --
+ * return TINYMPC_ERR_INVALID_INPUT and leave mode, slopes, flags and ADMM state as they were: everything is validated (on the device,
+ * one flag read back) before anything is written. Single-instance handles: the same as tinympc_set_cone_constraints with the held
+ * structure, with count 1. The input has been copied when the call returns. */
+int tinympc_set_cone_slopes_batch(tinympc_solver *s, const double *cx, int ncx, const double *cu, int ncu, int first, int count);
+/* Same, from device memory on the handle's GPU (host and device form give the same bits: one builder); same contract as
+ * tinympc_set_x0_batch_device. */
+int tinympc_set_cone_slopes_batch_device(tinympc_solver *s, const double *d_cx, int ncx, const double *d_cu, int ncu, int first, int count);
 
 /* Per-instance models for instances [first, first+count) of a batched handle.
  * A: nx*nx*count, B: nx*nu*count, fdyn: nx*count (NULL = zeros), Q: nx*nx*count, R: nu*nu*count; column-major, instance b's block

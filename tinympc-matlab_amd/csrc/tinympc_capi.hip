@@ -795,6 +795,7 @@ int tinympc_set_linear_constraints(tinympc_solver *s, const double *Alin_x, cons
         s->inst.lin = false;
         if (s->inst_tables()) s->inst.mark(0, s->batch);
     }
+    s->inst.shared_rows_dirty = true;  // (per-instance cone slopes alone: the store's rows are a copy of these)
     s->n_lin_x = nlx;
     s->n_lin_u = nlu;
     s->Alin_x.assign(Alin_x, Alin_x + (size_t)nlx * s->nx);
@@ -857,6 +858,11 @@ int tinympc_set_cone_constraints(tinympc_solver *s, const int *Acx, const int *q
     s->n_cone_u = ncu;
     s->Acx.assign(Acx, Acx + ncx); s->qcx.assign(qcx, qcx + ncx); s->cx.assign(cx, cx + ncx);
     s->Acu.assign(Acu, Acu + ncu); s->qcu.assign(qcu, qcu + ncu); s->cu.assign(cu, cu + ncu);
+    if (s->inst.cones) {  // (per-instance cone slopes: a new structure, every instance on the shared slopes again)
+        s->inst.cones = false;
+        if (s->inst_tables()) s->inst.mark(0, s->batch);
+    }
+    s->inst.slopes_dirty = true;  // (per-instance linear rows alone: the store's slope vectors are a copy of these)
     if (ncx > 0) s->st.en_state_soc = 1;  // bindings.cpp:468-476
     if (ncu > 0) s->st.en_input_soc = 1;
     s->fam_dirty = true;
@@ -886,6 +892,8 @@ int tinympc_update_settings(tinympc_solver *s, double abs_pri_tol, double abs_du
     s->st.abs_pri_tol = abs_pri_tol; s->st.abs_dua_tol = abs_dua_tol;
     s->st.max_iter = max_iter; s->st.check_termination = check_termination;
     s->st.en_state_bound = en_state_bound; s->st.en_input_bound = en_input_bound;
+    // (the cones' rounds follow the enabled sides, and the per-instance slope vectors the rounds)
+    if ((s->st.en_state_soc != 0) != (en_state_soc != 0) || (s->st.en_input_soc != 0) != (en_input_soc != 0)) s->inst.slopes_dirty = true;
     s->st.en_state_soc = en_state_soc; s->st.en_input_soc = en_input_soc;
     s->st.en_state_linear = en_state_linear; s->st.en_input_linear = en_input_linear;
     s->st.adaptive_rho = adaptive_rho; s->st.adaptive_rho_min = adaptive_rho_min;
@@ -1742,6 +1750,7 @@ int set_lin_batch(tinympc_solver *s, const double *Ax, const double *bx, int nlx
             z.nlx = z.nlu = 0; z.first = 0; z.count = s->groups * s->IPW;
             z.Ax = z.bx = z.Au = z.bu = nullptr;
             HIP_TRY(launch_build_inst_lin(z, s->stream));
+            in.slopes_dirty = true;  // (the groups' slope vectors share the blocks that were just laid out anew: rebuilt at the next launch)
             if (!whole) {  // ... and the instances this call does not name on the shared rows of this moment (same counts: checked above)
                 double *sh = nullptr;
                 if ((rc = dalloc(s, &sh, per))) return rc;
@@ -1760,9 +1769,13 @@ int set_lin_batch(tinympc_solver *s, const double *Ax, const double *bx, int nlx
         }
         HIP_TRY(launch_build_inst_lin(q, s->stream));
     }
-    if (!in.lin) in.mark(0, s->batch);  // (the reference and clamp rows of every instance: this mode's kernel always reads them per instance)
+    if (!in.fam()) {  // (the mode begins; the reference and clamp rows of every instance: this mode's kernel always reads them per instance)
+        in.mark(0, s->batch);
+        in.slopes_dirty = true;
+    }
     in.lin = true;
     in.lin_nlx = nlx; in.lin_nlu = nlu; in.lin_nl = q.nl;
+    if (!s->layout_m) in.fam_rows_nl = q.nl;
     if (nlx != s->n_lin_x || nlu != s->n_lin_u) {  // (the shared rows are not read while the mode is on; they keep the handle's counts consistent)
         s->n_lin_x = nlx; s->n_lin_u = nlu;
         s->Alin_x.assign(ax, 0.0); s->blin_x.assign(nlx, std::numeric_limits<double>::infinity());
@@ -1777,7 +1790,105 @@ int set_lin_batch(tinympc_solver *s, const double *Ax, const double *bx, int nlx
     return TINYMPC_OK;
 }
 
+// tinympc_set_cone_slopes_batch (+ _device): the cone slopes of instances [first, first+count) on the handle's cone structure. Host
+// input is staged on the device; from there both forms are ONE path -- k_check_inst_slopes validates the values where they lie (one
+// flag read back), then, and only then, k_store_inst_slopes copies them into the raw array every instance's slopes are kept in. The
+// store the kernels read is rebuilt from it at the next launch (refresh_inst_families).
+int set_cone_slopes_batch(tinympc_solver *s, const double *cx, int ncx, const double *cu, int ncu, bool on_device, int first, int count) {
+    const char *verb = on_device ? "set_cone_slopes_batch_device" : "set_cone_slopes_batch";
+    int rc = check_handle(s);
+    if (rc) return rc;
+    if (s->n_cone_x + s->n_cone_u == 0)
+        return fail(TINYMPC_ERR_INVALID_INPUT, "%s: the handle holds no cones (tinympc_set_cone_constraints sets the structure)", verb);
+    if (ncx != s->n_cone_x || ncu != s->n_cone_u)
+        return fail(TINYMPC_ERR_INVALID_INPUT, "%s: %d state and %d input slopes, but the handle's structure has %d and %d cones", verb, ncx, ncu,
+                    s->n_cone_x, s->n_cone_u);
+    if ((ncx > 0 && !cx) || (ncu > 0 && !cu)) return fail(TINYMPC_ERR_INVALID_INPUT, "%s: NULL array for a non-empty side", verb);
+    if (first < 0 || count < 1 || first > s->batch - count)
+        return fail(TINYMPC_ERR_INVALID_INPUT, "%s: instance range [%d, %d + %d) is empty or outside batch of %d", verb, first, first, count, s->batch);
+    if (on_device && ((ncx > 0 && !on_handles_device(s, cx)) || (ncu > 0 && !on_handles_device(s, cu))))
+        return fail(TINYMPC_ERR_INVALID_INPUT, "%s: the slopes are not device memory of the handle's GPU %d", verb, s->device);
+    InstState &in = s->inst;
+    const size_t nc = (size_t)ncx + ncu, n = (size_t)count;
+    if (s->batch == 1) {  // the shared verb with the held structure, after this verb's own checks of the values
+        std::vector<double> h(nc);
+        if (on_device && (rc = bind_device(s))) return rc;
+        if (ncx > 0) { if (on_device) { if ((rc = download(s, h.data(), cx, sizeof(double) * ncx))) return rc; } else std::memcpy(h.data(), cx, sizeof(double) * ncx); }
+        if (ncu > 0) { if (on_device) { if ((rc = download(s, h.data() + ncx, cu, sizeof(double) * ncu))) return rc; } else std::memcpy(h.data() + ncx, cu, sizeof(double) * ncu); }
+        for (size_t i = 0; i < nc; ++i)
+            if (!(h[i] > 0.0) || !std::isfinite(h[i])) return fail(TINYMPC_ERR_INVALID_INPUT, "%s: a slope is NaN, infinite or not positive", verb);
+        const std::vector<int> Acx = s->Acx, qcx = s->qcx, Acu = s->Acu, qcu = s->qcu;
+        const int esx = s->st.en_state_soc, esu = s->st.en_input_soc;
+        rc = tinympc_set_cone_constraints(s, Acx.data(), qcx.data(), h.data(), ncx, Acu.data(), qcu.data(), h.data() + ncx, ncu);
+        if (rc == TINYMPC_OK && (s->st.en_state_soc != esx || s->st.en_input_soc != esu)) {  // (this verb changes no enable flag)
+            s->st.en_state_soc = esx; s->st.en_input_soc = esu;
+        }
+        return rc;
+    }
+    if ((rc = bind_device(s))) return rc;
+    InstSlopeParams q{};
+    q.W = s->W; q.ncx = ncx; q.ncu = ncu; q.batch = s->batch; q.groups = s->groups; q.first = first; q.count = count;
+    q.cx_stride = (size_t)ncx; q.cu_stride = (size_t)ncu;
+    double *old_stage = nullptr;
+    if (on_device) {
+        q.cx = cx; q.cu = cu;
+    } else {
+        if (nc * n > in.lstage_cap) {
+            old_stage = in.lstage;
+            if ((rc = dalloc(s, &in.lstage, nc * n))) return rc;
+            in.lstage_cap = nc * n;
+        }
+        double *dcx = in.lstage, *dcu = dcx + (size_t)ncx * n;
+        if (ncx > 0) HIP_TRY(hipMemcpyAsync(dcx, cx, sizeof(double) * ncx * n, hipMemcpyHostToDevice, s->stream));
+        if (ncu > 0) HIP_TRY(hipMemcpyAsync(dcu, cu, sizeof(double) * ncu * n, hipMemcpyHostToDevice, s->stream));
+        q.cx = dcx; q.cu = dcu;
+    }
+    if (!in.mflag && (rc = dalloc(s, &in.mflag, (size_t)1))) return rc;
+    int bad = 0;
+    HIP_TRY(hipMemsetAsync(in.mflag, 0, sizeof(int), s->stream));
+    HIP_TRY(launch_check_inst_slopes(q, in.mflag, s->stream));
+    if ((rc = download(s, &bad, in.mflag, sizeof(int)))) return rc;  // (host input has been copied when this returns)
+    if (old_stage) dfree(s, old_stage);
+    if (bad) return fail(TINYMPC_ERR_INVALID_INPUT, "%s: a slope is NaN, infinite or not positive", verb);
+    // ---- valid: from here on the call writes
+    if (nc * s->batch > in.craw_cap) {  // (a structure with more cones than the last one the half was on with; the half is off then)
+        double *old = in.craw;
+        if ((rc = dalloc(s, &in.craw, nc * s->batch))) return rc;
+        in.craw_cap = nc * s->batch;
+        if (old) dfree(s, old);
+    }
+    q.raw = in.craw; q.raw_stride = nc;
+    if (!in.cones) {  // the half begins: every instance on the shared slopes of this moment
+        if (!in.cshared && (rc = dalloc(s, &in.cshared, (size_t)HARD_MAX_CONES))) return rc;
+        std::vector<double> h(s->cx);
+        h.insert(h.end(), s->cu.begin(), s->cu.end());
+        if ((rc = upload(s, in.cshared, h.data(), nc))) return rc;
+        InstSlopeParams w = q;
+        w.first = 0; w.count = s->batch;
+        w.cx = in.cshared; w.cu = in.cshared + ncx; w.cx_stride = w.cu_stride = 0;
+        HIP_TRY(launch_store_inst_slopes(w, s->stream));
+    }
+    HIP_TRY(launch_store_inst_slopes(q, s->stream));
+    if (!in.fam()) {  // (the mode begins; the reference and clamp rows of every instance: its kernels always read them per instance)
+        if (!s->layout_m && (rc = alloc_inst_rows(s, true))) return rc;
+        in.mark(0, s->batch);
+        in.shared_rows_dirty = true;
+    }
+    in.cones = true;
+    in.slopes_dirty = true;
+    // the caller keeps ownership of its buffers: everything has been read when the call returns (the tinympc_set_x0_batch_device rule)
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return TINYMPC_OK;
+}
+
 }  // namespace
+
+int tinympc_set_cone_slopes_batch(tinympc_solver *s, const double *cx, int ncx, const double *cu, int ncu, int first, int count) {
+    return set_cone_slopes_batch(s, cx, ncx, cu, ncu, false, first, count);
+}
+int tinympc_set_cone_slopes_batch_device(tinympc_solver *s, const double *d_cx, int ncx, const double *d_cu, int ncu, int first, int count) {
+    return set_cone_slopes_batch(s, d_cx, ncx, d_cu, ncu, true, first, count);
+}
 
 int tinympc_set_linear_constraints_batch(tinympc_solver *s, const double *Alin_x, const double *blin_x, int nlx, const double *Alin_u,
                                          const double *blin_u, int nlu, int first, int count) {

@@ -256,6 +256,9 @@ struct SolveParams {
     // Per-instance linear rows (tinympc_set_linear_constraints_batch; layout A's InstFamilies variant, k_admm_solve_ifam): ilin is
     // [groups][3 * ilin_nl][64] -- per wavefront and row k the three vectors a_k | b_k | ||a_k||^2 of the shared description (fam_doubles()),
     // one 512-byte line each, in the solve kernel's lane order; ilin_nl = max(rows per side) of the mode. Built by k_build_inst_lin.
+    // In front of a group's 3 * ilin_nl row vectors lie its INST_FAM_SLOPE_ROWS cone-slope vectors (tinympc_set_cone_slopes_batch): per round q
+    // of the shared cone structure the slope of the cone each lane's row belongs to, 0 for a row in no cone of the round -- mu[W] of the
+    // shared description, per instance (k_build_inst_slopes). A group's block is inst_fam_group_doubles(ilin_nl) doubles.
 };
 
 // Per-instance references and bounds of a batched handle (k_store_inst_refs, k_build_inst_tables; tinympc_kernels.hip). The references
@@ -304,7 +307,25 @@ struct InstLinParams {
     size_t ax_stride, bx_stride, au_stride, bu_stride;
     double *dst;
 };
-__host__ __device__ inline size_t inst_lin_doubles(int groups, int nl) { return (size_t)groups * 3 * (nl > 0 ? nl : 1) * 64; }
+// A group's block of the store: one cone-slope vector per round (INST_FAM_SLOPE_ROWS = MAX_ROUNDS, below), then 3 nl row vectors -- the
+// slopes first, so that their address does not depend on the row count (k_admm_solve_ifam reads them inside its ADMM loop).
+constexpr int INST_FAM_SLOPE_ROWS = 4;
+__host__ __device__ constexpr size_t inst_fam_group_doubles(int nl) { return (size_t)(3 * (nl > 0 ? nl : 1) + INST_FAM_SLOPE_ROWS) * 64; }
+__host__ __device__ inline size_t inst_lin_doubles(int groups, int nl) { return (size_t)groups * inst_fam_group_doubles(nl); }
+// Per-instance cone slopes (tinympc_set_cone_slopes_batch). k_store_inst_slopes keeps the verb's values: raw [batch][ncx + ncu] <- cx | cu of
+// instances [first, first+count) (strides of 0: one block for every instance -- the shared slopes). k_build_inst_slopes scatters them
+// through the shared structure into the store's slope vectors: lane r of round q takes raw[inst][map[q][r]], 0 where map is -1 (the row
+// is in no cone of the round); lanes beyond the batch (the last group's padding) take instance 0's.
+struct InstSlopeParams {
+    int W, nl, ncx, ncu;
+    int batch, groups, first, count;
+    const double *cx, *cu;
+    size_t cx_stride, cu_stride;
+    double *raw;             // [batch][ncx + ncu]: instance b's slopes at b * raw_stride (the builder: a stride of 0 reads one block for every instance)
+    size_t raw_stride;
+    double *dst;             // the store (SolveParams::ilin)
+    signed char map[INST_FAM_SLOPE_ROWS][64];
+};
 struct InstTableParams {
     int nx, nu, N, W, KT, groups;
     int en_state_bound, en_input_bound;
@@ -391,6 +412,7 @@ constexpr int MAX_LIN_ROWS = 32;  // per side
 constexpr int FAM_REG_ROWS = 8;   // k_admm_solve_fam keeps this many rows' coefficients in registers, the rest is read per use
 constexpr int MAX_CONES = 16;
 constexpr int MAX_ROUNDS = 4;
+static_assert(INST_FAM_SLOPE_ROWS == MAX_ROUNDS, "the per-instance store holds one slope vector per round of the generic kernels");
 constexpr int HARD_MAX_LIN_ROWS = 128, HARD_MAX_CONES = 64;
 __host__ __device__ constexpr int fam_lin_cap(int nl) { return nl > MAX_LIN_ROWS ? nl : MAX_LIN_ROWS; }
 __host__ __device__ constexpr int fam_cone_cap(int ncone) { return ncone > MAX_CONES ? ncone : MAX_CONES; }
@@ -443,7 +465,7 @@ bool solve_e_supported(int nx, int nu, int N, bool const_tables, bool families, 
 hipError_t launch_solve_e(const SolveParams &p, const FamilyStructure &fs, hipStream_t stream);
 void solve_e_describe(int nx, int nu, int N, bool const_tables, bool families, const FamilyStructure &fs, char *buf, size_t len);
 void solve_jit_describe(int W, int nx, int nu, int N, bool const_tables, bool families, bool adaptive, char *buf, size_t len, bool goal = false,
-                        bool models = false, int ilin = 0);
+                        bool models = false, int ilin = 0, bool icone = false);
 // Layout F (tinympc_solve_f.hip, run-time specialised only): the latency kernel with compile-time shape and structure
 bool solve_f_plan(int nx, int nu, int N, bool const_tables, bool families, const FamilyStructure &fs, int *chunk_len, int *chunks, int *wpg, size_t *lds_bytes);
 bool solve_f_supported(int nx, int nu, int N, bool const_tables, bool families, const FamilyStructure &fs);  // plans AND compiles
@@ -494,6 +516,11 @@ hipError_t launch_check_positive(const double *v, int n, int *flag, hipStream_t 
 // row of A is all zero or holds a value that is not finite, or a b is NaN or -inf (the strides of p; dst is not touched)
 hipError_t launch_build_inst_lin(const InstLinParams &p, hipStream_t stream);
 hipError_t launch_check_inst_lin(const InstLinParams &p, int *flag, hipStream_t stream);
+// Per-instance cone slopes: the validation of the verb's input where it lies -- *flag <- 1 if a slope is NaN, infinite or <= 0 --, the
+// copy into the raw array and the store's slope vectors of every group (InstSlopeParams)
+hipError_t launch_check_inst_slopes(const InstSlopeParams &p, int *flag, hipStream_t stream);
+hipError_t launch_store_inst_slopes(const InstSlopeParams &p, hipStream_t stream);
+hipError_t launch_build_inst_slopes(const InstSlopeParams &p, hipStream_t stream);
 hipError_t launch_check_ref_steps(const int *steps, int n, int delta, int *flag, hipStream_t stream);  // *flag = 1 if some steps[i] + delta < 0
 hipError_t launch_advance_ref_steps(int *steps, int n, int delta, hipStream_t stream);                 // steps[i] += delta, saturating in [0, INT_MAX]
 // Layout A: one wavefront per workgroup, all ADMM state in LDS (lowest latency, 2 waves per CU). One kernel body, three
@@ -583,15 +610,16 @@ hipError_t launch_solve_m(const SolveParams &p, hipStream_t stream);
 // [batch][ops_doubles(W, KT)], staged per wavefront; 16 lanes, constant tables, box path). With TINYMPC_JIT=0 only a compiled-in one.
 // ilin: the per-instance linear-row form (-DTINY_JIT_ILIN=<nl> with families and goal: the families' variant reading every instance's own
 // rows, SolveParams::ilin, staged per wavefront; 16 lanes, constant tables; 0: off). With TINYMPC_JIT=0 only a compiled-in one.
+// icone (with ilin): ... and every instance's own cone slope (-DTINY_JIT_ICONE=1: the per-instance families form with the slope half on)
 bool solve_jit_supported(int W, int nx, int nu, int N, bool const_tables, bool families = false, bool adaptive = false, bool goal = false,
-                         bool models = false, int ilin = 0);
-hipError_t launch_solve_jit(const SolveParams &p, int W, hipStream_t stream, bool models = false, int ilin = 0);
+                         bool models = false, int ilin = 0, bool icone = false);
+hipError_t launch_solve_jit(const SolveParams &p, int W, hipStream_t stream, bool models = false, int ilin = 0, bool icone = false);
 bool solve_jit_refill_supported(int W, int nx, int nu, int N, bool const_tables);   // (compiles the slot-refill variant on first use)
 int solve_jit_resident_wavefronts(int W, int nx, int nu, int N, bool const_tables);  // wavefronts of the shape's plan the device holds at once
 int solve_jit_workgroups(int W, int nx, int nu, int N, bool const_tables, int groups, bool families = false, bool adaptive = false, bool goal = false,
-                         bool models = false, int ilin = 0);
+                         bool models = false, int ilin = 0, bool icone = false);
 size_t solve_jit_lds_bytes(int W, int nx, int nu, int N, bool const_tables, bool families = false, bool adaptive = false, bool goal = false,
-                           bool models = false, int ilin = 0);  // per workgroup, from the plan  // 8 wavefronts per workgroup, 4 on the long-horizon plan
+                           bool models = false, int ilin = 0, bool icone = false);  // per workgroup, from the plan  // 8 wavefronts per workgroup, 4 on the long-horizon plan
 #endif  // !__HIPCC_RTC__
 
 // Doubles of working state per group in layout A (G and V with N+2 rows, D with 64 dummy slots).

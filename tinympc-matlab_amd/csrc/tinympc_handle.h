@@ -115,10 +115,25 @@ struct InstState {
     // 0 no, 1 yes -- the answer for d_lin_nl rows; another count (a whole-batch call) makes it unknown again (resolve_plan). The cones are
     // no part of the specialisation: whether their structure is one the form takes is asked at every launch (lin_wants_d).
     int d_lin = -1, d_lin_nl = 0;
+    bool d_lin_cones = false;                // ... and for the slope half on / off (ICONE: the form that reads the slope per instance)
     double *lrows = nullptr;
     size_t lrows_cap = 0;                    // doubles lrows was allocated for
     double *lstage = nullptr;                // device staging of host input (the shared rows of a sub-range first call: a block of their own, freed in the call)
     size_t lstage_cap = 0;
+    // Per-instance cone slopes (tinympc_set_cone_slopes_batch): the other half of the same mode -- on from the first call until
+    // tinympc_set_cone_constraints. The cones' STRUCTURE stays the handle's; craw keeps every instance's slopes, [batch][n_cone_x + n_cone_u]
+    // in list order (instances the verb never named: the shared slopes of the moment the half began). The kernels read the store's slope
+    // vectors in front of each group's rows in lrows, which refresh_inst_families rebuilds from craw -- or, while only the row half is on,
+    // from the shared slopes -- whenever the slopes, the structure or an enable flag changed (the rounds follow the enabled sides).
+    // While only THIS half is on the store's rows are the shared rows, copied for every instance (fam_rows_nl of them; one absent row on a
+    // handle without linear rows).
+    bool cones = false;
+    bool fam() const { return lin || cones; }  // the per-instance families mode: either half
+    double *craw = nullptr;
+    double *cshared = nullptr;               // the shared slopes cx | cu on the device (the row half alone)
+    size_t craw_cap = 0;
+    bool slopes_dirty = true, shared_rows_dirty = true;  // the store's slope vectors / its copy of the shared rows are out of date
+    int fam_rows_nl = 0;                     // rows per instance the store holds now (SolveParams::ilin_nl; 0: no store yet)
     int dirty_lo = 0, dirty_hi = 0;
     bool refs() const { return x || u; }
     const double *lr_rows() const { return lr + (size_t)tinympc::INST_LR_PAD * 64; }  // SolveParams::iref_lr on layout A
@@ -265,7 +280,12 @@ struct tinympc_solver {
     bool fam_dirty = true;
     // Per-instance references and bounds (tinympc_set_x_ref_batch / _u_ref_batch / _bound_constraints_batch; batched handles): InstState.
     InstState inst;
-    bool inst_tables() const { return inst.refs() || inst.bounds || inst.models || inst.lin; }  // the per-instance table rows are in use
+    bool inst_tables() const { return inst.refs() || inst.bounds || inst.models || inst.fam(); }  // the per-instance table rows are in use
+    // rows per instance of the per-instance families store: the row half's count, else the shared rows' (one absent row where there are none)
+    int ifam_nl() const {
+        const int n = inst.lin ? inst.lin_nl : (n_lin_x > n_lin_u ? n_lin_x : n_lin_u);
+        return n > 0 ? n : 1;
+    }
     // Goal form (every instance's references AND bounds constant over the horizon): layout D's constant-table kernel carries it, with
     // knot 0's rows per instance; everything else runs on layout A.
     bool iref_goal() const {
@@ -355,6 +375,7 @@ int flush_host_refs(tinympc_solver *s);
 int refresh_derived(tinympc_solver *s);
 FamilyStructure family_structure(const tinympc_solver *s, double *mu = nullptr);
 int refresh_families(tinympc_solver *s);
+int refresh_inst_families(tinympc_solver *s);  // the per-instance families store: its copy of the shared rows (slope half alone) and its slope vectors
 int refresh_inst_tables(tinympc_solver *s);  // the per-instance table rows of the instances whose references / bounds / models changed
 int alloc_inst_rows(tinympc_solver *s, bool bounds);  // the table rows themselves (allocated by the first per-instance verb that needs them)
 void destroy(tinympc_solver *s);

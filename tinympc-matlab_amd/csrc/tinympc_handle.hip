@@ -358,7 +358,7 @@ int refresh_inst_tables(tinympc_solver *s) {
     p.x_min = in.bounds ? in.xmin : s->dxmin; p.x_max = in.bounds ? in.xmax : s->dxmax;
     p.u_min = in.bounds ? in.umin : s->dumin; p.u_max = in.bounds ? in.umax : s->dumax;
     p.lr = const_cast<double *>(in.lr_rows()); p.pn = in.pn; p.lrg = in.lrg; p.bndg = in.bndg;
-    p.bnd = (in.bounds || in.models || in.lin) ? in.bnd : nullptr;  // (the models' and the linear rows' kernels always read per-instance clamp rows: shared bounds are copied)
+    p.bnd = (in.bounds || in.models || in.fam()) ? in.bnd : nullptr;  // (the models' and the linear rows' kernels always read per-instance clamp rows: shared bounds are copied)
     HIP_TRY(launch_build_inst_tables(p, s->stream));
     in.dirty_lo = in.dirty_hi = 0;
     return TINYMPC_OK;
@@ -539,7 +539,7 @@ int refresh_families(tinympc_solver *s) {
     (void)cone_u;
     // (per-instance linear rows: the rows live in InstState::lrows, k_admm_solve_ifam reads the enable flags above and nothing of the
     // block below; the shared vectors may not even have the mode's counts)
-    const bool shared_rows = !s->inst.lin;
+    const bool shared_rows = !s->inst.fam();
     const int nlx = lin_x && shared_rows ? s->n_lin_x : 0, nlu = lin_u && shared_rows ? s->n_lin_u : 0;
     const int nl = nlx > nlu ? nlx : nlu;
     lin[0] = (double)nl;
@@ -559,6 +559,81 @@ int refresh_families(tinympc_solver *s) {
     int rc = upload(s, s->dfam, f.data(), f.size());
     if (rc) return rc;
     s->fam_dirty = false;
+    return TINYMPC_OK;
+}
+
+// The per-instance families store (InstState::lrows, SolveParams::ilin) before a launch of the mode's kernels, which read rows AND
+// slopes per instance whichever half is on: while only the slope half is on, the rows are the shared rows copied for every instance
+// (k_build_inst_lin with strides of 0 -- the values and norms refresh_families would write); the slope vectors come from every
+// instance's raw slopes, or from the shared ones while only the row half is on, through the structure of the ENABLED sides
+// (family_structure: the rounds follow the enable flags). Nothing runs when nothing changed.
+int refresh_inst_families(tinympc_solver *s) {
+    InstState &in = s->inst;
+    if (!in.fam() || s->layout_m) return TINYMPC_OK;
+    int rc;
+    const int nl = s->ifam_nl(), IPW = 64 / s->W;
+    const size_t need = inst_lin_doubles(s->groups, nl);
+    if (need > in.lrows_cap) {  // (only ever here while the row half is off: its verb sizes the store itself; the old block stays on the handle's free list)
+        if ((rc = dalloc(s, &in.lrows, need))) return rc;
+        in.lrows_cap = need;
+        in.fam_rows_nl = 0;
+    }
+    if (nl != in.fam_rows_nl) {  // a new store, or another row count: the groups' blocks have moved
+        in.slopes_dirty = true;
+        if (!in.lin) in.shared_rows_dirty = true;
+    }
+    if (!in.lin && in.shared_rows_dirty) {
+        const int nlx = s->n_lin_x, nlu = s->n_lin_u;
+        const size_t ax = (size_t)nlx * s->nx, au = (size_t)nlu * s->nu, per = ax + nlx + au + nlu;
+        InstLinParams z{};
+        z.nx = s->nx; z.nu = s->nu; z.W = s->W; z.nl = nl; z.batch = s->batch; z.first = 0; z.count = s->groups * IPW;
+        z.dst = in.lrows;
+        HIP_TRY(launch_build_inst_lin(z, s->stream));  // every lane absent, padding included
+        if (per > 0) {
+            if (per > in.lstage_cap) {
+                if ((rc = dalloc(s, &in.lstage, per))) return rc;
+                in.lstage_cap = per;
+            }
+            std::vector<double> h;
+            h.insert(h.end(), s->Alin_x.begin(), s->Alin_x.end()); h.insert(h.end(), s->blin_x.begin(), s->blin_x.end());
+            h.insert(h.end(), s->Alin_u.begin(), s->Alin_u.end()); h.insert(h.end(), s->blin_u.begin(), s->blin_u.end());
+            if (h.size() != per) return fail(TINYMPC_ERR_INVALID_INPUT, "per-instance cone slopes: the shared linear rows are inconsistent");
+            if ((rc = upload(s, in.lstage, h.data(), per))) return rc;
+            InstLinParams w = z;
+            w.nlx = nlx; w.nlu = nlu; w.count = s->batch;
+            w.Ax = in.lstage; w.bx = w.Ax + ax; w.Au = w.bx + nlx; w.bu = w.Au + au;
+            HIP_TRY(launch_build_inst_lin(w, s->stream));
+        }
+        in.shared_rows_dirty = false;
+    }
+    if (in.slopes_dirty) {
+        const int ncx = s->n_cone_x, ncu = s->n_cone_u, nc = ncx + ncu;
+        InstSlopeParams q{};
+        q.W = s->W; q.nl = nl; q.ncx = ncx; q.ncu = ncu; q.batch = s->batch; q.groups = s->groups;
+        q.dst = in.lrows;
+        for (int r = 0; r < INST_FAM_SLOPE_ROWS; ++r)
+            for (int l = 0; l < 64; ++l) q.map[r][l] = -1;
+        const FamilyStructure fs = family_structure(s);
+        const bool state_on = s->st.en_state_soc && ncx > 0;
+        for (int c = 0; c < fs.ncone; ++c) {  // the active cones in list order: state cones first where that side is enabled
+            const int raw = state_on ? c : ncx + c, round = fs.cone[c][0];
+            if (round >= INST_FAM_SLOPE_ROWS || raw >= nc) continue;  // (beyond the generic kernels: the launch refuses)
+            for (int r = fs.cone[c][1]; r <= fs.cone[c][2] && r < 64; ++r) q.map[round][r] = (signed char)raw;
+        }
+        if (in.cones) {
+            q.raw = in.craw; q.raw_stride = (size_t)nc;
+        } else if (nc > 0) {  // the row half alone: the shared slopes for every instance
+            if (!in.cshared && (rc = dalloc(s, &in.cshared, (size_t)HARD_MAX_CONES))) return rc;
+            std::vector<double> h(s->cx);
+            h.insert(h.end(), s->cu.begin(), s->cu.end());
+            if ((int)h.size() != nc || nc > HARD_MAX_CONES) return fail(TINYMPC_ERR_INVALID_INPUT, "per-instance linear rows: the shared cones are inconsistent");
+            if ((rc = upload(s, in.cshared, h.data(), (size_t)nc))) return rc;
+            q.raw = in.cshared; q.raw_stride = 0;
+        }
+        HIP_TRY(launch_build_inst_slopes(q, s->stream));
+        in.slopes_dirty = false;
+    }
+    in.fam_rows_nl = nl;
     return TINYMPC_OK;
 }
 

@@ -5,6 +5,7 @@
 //   k_build_tables          per-knot clamp bounds / linear-cost reference terms
 //   k_build_inst_tables     the same rows per instance (per-instance references / bounds of a batched handle; reference tracks)
 //   k_build_inst_lin        per-instance linear rows: the store layout A's InstFamilies variant reads (k_check_inst_lin validates the input)
+//   k_build_inst_slopes     per-instance cone slopes: the same store's slope vectors (k_check_inst_slopes validates, k_store_inst_slopes keeps the input)
 //   k_advance_ref_steps     reference tracks: every instance's step moves on the device (k_check_ref_steps validates device input)
 //   k_build_adapt           adaptive rho: the sensitivity rows of the sweep operators and [A'; B']
 //
@@ -776,7 +777,7 @@ __global__ void __launch_bounds__(256) k_build_inst_lin(const InstLinParams p) {
             a = A[k + (size_t)(r - nx) * p.nlu];
             bv = p.bu[b * p.bu_stride + k];
         }
-        double *row = p.dst + ((inst / IPW) * 3 * p.nl + (size_t)3 * k) * 64 + (inst % IPW) * W + r;
+        double *row = p.dst + (inst / IPW) * inst_fam_group_doubles(p.nl) + (size_t)(INST_FAM_SLOPE_ROWS + 3 * k) * 64 + (inst % IPW) * W + r;
         row[0] = a;
         row[64] = bv;
         row[128] = nrm;
@@ -816,6 +817,67 @@ hipError_t launch_check_inst_lin(const InstLinParams &p, int *flag, hipStream_t 
     if (total == 0) return hipSuccess;
     const size_t blocks = (total + 255) / 256;
     hipLaunchKernelGGL(k_check_inst_lin, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(256), 0, stream, p, flag);
+    return hipGetLastError();
+}
+
+// Per-instance cone slopes (tinympc_set_cone_slopes_batch): k_check_inst_slopes validates the verb's arrays where they lie, one thread per
+// (instance, cone): *flag <- 1 if a slope is NaN, infinite or <= 0. k_store_inst_slopes copies cx | cu of the call's instances into the
+// raw array. k_build_inst_slopes writes the store's slope vectors, [group][INST_FAM_SLOPE_ROWS | 3 nl rows][64], of EVERY group from the
+// raw array through the shared structure's map: one thread per (group, round, lane) -- values are copied, nothing is computed.
+__global__ void __launch_bounds__(256) k_check_inst_slopes(const InstSlopeParams p, int *flag) {
+    const int nc = p.ncx + p.ncu;
+    const size_t total = (size_t)nc * p.count;
+    const double big = 1.79769313486231570815e308;
+    for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
+        const size_t b = idx / nc;
+        const int c = (int)(idx % nc);
+        const double v = c < p.ncx ? p.cx[b * p.cx_stride + c] : p.cu[b * p.cu_stride + (c - p.ncx)];
+        if (!(v > 0.0) || !(v <= big)) *flag = 1;  // (NaN fails both)
+    }
+}
+__global__ void __launch_bounds__(256) k_store_inst_slopes(const InstSlopeParams p) {
+    const int nc = p.ncx + p.ncu;
+    const size_t total = (size_t)nc * p.count;
+    for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
+        const size_t b = idx / nc;
+        const int c = (int)(idx % nc);
+        const size_t inst = (size_t)p.first + b;
+        if (inst >= (size_t)p.batch) continue;
+        p.raw[inst * nc + c] = c < p.ncx ? p.cx[b * p.cx_stride + c] : p.cu[b * p.cu_stride + (c - p.ncx)];
+    }
+}
+__global__ void __launch_bounds__(256) k_build_inst_slopes(const InstSlopeParams p) {
+    const int W = p.W, IPW = 64 / W, nc = p.ncx + p.ncu;
+    const size_t total = (size_t)p.groups * INST_FAM_SLOPE_ROWS * 64;
+    const size_t gd = inst_fam_group_doubles(p.nl);
+    for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
+        const size_t g = idx / (INST_FAM_SLOPE_ROWS * 64);
+        const int q = (int)((idx / 64) % INST_FAM_SLOPE_ROWS), lane = (int)(idx % 64);
+        size_t inst = g * IPW + lane / W;
+        if (inst >= (size_t)p.batch) inst = 0;
+        const int c = p.map[q][lane % W];
+        p.dst[g * gd + (size_t)q * 64 + lane] = (c >= 0 && c < nc) ? p.raw[inst * p.raw_stride + c] : 0.0;
+    }
+}
+hipError_t launch_check_inst_slopes(const InstSlopeParams &p, int *flag, hipStream_t stream) {
+    const size_t total = (size_t)(p.ncx + p.ncu) * p.count;
+    if (total == 0) return hipSuccess;
+    const size_t blocks = (total + 255) / 256;
+    hipLaunchKernelGGL(k_check_inst_slopes, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(256), 0, stream, p, flag);
+    return hipGetLastError();
+}
+hipError_t launch_store_inst_slopes(const InstSlopeParams &p, hipStream_t stream) {
+    const size_t total = (size_t)(p.ncx + p.ncu) * p.count;
+    if (total == 0) return hipSuccess;
+    const size_t blocks = (total + 255) / 256;
+    hipLaunchKernelGGL(k_store_inst_slopes, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, stream, p);
+    return hipGetLastError();
+}
+hipError_t launch_build_inst_slopes(const InstSlopeParams &p, hipStream_t stream) {
+    const size_t total = (size_t)p.groups * INST_FAM_SLOPE_ROWS * 64;
+    if (total == 0) return hipSuccess;
+    const size_t blocks = (total + 255) / 256;
+    hipLaunchKernelGGL(k_build_inst_slopes, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, stream, p);
     return hipGetLastError();
 }
 

@@ -157,14 +157,14 @@ bool d_is_jit(const tinympc_solver *s, bool fam, bool adaptive) {
 // where the handle runs layout D, 16 lanes per instance (wider operators do not fit a wavefront's LDS share), references and bounds
 // constant over the horizon, box path. Whether the kernel exists is inst.d_models (resolve_plan).
 bool models_want_d(const tinympc_solver *s) {
-    return s->inst.models && !s->inst.lin && s->specialise_asked && s->layout_d && !s->layout_m && s->W == 16 && s->iref_goal() && !s->families_active() &&
+    return s->inst.models && !s->inst.fam() && s->specialise_asked && s->layout_d && !s->layout_m && s->W == 16 && s->iref_goal() && !s->families_active() &&
            !s->st.adaptive_rho;
 }
 
 // Per-instance linear rows (tinympc_set_linear_constraints_batch): layout A's InstFamilies variant, or layout D's ILIN form (below). What
 // neither can carry is refused at the launch (lin_refusal), never solved with shared rows.
 bool lin_runs(const tinympc_solver *s) {
-    return s->inst.lin && !s->layout_m && !s->inst.models && !s->st.adaptive_rho && !family_structure(s).beyond_generic();
+    return s->inst.fam() && !s->layout_m && !s->inst.models && !s->st.adaptive_rho && !family_structure(s).beyond_generic();
 }
 // ... on layout D: opt-in like the models' form (tinympc_prepare -- without it the mode stays on layout A, which needs no specialisation),
 // where the handle runs layout D, 16 lanes per instance, references and bounds constant over the horizon (shared or per instance: no
@@ -173,7 +173,9 @@ bool lin_runs(const tinympc_solver *s) {
 bool lin_wants_d(const tinympc_solver *s) {
     return lin_runs(s) && s->specialise_asked && s->layout_d && s->W == 16 && s->iref_goal() && family_structure(s).nround <= 1;
 }
-bool lin_on_d(const tinympc_solver *s) { return lin_wants_d(s) && s->inst.d_lin == 1 && s->inst.d_lin_nl == s->inst.lin_nl; }
+bool lin_on_d(const tinympc_solver *s) {
+    return lin_wants_d(s) && s->inst.d_lin == 1 && s->inst.d_lin_nl == s->ifam_nl() && s->inst.d_lin_cones == s->inst.cones;
+}
 
 }  // namespace
 
@@ -201,7 +203,7 @@ LaunchPlan current_plan(const tinympc_solver *s) {
     if (lin_runs(s)) {
         pl.kernel = lin_on_d(s) ? KernelId::D_JIT : KernelId::A;
         pl.inst_lin = pl.inst_refs = pl.inst_bounds = true;  // (both kernels always run on per-instance reference and clamp rows)
-    } else if (s->inst_tables() && !s->inst.lin && !s->layout_m && !fam && !adaptive) {
+    } else if (s->inst_tables() && !s->inst.fam() && !s->layout_m && !fam && !adaptive) {
         // goals, where the handle runs layout D: its constant-table kernel (compiled in for the 16-lane shapes that are, run-time
         // specialised otherwise -- wide systems included); trajectories, and goals without such a kernel: layout A. "Goal" means that
         // references AND bounds are constant over the horizon, each per instance or shared
@@ -233,9 +235,9 @@ LaunchPlan current_plan(const tinympc_solver *s) {
         case KernelId::D_JIT: {
             pl.layout = 'D';
             pl.jit = true;
-            const int ilin = pl.inst_lin ? s->inst.lin_nl : 0;  // (the ILIN form: the families' kernel whichever sides are enabled)
-            pl.workgroups = solve_jit_workgroups(s->W, s->nx, s->nu, s->N, ct, s->groups, fam || ilin, adaptive, pl.inst_refs, pl.inst_models, ilin);
-            pl.lds_bytes = solve_jit_lds_bytes(s->W, s->nx, s->nu, s->N, ct, fam || ilin, adaptive, pl.inst_refs, pl.inst_models, ilin);
+            const int ilin = pl.inst_lin ? s->ifam_nl() : 0;  // (the ILIN form: the families' kernel whichever sides are enabled)
+            pl.workgroups = solve_jit_workgroups(s->W, s->nx, s->nu, s->N, ct, s->groups, fam || ilin, adaptive, pl.inst_refs, pl.inst_models, ilin, ilin && s->inst.cones);
+            pl.lds_bytes = solve_jit_lds_bytes(s->W, s->nx, s->nu, s->N, ct, fam || ilin, adaptive, pl.inst_refs, pl.inst_models, ilin, ilin && s->inst.cones);
             break;
         }
         case KernelId::D_COMPILED:
@@ -288,7 +290,7 @@ int resolve_plan(tinympc_solver *s) {
     int rc;
     if (s->inst_tables()) {  // layout A or D's goal form, or a refusal: only the goal form's specialisation to decide
         int &known = s->inst.d_goal;
-        if (known < 0 && !s->inst.lin && s->layout_d && s->iref_goal() && !s->inst.models && !(s->W == 16 && !s->d_jit && solve_d_supported(s->nx, s->nu, s->N, true)) &&
+        if (known < 0 && !s->inst.fam() && s->layout_d && s->iref_goal() && !s->inst.models && !(s->W == 16 && !s->d_jit && solve_d_supported(s->nx, s->nu, s->N, true)) &&
             !s->families_active() && !s->st.adaptive_rho)
             known = solve_jit_supported(s->W, s->nx, s->nu, s->N, true, false, false, true) ? 1 : 0;
         // ... and the model form's (compiled in for the quadrotor N=50, specialised now otherwise; a refusal leaves the mode on layout A)
@@ -296,10 +298,11 @@ int resolve_plan(tinympc_solver *s) {
             s->inst.d_models = solve_jit_supported(s->W, s->nx, s->nu, s->N, true, false, false, false, true) ? 1 : 0;
         // ... and the linear-row form's, for the mode's row count (compiled in for the quadrotor N=20 with one row, specialised now
         // otherwise; a refusal leaves the mode on layout A). Another count is another specialisation: asked again.
-        if (s->inst.lin && s->inst.d_lin_nl != s->inst.lin_nl) s->inst.d_lin = -1;
+        if (s->inst.fam() && (s->inst.d_lin_nl != s->ifam_nl() || s->inst.d_lin_cones != s->inst.cones)) s->inst.d_lin = -1;
         if (s->inst.d_lin < 0 && lin_wants_d(s)) {
-            s->inst.d_lin_nl = s->inst.lin_nl;
-            s->inst.d_lin = solve_jit_supported(s->W, s->nx, s->nu, s->N, true, true, false, true, false, s->inst.lin_nl) ? 1 : 0;
+            s->inst.d_lin_nl = s->ifam_nl();
+            s->inst.d_lin_cones = s->inst.cones;
+            s->inst.d_lin = solve_jit_supported(s->W, s->nx, s->nu, s->N, true, true, false, true, false, s->ifam_nl(), s->inst.cones) ? 1 : 0;
         }
         return TINYMPC_OK;
     }
@@ -384,14 +387,18 @@ int launch(tinympc_solver *s, bool timed) {
     if ((rc = resolve_plan(s))) return rc;
     const LaunchPlan pl = current_plan(s);
     const bool fam = pl.families, adaptive = pl.adaptive;
-    if (s->inst.lin && !pl.inst_lin) {  // never a solve with shared rows in their place
+    if (s->inst.fam() && !pl.inst_lin) {  // never a solve with shared rows or slopes in their place
         const char *why = s->layout_m ? "for systems with nx+nu > 64"
                           : s->inst.models ? (s->inst.rho_verb ? "with per-instance models or rho (set_model_batch / set_rho_batch); tinympc_clear_model_batch returns to the shared model and rho"
                                                                : "with per-instance models (set_model_batch); tinympc_clear_model_batch returns to the shared model")
                           : adaptive ? "with adaptive rho"
                                      : "with more cones or rounds of overlapping cones than the generic kernel holds";
-        return fail(TINYMPC_ERR_UNSUPPORTED, "per-instance linear constraints (set_linear_constraints_batch) are not supported %s; "
-                    "tinympc_set_linear_constraints returns to shared rows", why);
+        if (!s->inst.lin)
+            return fail(TINYMPC_ERR_UNSUPPORTED, "per-instance cone slopes (set_cone_slopes_batch) are not supported %s; "
+                        "tinympc_set_cone_constraints returns to shared slopes", why);
+        return fail(TINYMPC_ERR_UNSUPPORTED, "per-instance linear constraints (set_linear_constraints_batch)%s are not supported %s; "
+                    "tinympc_set_linear_constraints returns to shared rows%s", s->inst.cones ? " and cone slopes (set_cone_slopes_batch)" : "", why,
+                    s->inst.cones ? ", tinympc_set_cone_constraints to shared slopes" : "");
     }
     if (s->inst_tables() && !pl.inst_refs) {  // never a solve with the shared references / bounds / model in their place
         const bool r = s->inst.refs(), b = s->inst.bounds, m = s->inst.models;
@@ -431,6 +438,7 @@ int launch(tinympc_solver *s, bool timed) {
         a.A = s->dA; a.B = s->dB; a.Pinf = s->dPinf; a.dK = s->ddK; a.dP = s->ddP; a.Xref = s->dXref; a.out = s->dadapt;
         HIP_TRY(launch_build_adapt(a, s->stream));
     }
+    if (pl.inst_lin && (rc = refresh_inst_families(s))) return rc;  // (the store's copy of the shared rows, its slope vectors)
     if ((fam || pl.inst_lin) && (rc = refresh_families(s))) return rc;  // (per-instance linear rows: the kernel reads cones and enable flags there)
     if (pl.inst_refs && (rc = refresh_inst_tables(s))) return rc;
     SolveParams p{};
@@ -481,7 +489,7 @@ int launch(tinympc_solver *s, bool timed) {
         s->refs_on_host = false;  // the kernel brings the tables and the device copies up to date
     }
     p.adapt = s->dadapt; p.rho_inst = s->drho_inst;
-    if (pl.inst_lin) { p.ilin = s->inst.lrows; p.ilin_nl = s->inst.lin_nl; }  // (share the slots of adapt / chunk_len, which this kernel never reads)
+    if (pl.inst_lin) { p.ilin = s->inst.lrows; p.ilin_nl = s->ifam_nl(); }  // (share the slots of adapt / chunk_len, which this kernel never reads)
     if (pl.inst_models) p.rho_inst = s->inst.mrho;  // (the model kernels read rho per instance: the handle's, or what tinympc_set_rho_batch set)
     if (pl.inst_refs) {
         p.iref_lr = pl.kernel == KernelId::A ? s->inst.lr_rows() : s->inst.lrg;
@@ -510,7 +518,7 @@ int launch(tinympc_solver *s, bool timed) {
             HIP_TRY(launch_solve_m(p, s->stream));
             break;
         case KernelId::D_JIT:  // (box path, families with everything in registers, or adaptive rho per lane)
-            HIP_TRY(launch_solve_jit(p, s->W, s->stream, pl.inst_models, pl.inst_lin ? s->inst.lin_nl : 0));
+            HIP_TRY(launch_solve_jit(p, s->W, s->stream, pl.inst_models, pl.inst_lin ? s->ifam_nl() : 0, pl.inst_lin && s->inst.cones));
             break;
         case KernelId::D_COMPILED:
             if (lean_applies(s, pl) && !p.x0_mirror && !p.u0_host && !p.refill_next)
@@ -593,6 +601,7 @@ int tinympc_get_jit_info(tinympc_solver *s, char *buf, int len) {
     if ((rc = jit_info_text(s, buf, len))) return rc;
     if (s->inst.tracks()) strncat(buf, " reference-track", (size_t)len - strlen(buf) - 1);  // (a half is in track mode)
     if (s->inst.lin) strncat(buf, " per-instance-linear", (size_t)len - strlen(buf) - 1);
+    if (s->inst.cones) strncat(buf, " per-instance-cones", (size_t)len - strlen(buf) - 1);
     return TINYMPC_OK;
 }
 
@@ -607,14 +616,18 @@ static int jit_info_text(tinympc_solver *s, char *buf, int len) {
         const char *words = w.c_str();
         if (pl.kernel == KernelId::D_JIT) {
             if ((rc = bind_device(s))) return rc;
-            const int ilin = pl.inst_lin ? s->inst.lin_nl : 0;
-            solve_jit_describe(s->W, s->nx, s->nu, s->N, true, ilin != 0, false, buf, (size_t)len, true, pl.inst_models, ilin);
+            const int ilin = pl.inst_lin ? s->ifam_nl() : 0;
+            solve_jit_describe(s->W, s->nx, s->nu, s->N, true, ilin != 0, false, buf, (size_t)len, true, pl.inst_models, ilin, ilin && s->inst.cones);
             strncat(buf, words, (size_t)len - strlen(buf) - 1);
             strncat(buf, " goal", (size_t)len - strlen(buf) - 1);
-        } else if (pl.inst_lin && lin_wants_d(s) && s->inst.d_lin == 0 && s->inst.d_lin_nl == s->inst.lin_nl) {  // asked for and refused: layout A, and why
+        } else if (pl.inst_lin && lin_wants_d(s) && s->inst.d_lin == 0 && s->inst.d_lin_nl == s->ifam_nl() && s->inst.d_lin_cones == s->inst.cones) {  // asked for and refused: layout A, and why
             if ((rc = bind_device(s))) return rc;
-            solve_jit_describe(s->W, s->nx, s->nu, s->N, true, true, false, buf, (size_t)len, true, false, s->inst.lin_nl);
+            solve_jit_describe(s->W, s->nx, s->nu, s->N, true, true, false, buf, (size_t)len, true, false, s->ifam_nl(), s->inst.cones);
             strncat(buf, words, (size_t)len - strlen(buf) - 1);
+        } else if (pl.inst_lin && lin_runs(s) && s->specialise_asked && s->layout_d && s->W == 16 && s->iref_goal() && family_structure(s).nround > 1) {
+            // asked for, and only the cones keep the mode off layout D: layout A, and why
+            snprintf(buf, (size_t)len, "refused(cones that share rows run in rounds: layout D's per-instance form takes cones without rounds) layout=%c%s",
+                     pl.layout, words);
         } else if (pl.inst_models && models_want_d(s) && s->inst.d_models == 0) {  // asked for and refused: layout A, and why
             if ((rc = bind_device(s))) return rc;
             solve_jit_describe(s->W, s->nx, s->nu, s->N, true, false, false, buf, (size_t)len, false, true);

@@ -180,6 +180,9 @@ int tinympc_session_begin(tinympc_solver *s) {
     if (s->inst.lin)
         return fail(TINYMPC_ERR_UNSUPPORTED, "session: per-instance linear constraints (set_linear_constraints_batch) are not supported; "
                     "tinympc_set_linear_constraints returns to shared rows");
+    if (s->inst.cones)
+        return fail(TINYMPC_ERR_UNSUPPORTED, "session: per-instance cone slopes (set_cone_slopes_batch) are not supported; "
+                    "tinympc_set_cone_constraints returns to shared slopes");
     if (s->st.max_iter < 1) return fail(TINYMPC_ERR_INVALID_INPUT, "session: max_iter must be >= 1");
     // Which resident kernel: layout F's (round 4) where the handle's launches run on layout F -- then the session's ticks are bit-identical
     // to launched ticks --, else the latency kernel's SESSION variant (layout C: box path, families up to N = 65 with disjoint cones).

@@ -5,7 +5,8 @@
 // No include guard: it is meant to be included once per kernel.
     // per-instance linear rows (with the per-instance rows of both kinds): the families' variant whose linear rows a_k | b_k | ||a_k||^2 are
     // this lane's INSTANCE's, from p.ilin, [group][3 nl][64] -- one 512-byte line per row vector and wavefront -- instead of the shared
-    // description's; cones, enable flags and everything else as in the families' variant
+    // description's; and whose cone SLOPES are the instance's too (tinympc_set_cone_slopes_batch), one vector per round in front of the
+    // group's rows. The cones' structure -- roles, last rows, round masks --, the enable flags and everything else as in the families' variant
     constexpr bool IFAM = E == SolveExt::InstFamilies;
     constexpr bool FAM = E == SolveExt::Families || IFAM, ADAPT = E == SolveExt::Adaptive;
     // per-instance references: this instance's linref rows and pNref from p.iref_lr / iref_pn (HBM / L2, the lane's own 512-byte line
@@ -124,7 +125,7 @@
                 const double *rd = q == 0 ? p.fam : p.fam + fam_round_offset(W, KT, q);
                 const double *ctq = q == 0 ? p.fam + 4 * W + M : rd + 2 * W + M;
                 r_role[q] = (int)rd[r];
-                r_mu[q] = rd[W + r];
+                r_mu[q] = IFAM ? p.ilin[(size_t)grp * inst_fam_group_doubles(p.ilin_nl) + (size_t)q * 64 + lane] : rd[W + r];
                 r_imu[q] = (r_mu[q] != 0.0) ? 1.0 / r_mu[q] : 0.0;
                 for (int k = 0; k < nxu; ++k)
                     if (ctq[(size_t)r * KT + k] != 0.0) r_head[q] = k;
@@ -134,21 +135,24 @@
         }
     }
     const int role = FAM ? (int)p.fam[r] : 0;
-    const double mu = FAM ? p.fam[W + r] : 0.0;
-    const double inv_mu = (mu != 0.0) ? 1.0 / mu : 0.0;  // (mu = 0: row in no cone)
     const bool famc = FAM && p.fam[2 * W + r] != 0.0, faml = FAM && p.fam[3 * W + r] != 0.0;
-    // (per-instance rows: row vector v of this wavefront at ilin + (grp 3 nl + v) 64, this lane's entry at + lane = j W + r; the shared
-    // description keeps its count in front of the vectors: base LB, vector stride LW -- lin_rows[LB + v LW + r] serves both)
-    constexpr int LW = IFAM ? 64 : W, LB = IFAM ? 0 : 1;
+    // (per-instance rows: this wavefront's block at ilin + grp inst_fam_group_doubles(nl) -- one slope vector per round, then row vector v
+    // at + (INST_FAM_SLOPE_ROWS + v) 64 --, this lane's entry at + lane = j W + r; the shared description keeps its count in front of the
+    // vectors: base LB, vector stride LW -- lin_rows[LB + v LW + r] serves both)
+    constexpr int LW = IFAM ? 64 : W, LB = IFAM ? INST_FAM_SLOPE_ROWS * 64 : 1;
     const double *lin_shared = p.fam + 4 * W + 3 * M;
     const int nl = IFAM ? p.ilin_nl : FAM ? (int)lin_shared[0] : 0;
-    const double *lin_rows = IFAM ? p.ilin + ((size_t)grp * 3 * nl * 64 + j * W) : lin_shared;
+    const double *lin_rows = IFAM ? p.ilin + ((size_t)grp * inst_fam_group_doubles(nl) + j * W) : lin_shared;
+    // (per-instance slopes: round q's vector of this wavefront leads its block, at lin_rows + q 64 -- an address without the row count)
+    const double mu = IFAM ? lin_rows[r] : FAM ? p.fam[W + r] : 0.0;
+    const double inv_mu = (mu != 0.0) ? 1.0 / mu : 0.0;  // (mu = 0: row in no cone)
     // the first FAM_REG_ROWS rows' coefficients in registers; problems with more rows (an equality constraint of five rows is
     // ten) read the rest from the family buffer (L2) where they are used
     double ak[FAM_REG_ROWS], bk[FAM_REG_ROWS], ink[FAM_REG_ROWS];  // ink = 1 / ||a_k||^2
 #pragma unroll
     for (int k = 0; k < (FAM && !RED ? FAM_REG_ROWS : 0); ++k) {
-        // (the per-instance store holds nl >= 1 rows, not the shared description's capacity: a register beyond nl repeats row 0, never used)
+        // (the per-instance store holds nl >= 1 rows, not the shared description's capacity: a register beyond nl repeats row 0, never used;
+        // a handle without any linear row holds one absent row there, a = 0, b = +inf, norm 1)
         const int kr = IFAM ? (k < nl ? k : 0) : k;
         ak[k] = lin_rows[LB + (size_t)(3 * kr + 0) * LW + r];
         bk[k] = lin_rows[LB + (size_t)(3 * kr + 1) * LW + r];
@@ -267,7 +271,7 @@
             for (int q = 1; q < nround; ++q) {                           // (uniform trip count; the masks of round q from L2)
                 const double *rd = p.fam + fam_round_offset(W, KT, q);
                 const int role_q = (int)rd[r];
-                const double mu_q = rd[W + r];
+                const double mu_q = IFAM ? lin_rows[q * 64 + r] : rd[W + r];
                 double cq[KT], tq[KT];
 #pragma unroll
                 for (int k = 0; k < KT; ++k) {

@@ -350,7 +350,7 @@ __device__ __forceinline__ bool wave_may_converge_d32(unsigned long long bad, un
 // arithmetic of an instance is that of the plain kernel (bit-identical results: tests/test_hip_parity.py); what changes is that
 // a wavefront's time is the sum of what its rows worked, not four times its slowest instance.
 template <int NX, int NU, int N, bool CT, int WPG, int VL, bool FAM = false, bool ADAPT = false, bool TWO_PER_SIMD = true, bool HOSTX = false,
-          bool REFILL = false, bool IGOAL = false, bool IMOD = false, int ILIN = 0>
+          bool REFILL = false, bool IGOAL = false, bool IMOD = false, int ILIN = 0, bool ICONE = false>
 #else
 // IGOAL: the per-instance goal form (every instance's references and bounds constant over the horizon; k_admm_solve_d_gbnd) -- the
 // four table constants lr_c, pNref, lo_c and hi_c come per lane from SolveParams::iref_lr / iref_pn / ibnd ([instance][16], ibnd's hi
@@ -360,16 +360,18 @@ template <int NX, int NU, int N, bool CT, int WPG, int VL, bool FAM = false, boo
 // cf, cb, c0 and the folded start value come from the instance's block. The per-lane arithmetic is the goal kernel's.
 // ILIN: the per-instance linear-row form of the families (tinympc_set_linear_constraints_batch after tinympc_prepare; ILIN = the mode's
 // row count nl, 0: off) -- the families' code reads a_k | b_k | 1/||a_k||^2 of the lane's own INSTANCE from SolveParams::ilin,
-// [group][3 nl][64], which every wavefront stages into an LDS region of its own; the shared sLin block does not exist. Cones, rounds,
-// role / mu and the enable flags stay those of the shared description, the four table constants come per lane as in the goal form
+// [group][slopes | 3 nl rows][64], which every wavefront stages into an LDS region of its own; the shared sLin block does not exist. The
+// ICONE (with ILIN): the cone slope mu is the lane's instance's too (tinympc_set_cone_slopes_batch: the store's round-0 vector; a handle
+// without linear rows runs the form with one absent row); without it the form's code is what it was before the slopes' half existed. Cones, role and the enable flags stay those of the shared description, the four table constants come per lane as in the goal form
 // (layout A's variant of the mode always runs on per-instance reference and clamp rows). The per-element arithmetic is FAM's.
 template <int NX, int NU, int N, bool CT, int WPG, int VL, bool FAM = false, bool ADAPT = false, bool TWO_PER_SIMD = true, bool HOSTX = false,
-          bool REFILL = false, bool IGOAL = false, bool IMOD = false, int ILIN = 0>
+          bool REFILL = false, bool IGOAL = false, bool IMOD = false, int ILIN = 0, bool ICONE = false>
 #endif
 __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double *smem) {
     static_assert(!(FAM && ADAPT), "adaptive rho and the constraint families exclude each other (as in the C ABI)");
     static_assert(!IMOD || (IGOAL && CT && !FAM && !ADAPT && !REFILL && !HOSTX && !TINY_LEAN),
                   "per-instance models: the goal form of the box path (its rows are always built per instance), plain sweeps");
+    static_assert(!ICONE || ILIN > 0, "per-instance cone slopes: with the per-instance rows' form (one absent row where there are none)");
     static_assert(ILIN == 0 || (ILIN > 0 && ILIN <= MAX_LIN_ROWS && FAM && IGOAL && CT && !ADAPT && !IMOD && !REFILL && !HOSTX && !TINY_LEAN),
                   "per-instance linear rows: the families' variant in the goal form (references and bounds constant over the horizon), plain sweeps");
 #if TINY_REFILL
@@ -462,7 +464,7 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
         // ... per wavefront: the 3 nl vectors of its own group, in the kernel's lane order as k_build_inst_lin wrote them (lanes beyond the
         // batch: a = 0, b = +inf, norm 1 -- the row is off); the third vector as its reciprocal, like the shared copy below
         if (grp_ok) {
-            const double *const rows_g = p.ilin + (size_t)grp * (3 * ILIN * 64);
+            const double *const rows_g = p.ilin + (size_t)grp * inst_fam_group_doubles(ILIN) + INST_FAM_SLOPE_ROWS * 64;
             for (int i = lane; i < 3 * ILIN * 64; i += 64) {
                 const double v = rows_g[i];
                 sLinW[i] = ((i >> 6) % 3 == 2) ? 1.0 / v : v;  // 1 / ||a_k||^2
@@ -546,6 +548,9 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
         }
         role = (int)p.fam[r];
         mu = p.fam[W + r];
+        // (ICONE: the lane's INSTANCE's slope, tinympc_set_cone_slopes_batch -- round 0's vector in front of the group's rows in SolveParams::ilin;
+        // read once, here: the iteration loop gains no load. The form takes cones without rounds.)
+        if constexpr (ICONE) mu = grp_ok ? p.ilin[(size_t)grp * inst_fam_group_doubles(ILIN) + lane] : mu;
         inv_mu = (mu != 0.0) ? 1.0 / mu : 0.0;  // (mu = 0: row in no cone)
         famc = p.fam[2 * W + r] != 0.0;
         faml = p.fam[3 * W + r] != 0.0;
@@ -1616,6 +1621,9 @@ TINY_KERNEL_NAME(const tinympc::SolveParams p) {
 #endif
     constexpr bool ADJ = TINY_JIT_ADAPT != 0;  // adaptive rho
     constexpr bool IMJ = TINY_JIT_IMOD != 0;  // per-instance models (implies the goal form)
+#ifndef TINY_JIT_ICONE
+#define TINY_JIT_ICONE 0
+#endif
     constexpr int ILJ = TINY_JIT_ILIN;  // per-instance linear rows: the mode's row count (with -DTINY_JIT_FAM=1 -DTINY_JIT_IGOAL=1); 0: off
     constexpr int VLJ = tinympc::d_vl(TINY_JIT_NU, TINY_JIT_N, CTJ, WPGJ, 4 * TINY_JIT_WPS, FAMJ, ADJ, IMJ, ILJ);
     static_assert(VLJ >= 0, "shape does not fit the layout-D plan");
@@ -1630,7 +1638,7 @@ TINY_KERNEL_NAME(const tinympc::SolveParams p) {
 #define TINY_JIT_IGOAL 0
 #endif
     tinympc::k_admm_solve_d_body<TINY_JIT_NX, TINY_JIT_NU, TINY_JIT_N, CTJ, WPGJ, VLJ, FAMJ, ADJ, TINY_JIT_WPS == 2, false, false,
-                                 TINY_JIT_IGOAL != 0 || IMJ, IMJ, ILJ>(p, smem_jit);
+                                 TINY_JIT_IGOAL != 0 || IMJ, IMJ, ILJ, TINY_JIT_ICONE != 0>(p, smem_jit);
 #endif
 }
 namespace tinympc {

@@ -461,6 +461,49 @@ class TinyMPC:
         if nlu:
             self.settings["en_input_linear"] = True
 
+    def set_cone_slopes_batch(self, cx, cu, first: int = 0):
+        """Per-instance cone slopes for instances first, first+1, ... on the cone structure set_cone_constraints() installed: numpy arrays
+        of shape (ncx, count) / (ncu, count) in the order of the cone list -- or contiguous float64 CUDA tensors (count, ncx) /
+        (count, ncu); a side without cones is None. The structure belongs to the batch, the slopes to the instance: instance first+b
+        solves what a single-instance solver would after set_cone_constraints(Acx, qcx, cx[:, b], Acu, qcu, cu[:, b]). Instances the
+        call does not name keep the shared slopes; set_cone_constraints() returns every instance to shared slopes. Changes no enable
+        flag and keeps the ADMM state: re-send the slopes between two mpc_step() ticks. On a single-instance solver the arrays may lack
+        the count axis."""
+        self._check_setup()
+        sides = []
+        for c, name in ((cx, "x"), (cu, "u")):
+            empty = c is None or (hasattr(c, "numel") and c.numel() == 0) or (not hasattr(c, "numel") and np.asarray(c).size == 0)
+            if empty:
+                sides.append((None, 0, None, False, None))
+            elif hasattr(c, "data_ptr") and getattr(c, "is_cuda", False):
+                import torch
+                if c.dim() == 1 and self.batch == 1:
+                    c = c.reshape(1, -1)
+                if c.dtype != torch.float64 or not c.is_contiguous() or c.dim() != 2:
+                    raise TinyMPCError(_lib.ERR_INVALID_INPUT, "cone slopes on the device must be a contiguous float64 tensor of shape (count, nc%s), "
+                                       "got %s %s" % (name, c.dtype, tuple(c.shape)))
+                sides.append((C.c_void_p(c.data_ptr()), int(c.shape[1]), int(c.shape[0]), True, c))
+            else:
+                a = np.asarray(c, dtype=np.float64)
+                if a.ndim == 1 and self.batch == 1:
+                    a = a.reshape(-1, 1)
+                if a.ndim != 2:
+                    raise TinyMPCError(_lib.ERR_INVALID_INPUT, "cone slopes must be nc%s x count, got %s" % (name, a.shape))
+                a = _f(a)
+                sides.append((_p(a), int(a.shape[0]), int(a.shape[1]), False, a))
+        (px, ncx, nbx, dx, keep_x), (pu, ncu, nbu, du, keep_u) = sides
+        if ncx and ncu and (nbx != nbu or dx != du):
+            raise TinyMPCError(_lib.ERR_INVALID_INPUT, "cone slopes: both sides must have the same count and be on the same side of the bus")
+        if not ncx and not ncu:
+            raise TinyMPCError(_lib.ERR_INVALID_INPUT, "cone slopes: no slopes on either side")
+        on_device = dx if ncx else du
+        count = nbx if ncx else nbu
+        if on_device:
+            import torch
+            torch.cuda.current_stream((keep_x if ncx else keep_u).device).synchronize()  # (the set_x0_batch contract)
+        f = self._L.tinympc_set_cone_slopes_batch_device if on_device else self._L.tinympc_set_cone_slopes_batch
+        _lib.check(f(self._h, px, ncx, pu, ncu, int(first), int(count)))
+
     def set_model_batch(self, A, B, Q, R, fdyn=None, first: int = 0):
         """Per-instance models for instances first, first+1, ...: numpy arrays of shape (nx, nx, count), (nx, nu, count), (nx, nx, count),
         (nu, nu, count) and, optionally, fdyn (nx, count) -- or contiguous float64 CUDA tensors with the same memory layout, (count, nx, nx)
@@ -723,7 +766,9 @@ class TinyMPC:
         handle: a batch with per-instance models (set_model_batch, before or after this call) then runs on layout D's per-instance
         model form -- nx+nu <= 16, references and bounds constant over the horizon, a horizon that form holds -- instead of layout A,
         and a batch with per-instance linear rows (set_linear_constraints_batch, before or after this call) on layout D's per-instance
-        linear-row form under the same conditions (launch_info()["layout"] and jit_info() say which)."""
+        linear-row form under the same conditions (launch_info()["layout"] and jit_info() say which). Per-instance cone slopes
+        (set_cone_slopes_batch) are the other half of that mode and run on the same form, whose cone slope is always the instance's;
+        cones that share rows stay on layout A."""
         self._check_setup()
         self._push_settings()
         _lib.check(self._L.tinympc_prepare(self._h))
