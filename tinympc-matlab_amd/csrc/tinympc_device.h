@@ -550,6 +550,7 @@ hipError_t launch_solve_d_lean(const SolveParams &p, hipStream_t stream);    // 
 hipError_t launch_solve_d_lean_start(const SolveParams &p, hipStream_t stream);  // tinympc_lstart_d.hip (accumulator starts from LDS, control hoisted)
 hipError_t launch_solve_d_lean_trim(const SolveParams &p, hipStream_t stream);   // tinympc_ltrim_d.hip (... and the lean rounds' d stores without the EXEC round trip)
 hipError_t launch_solve_d_lean_share(const SolveParams &p, hipStream_t stream);  // tinympc_lshare_d.hip (... and d and the slack sharing the register slots)
+hipError_t launch_solve_d_lean_park(const SolveParams &p, hipStream_t stream);   // tinympc_lpark_d.hip (... and more register slots inside a run; quadrotor N=50, constant tables)
 int solve_d_workgroups(int nu, int N, bool const_tables, int groups);
 size_t solve_d_lds_bytes(int nu, int N, bool const_tables);  // per workgroup
 int solve_d_resident_workgroups(int wpg);  // workgroups of `wpg` wavefronts the device holds at two wavefronts per SIMD (slot refill)

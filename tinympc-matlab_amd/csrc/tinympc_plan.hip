@@ -373,8 +373,33 @@ static bool lean_share_applies() {
     const char *env = getenv("TINYMPC_LEAN_SHARE");
     return lean_trim_applies() && (!env || atoi(env) != 0);
 }
+// ... and, for the one shape that has LDS slots (quadrotor N=50, constant tables), with twelve of them turned into register slots
+// inside a run of lean rounds (tinympc_lpark_d.hip; bit-identical again) -- where the run is long enough to pay for its entry and exit.
+// A run of n rounds is n - 1 shared rounds, each 48 LDS instructions shorter than the shared kernels' (72 to 110 SIMD-cycles at the 1.5
+// to 2.3 cycles per LDS instruction of docs/NOTEBOOK.md sections 14 and 18), and one last round; entry and exit cost 12 more reads of
+// d, three stores and three reads of the parked values and one more wait for them, about 100 to 150 cycles: even at n = 3. The
+// threshold is twice that and one more, PARK_MIN_RUN = 6 (at least 360 cycles saved against at most 150 spent); shorter runs keep the
+// shared kernels. The length is that of the launch's first run, as the kernel's loop forms it: check_termination - 1 with tolerances
+// that can be met, else up to the last check of the launch (max_iter - 1 where max_iter is a multiple of the interval).
+// TINYMPC_LEAN_PARK=0 selects the kernels of tinympc_lshare_d.hip.
+constexpr int PARK_MIN_RUN = 6;
+static int first_lean_run(const tinympc_solver *s) {
+    const int max_iter = s->st.max_iter, ct = s->st.check_termination;
+    const bool reachable = s->st.abs_pri_tol > 0.0 && s->st.abs_dua_tol > 0.0;
+    if (ct > 0 && reachable) return ct - 1 < max_iter ? ct - 1 : max_iter;
+    const int last_check = ct > 0 ? (max_iter / ct) * ct : 0;
+    return last_check > 0 ? last_check - 1 : max_iter;
+}
+static bool lean_park_applies(const tinympc_solver *s) {
+    const char *env = getenv("TINYMPC_LEAN_PARK");
+    if (!lean_share_applies() || (env && atoi(env) == 0)) return false;
+    if (!(s->nx == 12 && s->nu == 4 && s->N == 50)) return false;
+    return first_lean_run(s) >= PARK_MIN_RUN;
+}
 static const char *lean_words(const tinympc_solver *s, const LaunchPlan &pl) {
+    const bool ct = s->tables_const() || (pl.inst_refs && pl.kernel != KernelId::A);  // (SolveParams::const_tables)
     return !lean_applies(s, pl)   ? ""
+           : ct && lean_park_applies(s) ? " lean lds-start trim share park"
            : lean_share_applies() ? " lean lds-start trim share"
            : lean_trim_applies()  ? " lean lds-start trim"
            : lean_start_applies() ? " lean lds-start"
@@ -522,7 +547,8 @@ int launch(tinympc_solver *s, bool timed) {
             break;
         case KernelId::D_COMPILED:
             if (lean_applies(s, pl) && !p.x0_mirror && !p.u0_host && !p.refill_next)
-                HIP_TRY(lean_share_applies()   ? launch_solve_d_lean_share(p, s->stream)
+                HIP_TRY(p.const_tables && lean_park_applies(s) ? launch_solve_d_lean_park(p, s->stream)
+                        : lean_share_applies() ? launch_solve_d_lean_share(p, s->stream)
                         : lean_trim_applies()  ? launch_solve_d_lean_trim(p, s->stream)
                         : lean_start_applies() ? launch_solve_d_lean_start(p, s->stream)
                                                : launch_solve_d_lean(p, s->stream));

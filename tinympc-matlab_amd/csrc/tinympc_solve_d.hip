@@ -158,6 +158,48 @@
 #if TINY_LEAN_SHARE && !(TINY_LEAN_TRIM && TINY_TRIM_DSTORE)
 #error "TINY_LEAN_SHARE: a variant of the trimmed lean kernels (with their dstore addresses)"
 #endif
+// ... and the shared kernels have a textual variant (TINY_LEAN_PARK: tinympc_lpark_d.hip sets it with the four above; new symbols
+// k_admm_solve_d_lean_park, k_admm_solve_d_gbnd_lean_park, launch_solve_d_lean_park; quadrotor N=50 with constant tables only -- the
+// other shapes have no LDS slot). The kernel stands at 254 VGPRs, which is why VL is 25, but the shared round -- the loop a run spends
+// its time in -- names only 217 of them: the rest hold temporaries of the other round bodies and values the loop does not use. So
+// INSIDE a run a second split holds: VLR = VL - TINY_PARK_SLOTS LDS slots, and the slots VLR..VL-1 are register slots of a second
+// array, Vx[], that lives from the run's entry to the last round's forward sweep. Each converted slot saves the four LDS instructions
+// a round spends on it (slack store and d read going forward, slack read and d store going backward).
+//   entry     behind the control block and the dstore addresses: d_s of ALL NS - VLR register slots comes from LDS into Vr[] and Vx[].
+//   shared    (form 3) a slot >= VLR takes the register-slot text of TINY_LEAN_SHARE, on Vx[s-VLR] below VL; the boundary block is VLR.
+//   last      (form 4) the forward step of a converted slot takes Vx[q-VLR] as its d operand and hands its clamp to the slot's LDS slack
+//             row (fwd_lds_start's text and the store that always followed it); behind the forward sweep Vx[] is dead. The backward
+//             sweep is the trimmed kernels', on VL: Vr[] is the slack, LDS holds all of d and the slack of the slots below VL.
+// Why this is the same computation. (1) The old slack of a converted slot is dead at entry for the reason Vr[]'s is: the first forward
+// sweep of a run writes v_s without reading it -- into Vx[] (form 3) or into the LDS row (form 4) --, and the control block in front of
+// the run has written every pending instance back (vget reads the LDS row there, before the entry). Between the entry and the last
+// round's forward sweep the LDS slack rows of the converted slots are stale and nothing reads them: a shared backward block takes v_s of
+// a slot >= VLR from its register, and nothing but sweeps runs inside a run. (2) The d rows VLR..NS-1 in LDS are not read inside a run
+// either (forward steps of register slots issue no d read); the last round's backward sweep rewrites all of them for live instances.
+// (3) Instances that are not live: as with Vr[], their lanes' Vx[] hold what a zombie's sweeps computed, and nothing reads it -- Vx[] is
+// dead behind the run; their LDS slack rows of converted slots are written by the last round's forward sweep exactly as every lean round
+// of the parent wrote them (the store is unconditional there too); their d rows below VLR are never written (aDw). (4) Dump lanes: a
+// dump lane writes row s-1 or s-2 of a live column at a block s that stores. In a shared round those are the blocks below VLR, so the
+// dump rows are -2..VLR-2, each overwritten by its own column's lane later in the same sweep (or spare): `dstore`'s argument with VLR
+// for VL. In the last round every block stores, as in the parent. (5) Parked values. The loop needs 217 + 24 = 241 registers; of the
+// values that live across a run without being used in it, three doubles per lane -- the residual snapshot snap_pri, snap_dua and the
+// pair (status, it_done) -- go to LDS at the entry and come back in the last round, between its forward sweep (behind which Vx[] is
+// dead) and its backward sweep; three more are rebuilt where they are used (the 64-bit constants of the "can still converge" test:
+// the test on 32-bit halves; the address of knot 0's stale copy and the instance's 64-bit index: from an opaque copy of the lane).
+// The parked rows are the d rows VLR..VLR+11 of the wavefront taken as [3][64 lanes]: the entry has just read them into registers,
+// no shared round reads or writes them (2), and the last round's backward sweep, which rewrites them for every live instance, runs
+// behind the reload. Instances that are not live keep parked bits in those rows of their d. Nothing reads them: their write-back
+// happened in front of the entry (pending is false inside a run), their lanes' arithmetic is never read (as in TINY_LEAN_SHARE; a DPP
+// chain stays inside its 16-lane row), and an instance that stops being live LATER was live in this run and had its rows rewritten.
+#ifndef TINY_LEAN_PARK
+#define TINY_LEAN_PARK 0
+#endif
+#if TINY_LEAN_PARK && !TINY_LEAN_SHARE
+#error "TINY_LEAN_PARK: a variant of the shared lean kernels"
+#endif
+#if TINY_LEAN_PARK && !defined(TINY_PARK_SLOTS)
+#define TINY_PARK_SLOTS 12  // LDS slots that become register slots inside a run (VL - VLR)
+#endif
 
 #define TINY_STR2(x) #x
 #define TINY_STR(x) TINY_STR2(x)
@@ -513,6 +555,12 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
 
     // ---- register-resident state
     double G[NS], G0, Vr[NVR > 0 ? NVR : 1], V0;
+#if TINY_LEAN_PARK
+    // the split inside a run of lean rounds: slots VLR..VL-1 are register slots there (Vx[], live from a run's entry to its last forward sweep)
+    static_assert(VL > TINY_PARK_SLOTS && TINY_PARK_SLOTS > 0, "the converted slots are LDS slots, and slot 0 stays one");
+    constexpr int VLR = VL - TINY_PARK_SLOTS, NVX = VL - VLR;
+    double Vx[NVX];
+#endif
     if (cold) {
         static_for<0, NS>([&](auto S) { G[S.value] = 0.0; });
         static_for<0, NVR>([&](auto S) { Vr[S.value] = 0.0; });
@@ -718,6 +766,32 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
     const int max_iter = p.max_iter;
 #if TINY_TRIM_DSTORE
     unsigned aDw = aD;  // where this lane's d stores of a lean round go: set in front of every run of lean rounds
+#endif
+#if TINY_LEAN_PARK
+    // What lives across a run of lean rounds without being used in it goes to LDS at the run's entry and comes back in the run's last
+    // round, between its forward sweep (behind which Vx[] is dead) and its backward sweep: the registers are free inside the run. The
+    // place is the rows VLR..NS-1 of the wavefront's d, taken as [PARK_ROWS][64 lanes]: the entry has just read them into Vr[] / Vx[],
+    // no shared round reads or writes them (register slots; the dump rows of the blocks that still store lie below VLR - 1), and the
+    // last round's backward sweep, which rewrites them for every live instance, comes behind the reload. (Instances that are not live
+    // keep the parked bits in those rows: their write-back is done, and nothing reads what their lanes compute from them.)
+    constexpr int PARK_ROWS = 3;
+    static_assert(PARK_ROWS * 64 <= (NS - VLR) * DS, "the parked rows fit into the d rows of the run's register slots");
+    auto park = [&]() __attribute__((always_inline)) {
+        const unsigned aP = lds_addr(sD + VLR * DS + lane);
+        lds_write_async<0 * 512>(aP, snap_pri);
+        lds_write_async<1 * 512>(aP, snap_dua);
+        lds_write_async<2 * 512>(aP, __hiloint2double(status, it_done));
+    };
+    auto unpark = [&]() __attribute__((always_inline)) {
+        const unsigned aP = lds_addr(sD + VLR * DS + lane);
+        double p0 = lds_read_async<0 * 512>(aP), p1 = lds_read_async<1 * 512>(aP), p2 = lds_read_async<2 * 512>(aP);
+        lds_wait();
+        asm volatile("" : "+v"(p0), "+v"(p1), "+v"(p2));  // (the reads are consumed behind their wait)
+        snap_pri = p0;
+        snap_dua = p1;
+        status = __double2hiint(p2);
+        it_done = __double2loint(p2);
+    };
 #endif
 #if TINY_LEAN
     // One round of the loop below, in two forms: LEAN_ = true without residuals, false the plain kernel's. Returns true when the solve
@@ -955,12 +1029,22 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
                 const bool bad = !((pri < p.abs_pri_tol) && (dua * rho < p.abs_dua_tol));
 #if TINY_REFILL
                 may = __builtin_amdgcn_readfirstlane((int)wave_may_converge_d(__ballot(bad), __ballot(REFILL ? chk : active))) != 0;
+#elif TINY_LEAN_PARK
+                // (the test on 32-bit halves: the 64-bit form keeps two 64-bit constants in vector registers across the run)
+                may = __builtin_amdgcn_readfirstlane((int)wave_may_converge_d32(__ballot(bad), __ballot(active))) != 0;
 #else
                 may = __builtin_amdgcn_readfirstlane((int)(ILIN ? wave_may_converge_d32(__ballot(bad), __ballot(active)) : wave_may_converge_d(__ballot(bad), __ballot(active)))) != 0;
 #endif
             }
 #if TINY_REFILL
             if (TINY_RARE(may) && is_x && active) gV1u[REFILL ? row_offset(cur) : (unsigned)lane] = V0;
+#elif TINY_LEAN_PARK
+            if (TINY_RARE(may) && is_x && active) {  // (as below, the address built in the rare path: no 64-bit pointer lives across the run)
+                unsigned lo = (unsigned)lane;
+                double *base = gV1u;
+                asm volatile("" : "+v"(lo), "+s"(base));
+                base[lo] = V0;
+            }
 #else
             if (TINY_RARE(may) && is_x && active) gV1u[(unsigned)lane] = V0;  // (active: see the stale copy of the slots below)
 #endif
@@ -978,7 +1062,10 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
         // LDS operands of a step (its d, and vold of its slot if that lives in LDS) are requested right before the
         // PREVIOUS step's block and retired by the wait behind that block (lds_reads_landed, inside the Step functions).
         double xcur = x0v;
-#if TINY_LEAN_SHARE
+#if TINY_LEAN_PARK
+        // (as below; slot 0 is an LDS slot inside a run too)
+        double dcur = lds_read_async<0>(aD), vcur = 0.0;
+#elif TINY_LEAN_SHARE
         // (a shared step of a register slot has its d in the slot's register: no read is issued for it)
         double dcur = 0.0, vcur = 0.0;
         if constexpr (!(SH_F && VL == 0)) dcur = lds_read_async<0>(aD);
@@ -1004,7 +1091,10 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
         auto fstep = [&](auto S) {
             constexpr int q = decltype(S)::value;
             double dn = 0.0, vn = 0.0, lon = lo_c, hin = hi_c;
-#if TINY_LEAN_SHARE
+#if TINY_LEAN_PARK
+            // (the register slots of a run start at VLR: no d read from there on)
+            if constexpr (q + 1 < NS && !(SH_F && q + 1 >= VLR)) dn = lds_read_async<(q + 1) * DS * 8>(aD);
+#elif TINY_LEAN_SHARE
             if constexpr (q + 1 < NS && !(SH_F && q + 1 >= VL)) dn = lds_read_async<(q + 1) * DS * 8>(aD);
 #else
             if constexpr (q + 1 < NS) dn = lds_read_async<(q + 1) * DS * 8>(aD);
@@ -1028,6 +1118,21 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
             double snew_q;
 #if TINY_LEAN
             if constexpr (LEANI) {  // S1 + D1 without R1's maxima: the clamp goes straight into the slot
+#if TINY_LEAN_PARK
+                if constexpr (SH_F && q >= VLR && q < VL) {
+                    // A converted slot: its d is in Vx[q-VLR]. In a shared round that register takes the clamp (the register-slot text); in
+                    // the last round of a run the clamp goes to the slot's LDS row, where the backward sweep on VL reads it.
+                    if constexpr (SH_B) {
+                        xcur = Step::fwd_reg_start(xcur, Vx[q - VLR], m, acur, locur, hicur, G[q], Vx[q - VLR]);
+                        snew_q = Vx[q - VLR];
+                    } else {
+                        double vnew;
+                        xcur = Step::fwd_lds_start(xcur, Vx[q - VLR], m, acur, locur, hicur, G[q], vnew);
+                        lds_write_async<q * 512>(aV, vnew);
+                        snew_q = vnew;
+                    }
+                } else
+#endif
                 if constexpr (q >= VL) {
 #if TINY_LEAN_SHARE
                     // (shared: the slot's register is the d operand and takes the clamp behind the chain's last read of it)
@@ -1115,6 +1220,8 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
                         const bool bad = !((pri < p.abs_pri_tol) && (dua * rho < p.abs_dua_tol));
 #if TINY_REFILL
                         may = __builtin_amdgcn_readfirstlane((int)wave_may_converge_d(__ballot(bad), __ballot(REFILL ? chk : active))) != 0;
+#elif TINY_LEAN_PARK
+                        may = __builtin_amdgcn_readfirstlane((int)wave_may_converge_d32(__ballot(bad), __ballot(active))) != 0;
 #else
                         may = __builtin_amdgcn_readfirstlane((int)(ILIN ? wave_may_converge_d32(__ballot(bad), __ballot(active)) : wave_may_converge_d(__ballot(bad), __ballot(active)))) != 0;
 #endif
@@ -1148,6 +1255,9 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
         }
 #else
         if (active) it_done = it1;  // admm.cpp:143
+#endif
+#if TINY_LEAN_PARK
+        if constexpr (SH_F && !SH_B) unpark();  // (the last round of a run: Vx[] is dead from here on)
 #endif
 
         // ---------------- adaptive rho (admm.cpp:147-174), as in k_admm_solve_adapt
@@ -1280,6 +1390,10 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
             }
             // slack operand of a block's tail: a register, or an LDS read issued one block ahead
             auto vreq = [&](auto S) -> double {
+#if TINY_LEAN_PARK
+                if constexpr (SH_B && decltype(S)::value >= VLR && decltype(S)::value < VL) return Vx[decltype(S)::value - VLR];
+                else
+#endif
                 if constexpr (decltype(S)::value >= VL) return Vr[decltype(S)::value - VL];
                 else return lds_read_async<decltype(S)::value * 512>(aV);
             };
@@ -1306,7 +1420,26 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
                 if constexpr (s >= 2) v2n = vreq(std::integral_constant<int, s3>{});
                 const double lr2 = lr_of(std::integral_constant<int, s2>{});
                 const double lrmc2 = is_x ? lr2 + cb : cb;
-#if TINY_LEAN_SHARE
+#if TINY_LEAN_PARK
+                if constexpr (SH_B && s >= VLR) {
+                    // The shared block below with the run's split: the register of slot s is Vr[s-VL], or Vx[s-VLR] for a converted slot;
+                    // the boundary block is VLR (it writes `an` into the scratch accumulator and the LDS slots go on as before).
+                    constexpr bool AN_REG = s - 1 >= VLR;
+                    constexpr int sn = AN_REG ? s - 1 : s;
+                    double &a_s = s >= VL ? Vr[s >= VL ? s - VL : 0] : Vx[s >= VL ? 0 : s - VLR];
+                    double &an_s = sn >= VL ? Vr[sn >= VL ? sn - VL : 0] : Vx[sn >= VL ? 0 : sn - VLR];
+                    double an_l, rn;
+                    static_assert(FOLD, "constant tables only");
+                    if constexpr (AN_REG) Step::bwd_fold(a_s, px, rcur, m, v2cur, G[s2], rhom, lrmc_f, an_s, rn);
+                    else Step::bwd_fold(a_s, px, rcur, m, v2cur, G[s2], rhom, lrmc_f, an_l, rn);
+                    if constexpr (!AN_REG) acc = an_l;
+                    px = a_s;
+                    rcur = rnext;
+                    rnext = rn;
+                    v2cur = v2n;
+                    return;
+                }
+#elif TINY_LEAN_SHARE
                 if constexpr (SH_B && s >= VL) {
                     // The shared block of a register slot: Vr[s-VL] holds the start value (its v_s was consumed two blocks ago) and
                     // becomes [p_s | d_s]; the tail's start value for block s-1 goes into that slot's register where it has one. No d
@@ -1394,7 +1527,18 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
             // Entry of a run: d_s of the register slots from LDS into the slots' registers (the old slack is dead, see the top of the
             // file), once per run; then the shared rounds and, last, the round whose backward sweep puts everything back in place.
             static_for<0, NVR>([&](auto S) { Vr[S.value] = lds_read_async<(VL + S.value) * DS * 8>(aD); });
+#if TINY_LEAN_PARK
+            // (... and of the slots that are register slots inside the run only; their old slack in LDS is dead in the same way)
+            static_for<0, NVX>([&](auto S) { Vx[S.value] = lds_read_async<(VLR + S.value) * DS * 8>(aD); });
             lds_wait();
+            static_for<0, NVX>([&](auto S) {
+                double &vx = Vx[decltype(S)::value];
+                asm volatile("" : "+v"(vx));
+            });
+            park();
+#else
+            lds_wait();
+#endif
             static_for<0, NVR>([&](auto S) {  // (the reads are consumed behind their wait)
                 double &vr = Vr[decltype(S)::value];
                 asm volatile("" : "+v"(vr));
@@ -1464,6 +1608,22 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
         ck[7] = (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) | ((unsigned long long)__builtin_amdgcn_s_getreg((3 << 11) | 20) << 32);  // HW_ID, XCC_ID
     }
 #endif
+#if TINY_LEAN_PARK
+    // (the instance's number again, from an opaque copy of the lane: the 64-bit index does not live across the iteration loop)
+    int lane_e = lane;
+    asm volatile("" : "+v"(lane_e));
+    const long inst_e = grp * IPW + (lane_e >> 4);
+    if (inst_ok && r == 0) {
+        p.istats[inst_e * 2 + 0] = it_done;
+        p.istats[inst_e * 2 + 1] = status;
+        if (res_valid) {
+            p.dstats[inst_e * 4 + 0] = res_px;
+            p.dstats[inst_e * 4 + 1] = res_dx;
+            p.dstats[inst_e * 4 + 2] = res_pu;
+            p.dstats[inst_e * 4 + 3] = res_du;
+        }
+    }
+#else
     if (inst_ok && r == 0) {
         if constexpr (ADAPT) p.rho_inst[inst] = rho;
         p.istats[inst * 2 + 0] = it_done;
@@ -1475,12 +1635,19 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
             p.dstats[inst * 4 + 3] = res_du;
         }
     }
+#endif
 }
 
 #if TINY_LEAN
 // (the lean translation unit, tinympc_lean_d.hip: the plain kernel and its per-instance goal form with lean sweeps; tinympc_plan.hip
 // decides when -- lean_applies; tinympc_lstart_d.hip: the same under the names of its variant)
-#if TINY_LEAN_SHARE
+#if TINY_LEAN_PARK
+#define k_admm_solve_d_lean k_admm_solve_d_lean_park
+#define k_admm_solve_d_gbnd_lean k_admm_solve_d_gbnd_lean_park
+#define launch_solve_d_lean launch_solve_d_lean_park
+// (the LDS plan is the shared kernels': no row moves, the run's split only changes which instructions touch them)
+static_assert(d_vl(4, 50, true, 4) == 25, "quadrotor N=50: 25 slack slots in LDS with four wavefronts per workgroup");
+#elif TINY_LEAN_SHARE
 #define k_admm_solve_d_lean k_admm_solve_d_lean_share
 #define k_admm_solve_d_gbnd_lean k_admm_solve_d_gbnd_lean_share
 #define launch_solve_d_lean launch_solve_d_lean_share
@@ -1543,12 +1710,19 @@ static hipError_t launch_d_one(const SolveParams &p, hipStream_t stream) {
     }
 }
 
+#if TINY_LEAN_PARK
+hipError_t launch_solve_d_lean(const SolveParams &p, hipStream_t stream) {  // (the one shape with LDS slots, constant tables: see the plan)
+    if (p.nx == 12 && p.nu == 4 && p.N == 50 && p.const_tables) return launch_d_one<12, 4, 50, true>(p, stream);
+    return hipErrorInvalidValue;
+}
+#else
 hipError_t launch_solve_d_lean(const SolveParams &p, hipStream_t stream) {  // (the shapes of TINY_D_SHAPES in the plain translation unit)
     if (p.nx == 12 && p.nu == 4 && p.N == 50) return p.const_tables ? launch_d_one<12, 4, 50, true>(p, stream) : launch_d_one<12, 4, 50, false>(p, stream);
     if (p.nx == 4 && p.nu == 1 && p.N == 20) return p.const_tables ? launch_d_one<4, 1, 20, true>(p, stream) : launch_d_one<4, 1, 20, false>(p, stream);
     if (p.nx == 4 && p.nu == 1 && p.N == 10) return p.const_tables ? launch_d_one<4, 1, 10, true>(p, stream) : launch_d_one<4, 1, 10, false>(p, stream);
     return hipErrorInvalidValue;
 }
+#endif
 #else  // the plain and the slot-refill kernels, their launchers, the run-time specialised entry point
 #ifndef TINY_JIT
 #if TINY_REFILL

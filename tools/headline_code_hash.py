@@ -18,7 +18,10 @@ The lean-start kernel with the d stores of its lean rounds going through a per-l
     python tools/headline_code_hash.py --record-lean-trim    write RECORD_LEAN_TRIM (after the A/B)
 The trimmed kernel with d and the slack sharing the register slots inside a run of lean rounds (k_admm_solve_d_lean_share<12, 4, 50, true, 4, 25>,
 tinympc_lshare_d.hip: what the headline runs now) has the fifth, RECORD_LEAN_SHARE.
-    python tools/headline_code_hash.py --record-lean-share   write RECORD_LEAN_SHARE (after the A/B)"""
+    python tools/headline_code_hash.py --record-lean-share   write RECORD_LEAN_SHARE (after the A/B)
+The shared kernel with twelve LDS slots turned into register slots inside a run of lean rounds (k_admm_solve_d_lean_park<12, 4, 50, true, 4, 25>,
+tinympc_lpark_d.hip: what the headline runs now) has the sixth, RECORD_LEAN_PARK.
+    python tools/headline_code_hash.py --record-lean-park    write RECORD_LEAN_PARK (after the A/B)"""
 import hashlib
 import json
 import os
@@ -63,6 +66,14 @@ LEAN_SHARE_MEASURED = ("kernel 1.375 ms avg (8,192 x 200 iterations, bench.py on
                        "the parent build's trimmed kernel (7,091 instructions, headline_kernel_code_d_lean_trim.json): 1.3689 vs 1.3844 ms (-1.1 %), and 1.3707 vs "
                        "1.3888 ms at TINY_D_PAD=1, four interleaved rounds each, ranges disjoint; 68.0 M against 87.5 M LDS and 763.7 M against 763.7 M VALU "
                        "instructions per launch; profiles/d_lean_share_headline_ab.txt")
+KERNEL_LEAN_PARK = "_ZN7tinympc24k_admm_solve_d_lean_parkILi12ELi4ELi50ELb1ELi4ELi25EEEvNS_11SolveParamsE"
+SOURCE_LEAN_PARK = "tinympc_lpark_d.hip"
+RECORD_LEAN_PARK = os.path.join(ROOT, "tests", "golden", "headline_kernel_code_d_lean_park.json")
+# what was measured for its recorded code (profiles/d_lean_park_headline_ab.txt)
+LEAN_PARK_MEASURED = ("kernel 1.371 ms avg (8,192 x 200 iterations, bench.py on MI355X; profiles/d_lean_park_kernel_stats.csv; the parent's 1.410 on the same box); tools/headline_ab.py, "
+                      "one box, against the parent build's shared kernel (9,241 instructions, headline_kernel_code_d_lean_share.json): 1.3563 vs 1.3738 ms (-1.3 %), and 1.3559 vs "
+                      "1.3742 ms at TINY_D_PAD=1, four interleaved rounds each, ranges disjoint; 48.5 M against 68.0 M LDS and 763.7 M against 763.7 M VALU "
+                      "instructions per launch; profiles/d_lean_park_headline_ab.txt")
 
 
 def compiler_version() -> str:
@@ -112,6 +123,9 @@ if __name__ == "__main__":
     share = current_hash(KERNEL_LEAN_SHARE, SOURCE_LEAN_SHARE)
     if share is not None:
         print(json.dumps(share, indent=1))
+    park = current_hash(KERNEL_LEAN_PARK, SOURCE_LEAN_PARK)
+    if park is not None:
+        print(json.dumps(park, indent=1))
     if "--record" in sys.argv:
         h["measured"] = ("kernel 1.647 ms avg (8,192 x 200 iterations, bench.py on MI355X; profiles/d_fold_kernel_stats.csv); tools/headline_ab.py, one box, "
                          "against the build before knot 0 and the backward tail were folded (4,257 instructions): 1.6350 vs 1.6733 ms (-2.3 %), and "
@@ -152,3 +166,11 @@ if __name__ == "__main__":
             json.dump(share, f, indent=1)
             f.write("\n")
         print("recorded", RECORD_LEAN_SHARE)
+    if "--record-lean-park" in sys.argv:
+        if park is None:
+            sys.exit("no assembly of the lean kernel with the run's own slot split: run __graft_entry__.build() first")
+        park["measured"] = LEAN_PARK_MEASURED
+        with open(RECORD_LEAN_PARK, "w") as f:
+            json.dump(park, f, indent=1)
+            f.write("\n")
+        print("recorded", RECORD_LEAN_PARK)
