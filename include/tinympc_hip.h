@@ -334,6 +334,44 @@ int tinympc_set_linear_constraints_batch(tinympc_solver *s, const double *Alin_x
 int tinympc_set_linear_constraints_batch_device(tinympc_solver *s, const double *d_Alin_x, const double *d_blin_x, int nlx,
                                                 const double *d_Alin_u, const double *d_blin_u, int nlu, int first, int count);
 
+/* Per-KNOT linear (half-space) constraints for instances [first, first+count) of a batched handle: a_{k,i}' x_i <= b_{k,i} at knot i,
+ * a_{k,i}' u_i <= b_{k,i} likewise -- the rows' values belong to the knot AND the instance (a moving obstacle, a path round an obstacle,
+ * a keep-out corridor that varies over the horizon). Column-major, instance first+b's block at b times the block size:
+ *   Alin_x: nlx x nx x N x count     blin_x: nlx x N x count     Alin_u: nlu x nu x (N-1) x count     blin_u: nlu x (N-1) x count
+ * Instance first+b solves the ADMM problem of the reference algorithm in which the state-linear slack at knot i is the row-after-row
+ * projection of x_i + gl_i onto knot i's own rows (knot 0 included, as the reference's slack update includes it), the input-linear slack
+ * likewise; everything else is as in the per-instance families' solve. An instance whose rows are equal at every knot gives, bit for
+ * bit, what tinympc_set_linear_constraints_batch gives for those rows on layout A. This is the third state of the rows' half of the
+ * per-instance families mode (shared rows; rows per instance, constant over the horizon; rows per instance and knot).
+ * The row COUNTS (nlx, nlu) belong to the batch, the values to the knot and the instance: b = +inf switches one row off at one knot. At
+ * most 32 rows per side (TINYMPC_ERR_UNSUPPORTED beyond). The FIRST call must name the whole batch (first = 0, count = batch); later
+ * calls may replace a sub-range with the same counts; a whole-batch call may change the counts. The call enables the linear family of
+ * every non-empty side and keeps the ADMM state, the family's duals included: re-sending shifted rows between two warm
+ * tinympc_mpc_step_batch ticks is the intended use.
+ * Leaving the mode: tinympc_set_linear_constraints returns every instance to shared rows; a whole-batch
+ * tinympc_set_linear_constraints_batch returns the half to rows constant over the horizon; a sub-range
+ * tinympc_set_linear_constraints_batch while the rows are per knot returns TINYMPC_ERR_INVALID_INPUT ("name the whole batch") and changes
+ * nothing. reset_workspace, update_settings, every reference, track and bound verb (shared or per instance), set_cone_constraints,
+ * set_cone_slopes_batch, the solve verbs, mpc_step_batch and prepare keep mode and rows; per-instance cone slopes combine with it (the
+ * other half of the same mode, the same store).
+ * The mode runs on layout A only, before and after tinympc_prepare: tinympc_get_layout says 'A', tinympc_get_jit_info carries
+ * " per-knot-linear" (in place of " per-instance-linear") and claims no refusal of a specialisation, since none exists. Refusals are
+ * those of tinympc_set_linear_constraints_batch: with per-instance models or rho, adaptive rho, nx+nu > 64 or more cones / rounds than
+ * the generic kernels hold a solve returns TINYMPC_ERR_UNSUPPORTED (never a solve with other rows), and so does tinympc_session_begin.
+ * Single-instance handles (batch == 1): TINYMPC_ERR_UNSUPPORTED -- their kernels read the shared description.
+ * Invalid arguments -- a row of A at some knot that is all zero or not finite, a b that is NaN or -inf, NULL for a non-empty side,
+ * negative counts or no row at all, a range that is empty or beyond the batch, a first call on a sub-range, a sub-range with other
+ * counts, host memory or another GPU's memory handed to the _device form -- return TINYMPC_ERR_INVALID_INPUT and leave mode, rows, enable
+ * flags and ADMM state as they were: everything is validated (on the device, one flag read back) before anything is written. A failed
+ * allocation returns TINYMPC_ERR_ALLOC and leaves everything as it was: the store holds 3 max(nlx, nlu) N + 4 vectors of 64 doubles per
+ * wavefront (8,192 quadrotors at N = 20 with one row: 67 MB). The input has been copied when the call returns. */
+int tinympc_set_linear_constraints_knots_batch(tinympc_solver *s, const double *Alin_x, const double *blin_x, int nlx,
+                                               const double *Alin_u, const double *blin_u, int nlu, int first, int count);
+/* Same, from device memory on the handle's GPU (host and device form give the same bits: one builder); same contract as
+ * tinympc_set_x0_batch_device. */
+int tinympc_set_linear_constraints_knots_batch_device(tinympc_solver *s, const double *d_Alin_x, const double *d_blin_x, int nlx,
+                                                      const double *d_Alin_u, const double *d_blin_u, int nlu, int first, int count);
+
 /* Per-instance cone slopes for instances [first, first+count) of a batched handle. The cone STRUCTURE (Acx, qcx, Acu, qcu) is the one the
  * handle holds from tinympc_set_cone_constraints and belongs to the batch; the slope values belong to the instance. cx: ncx x count,
  * column-major, instance first+b's slopes at b*ncx in the order of the shared cone list; cu: ncu x count likewise. ncx and ncu must

@@ -97,6 +97,10 @@ SIGNATURES = {
                                                        C.c_int, C.c_int]),
     "tinympc_set_linear_constraints_batch_device": (C.c_int, [Handle, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                                               C.c_int, C.c_int]),
+    "tinympc_set_linear_constraints_knots_batch": (C.c_int, [Handle, c_double_p, c_double_p, C.c_int, c_double_p, c_double_p, C.c_int,
+                                                             C.c_int, C.c_int]),
+    "tinympc_set_linear_constraints_knots_batch_device": (C.c_int, [Handle, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                                                    C.c_int, C.c_int]),
     "tinympc_set_cone_slopes_batch": (C.c_int, [Handle, c_double_p, C.c_int, c_double_p, C.c_int, C.c_int, C.c_int]),
     "tinympc_set_cone_slopes_batch_device": (C.c_int, [Handle, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "tinympc_set_model_batch": (C.c_int, [Handle, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, C.c_int, C.c_int]),

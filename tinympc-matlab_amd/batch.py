@@ -34,7 +34,8 @@ def job_shard(rank: int, world: int, batch_per_gpu: int = 0, global_batch: int =
 
 def shard_instances(arrays, rank: int, world: int) -> tuple[int, list]:
     """A rank's slice of per-instance arrays whose LAST axis is the instance (the layout of the per-instance verbs: set_x_ref_batch,
-    set_bound_constraints_batch, set_linear_constraints_batch, set_cone_slopes_batch, ...): returns (first, [slices]) for `rank`'s contiguous shard of
+    set_bound_constraints_batch, set_linear_constraints_batch, set_linear_constraints_knots_batch -- whose arrays carry the knot axis in front of
+    it --, set_cone_slopes_batch, ...): returns (first, [slices]) for `rank`'s contiguous shard of
     shard_range(). None entries (an empty side) stay None. The rank hands the slices to its own handle with first = 0."""
     arrays = list(arrays)
     totals = {np.asarray(a).shape[-1] for a in arrays if a is not None}

@@ -791,8 +791,9 @@ int tinympc_set_linear_constraints(tinympc_solver *s, const double *Alin_x, cons
         if (zero_row(Alin_x, nlx, s->nx, k)) return fail(TINYMPC_ERR_INVALID_INPUT, "Alin_x row %d is all zero", k);
     for (int k = 0; k < nlu; ++k)
         if (zero_row(Alin_u, nlu, s->nu, k)) return fail(TINYMPC_ERR_INVALID_INPUT, "Alin_u row %d is all zero", k);
-    if (s->inst.lin) {  // (per-instance linear rows: every instance is on the shared rows again)
+    if (s->inst.lin) {  // (per-instance linear rows, per knot too: every instance is on the shared rows again)
         s->inst.lin = false;
+        s->inst.lin_knots = 0;
         if (s->inst_tables()) s->inst.mark(0, s->batch);
     }
     s->inst.shared_rows_dirty = true;  // (per-instance cone slopes alone: the store's rows are a copy of these)
@@ -1654,9 +1655,13 @@ int set_rho_batch(tinympc_solver *s, const double *rho, bool on_device, int firs
 // tinympc_set_linear_constraints_batch (+ _device): the linear rows of instances [first, first+count). Host input is staged on the device;
 // from there both forms are ONE path -- k_check_inst_lin validates the arrays where they lie (one flag read back), then, and only
 // then, k_build_inst_lin writes the instances' rows into the store the kernel reads. Nothing else is kept.
+// tinympc_set_linear_constraints_knots_batch (+ _device) is the same path with per_knot set: the arrays hold the rows of every knot (N
+// blocks per instance on the state side, N-1 on the input side), k_check_inst_lin walks them as (instance, knot) pairs and
+// k_build_inst_lin_knots writes the store's knot slots.
 int set_lin_batch(tinympc_solver *s, const double *Ax, const double *bx, int nlx, const double *Au, const double *bu, int nlu, bool on_device,
-                  int first, int count) {
-    const char *verb = on_device ? "set_linear_constraints_batch_device" : "set_linear_constraints_batch";
+                  int first, int count, bool per_knot = false) {
+    const char *verb = per_knot ? (on_device ? "set_linear_constraints_knots_batch_device" : "set_linear_constraints_knots_batch")
+                                : (on_device ? "set_linear_constraints_batch_device" : "set_linear_constraints_batch");
     int rc = check_handle(s);
     if (rc) return rc;
     if (nlx < 0 || nlu < 0) return fail(TINYMPC_ERR_INVALID_INPUT, "%s: negative constraint count", verb);
@@ -1669,7 +1674,10 @@ int set_lin_batch(tinympc_solver *s, const double *Ax, const double *bx, int nlx
     if (nlx > MAX_LIN_ROWS || nlu > MAX_LIN_ROWS)
         return fail(TINYMPC_ERR_UNSUPPORTED, "%s: at most %d rows per side (got %d state, %d input): per-instance rows run on the generic kernel only",
                     verb, MAX_LIN_ROWS, nlx, nlu);
+    if (per_knot && s->batch == 1)
+        return fail(TINYMPC_ERR_UNSUPPORTED, "%s: single-instance handles run on the shared description: per-knot rows need a batched handle", verb);
     const size_t nx = s->nx, nu = s->nu, ax = (size_t)nlx * nx, au = (size_t)nlu * nu, n = (size_t)count;
+    const size_t kx = per_knot ? (size_t)s->N : 1, ku = per_knot ? (size_t)s->N - 1 : 1;  // blocks of rows per instance and side
     if (on_device && ((nlx > 0 && (!on_handles_device(s, Ax) || !on_handles_device(s, bx))) || (nlu > 0 && (!on_handles_device(s, Au) || !on_handles_device(s, bu)))))
         return fail(TINYMPC_ERR_INVALID_INPUT, "%s: the rows are not device memory of the handle's GPU %d", verb, s->device);
     InstState &in = s->inst;
@@ -1696,6 +1704,13 @@ int set_lin_batch(tinympc_solver *s, const double *Ax, const double *bx, int nlx
     const bool whole = first == 0 && count == s->batch;
     const bool same = in.lin ? (nlx == in.lin_nlx && nlu == in.lin_nlu)
                              : (nlx == s->n_lin_x && nlu == s->n_lin_u && s->Alin_x.size() == ax && s->Alin_u.size() == au);
+    // the per-knot form: a sub-range only replaces rows of a store that is already per knot; and only a whole batch leaves it
+    if (per_knot && !whole && !in.lin_knots)
+        return fail(TINYMPC_ERR_INVALID_INPUT, "%s: the first call must name the whole batch (first = 0, count = %d), got instances [%d, %d)", verb,
+                    s->batch, first, first + count);
+    if (!per_knot && !whole && in.lin_knots)
+        return fail(TINYMPC_ERR_INVALID_INPUT, "%s: the handle's rows are per knot (set_linear_constraints_knots_batch): name the whole batch "
+                    "(first = 0, count = %d) to return to rows constant over the horizon", verb, s->batch);
     if (!whole && !same)
         return fail(TINYMPC_ERR_INVALID_INPUT, "%s: %d state and %d input rows for instances [%d, %d) of %d, but %s %d and %d: name the whole batch "
                     "(first = 0, count = %d) to %s", verb, nlx, nlu, first, first + count, s->batch,
@@ -1705,8 +1720,9 @@ int set_lin_batch(tinympc_solver *s, const double *Ax, const double *bx, int nlx
     InstLinParams q{};
     q.nx = s->nx; q.nu = s->nu; q.W = s->W; q.nlx = nlx; q.nlu = nlu; q.nl = nlx > nlu ? nlx : nlu;
     q.batch = s->batch; q.first = first; q.count = count;
-    q.ax_stride = ax; q.bx_stride = (size_t)nlx; q.au_stride = au; q.bu_stride = (size_t)nlu;
-    const size_t per = ax + nlx + au + nlu;
+    q.ax_stride = ax * kx; q.bx_stride = (size_t)nlx * kx; q.au_stride = au * ku; q.bu_stride = (size_t)nlu * ku;
+    if (per_knot) { q.knots = s->N; q.ax_knot = ax; q.bx_knot = (size_t)nlx; q.au_knot = au; q.bu_knot = (size_t)nlu; }
+    const size_t per = (ax + nlx) * kx + (au + nlu) * ku;
     double *old_stage = nullptr, *old_rows = nullptr;
     if (on_device) {
         q.Ax = Ax; q.bx = bx; q.Au = Au; q.bu = bu;
@@ -1716,21 +1732,28 @@ int set_lin_batch(tinympc_solver *s, const double *Ax, const double *bx, int nlx
             if ((rc = dalloc(s, &in.lstage, per * n))) return rc;
             in.lstage_cap = per * n;
         }
-        double *dAx = in.lstage, *dbx = dAx + ax * n, *dAu = dbx + nlx * n, *dbu = dAu + au * n;
+        double *dAx = in.lstage, *dbx = dAx + ax * kx * n, *dAu = dbx + nlx * kx * n, *dbu = dAu + au * ku * n;
         if (nlx > 0) {
-            HIP_TRY(hipMemcpyAsync(dAx, Ax, sizeof(double) * ax * n, hipMemcpyHostToDevice, s->stream));
-            HIP_TRY(hipMemcpyAsync(dbx, bx, sizeof(double) * nlx * n, hipMemcpyHostToDevice, s->stream));
+            HIP_TRY(hipMemcpyAsync(dAx, Ax, sizeof(double) * ax * kx * n, hipMemcpyHostToDevice, s->stream));
+            HIP_TRY(hipMemcpyAsync(dbx, bx, sizeof(double) * nlx * kx * n, hipMemcpyHostToDevice, s->stream));
         }
         if (nlu > 0) {
-            HIP_TRY(hipMemcpyAsync(dAu, Au, sizeof(double) * au * n, hipMemcpyHostToDevice, s->stream));
-            HIP_TRY(hipMemcpyAsync(dbu, bu, sizeof(double) * nlu * n, hipMemcpyHostToDevice, s->stream));
+            HIP_TRY(hipMemcpyAsync(dAu, Au, sizeof(double) * au * ku * n, hipMemcpyHostToDevice, s->stream));
+            HIP_TRY(hipMemcpyAsync(dbu, bu, sizeof(double) * nlu * ku * n, hipMemcpyHostToDevice, s->stream));
         }
         q.Ax = dAx; q.bx = dbx; q.Au = dAu; q.bu = dbu;
     }
     if (!in.mflag && (rc = dalloc(s, &in.mflag, (size_t)1))) return rc;
     int bad = 0;
     HIP_TRY(hipMemsetAsync(in.mflag, 0, sizeof(int), s->stream));
-    HIP_TRY(launch_check_inst_lin(q, in.mflag, s->stream));
+    if (per_knot) {  // the rows of every (instance, knot) pair, a side at a time (the sides differ in their knots): blocks ax / au apart
+        InstLinParams c = q;
+        c.nlu = 0; c.count = count * (int)kx; c.ax_stride = ax; c.bx_stride = (size_t)nlx;
+        HIP_TRY(launch_check_inst_lin(c, in.mflag, s->stream));
+        c = q;
+        c.nlx = 0; c.count = count * (int)ku; c.au_stride = au; c.bu_stride = (size_t)nlu;
+        HIP_TRY(launch_check_inst_lin(c, in.mflag, s->stream));
+    } else HIP_TRY(launch_check_inst_lin(q, in.mflag, s->stream));
     if ((rc = download(s, &bad, in.mflag, sizeof(int)))) return rc;  // (host input has been copied when this returns)
     if (old_stage) dfree(s, old_stage);
     if (bad)
@@ -1738,18 +1761,20 @@ int set_lin_batch(tinympc_solver *s, const double *Ax, const double *bx, int nlx
     // ---- valid: from here on the call writes
     if (!s->layout_m) {  // (large systems: no kernel carries the mode -- the next solve refuses until the shared verb clears it)
         if ((rc = alloc_inst_rows(s, true))) return rc;
-        const size_t need = inst_lin_doubles(s->groups, q.nl);
+        const size_t need = inst_lin_store_doubles(s->groups, q.nl, q.knots);
         if (need > in.lrows_cap) {
             old_rows = in.lrows;
             if ((rc = dalloc(s, &in.lrows, need))) return rc;
             in.lrows_cap = need;
         }
         q.dst = in.lrows;
-        if (!in.lin || q.nl != in.lin_nl || old_rows) {  // the store begins (or changes its row count): every lane absent, padding included ...
+        // the store begins (or changes its row count, or moves between rows per knot and rows constant over the horizon): every lane absent,
+        // padding included ...
+        if (!in.lin || q.nl != in.lin_nl || q.knots != in.lin_knots || old_rows) {
             InstLinParams z = q;
             z.nlx = z.nlu = 0; z.first = 0; z.count = s->groups * s->IPW;
             z.Ax = z.bx = z.Au = z.bu = nullptr;
-            HIP_TRY(launch_build_inst_lin(z, s->stream));
+            HIP_TRY(per_knot ? launch_build_inst_lin_knots(z, s->stream) : launch_build_inst_lin(z, s->stream));
             in.slopes_dirty = true;  // (the groups' slope vectors share the blocks that were just laid out anew: rebuilt at the next launch)
             if (!whole) {  // ... and the instances this call does not name on the shared rows of this moment (same counts: checked above)
                 double *sh = nullptr;
@@ -1767,15 +1792,15 @@ int set_lin_batch(tinympc_solver *s, const double *Ax, const double *bx, int nlx
                 dfree(s, sh);
             }
         }
-        HIP_TRY(launch_build_inst_lin(q, s->stream));
+        HIP_TRY(per_knot ? launch_build_inst_lin_knots(q, s->stream) : launch_build_inst_lin(q, s->stream));
     }
     if (!in.fam()) {  // (the mode begins; the reference and clamp rows of every instance: this mode's kernel always reads them per instance)
         in.mark(0, s->batch);
         in.slopes_dirty = true;
     }
     in.lin = true;
-    in.lin_nlx = nlx; in.lin_nlu = nlu; in.lin_nl = q.nl;
-    if (!s->layout_m) in.fam_rows_nl = q.nl;
+    in.lin_nlx = nlx; in.lin_nlu = nlu; in.lin_nl = q.nl; in.lin_knots = q.knots;
+    if (!s->layout_m) { in.fam_rows_nl = q.nl; in.fam_rows_knots = q.knots; }
     if (nlx != s->n_lin_x || nlu != s->n_lin_u) {  // (the shared rows are not read while the mode is on; they keep the handle's counts consistent)
         s->n_lin_x = nlx; s->n_lin_u = nlu;
         s->Alin_x.assign(ax, 0.0); s->blin_x.assign(nlx, std::numeric_limits<double>::infinity());
@@ -1890,6 +1915,14 @@ int tinympc_set_cone_slopes_batch_device(tinympc_solver *s, const double *d_cx, 
     return set_cone_slopes_batch(s, d_cx, ncx, d_cu, ncu, true, first, count);
 }
 
+int tinympc_set_linear_constraints_knots_batch(tinympc_solver *s, const double *Alin_x, const double *blin_x, int nlx, const double *Alin_u,
+                                               const double *blin_u, int nlu, int first, int count) {
+    return set_lin_batch(s, Alin_x, blin_x, nlx, Alin_u, blin_u, nlu, false, first, count, true);
+}
+int tinympc_set_linear_constraints_knots_batch_device(tinympc_solver *s, const double *d_Alin_x, const double *d_blin_x, int nlx, const double *d_Alin_u,
+                                                      const double *d_blin_u, int nlu, int first, int count) {
+    return set_lin_batch(s, d_Alin_x, d_blin_x, nlx, d_Alin_u, d_blin_u, nlu, true, first, count, true);
+}
 int tinympc_set_linear_constraints_batch(tinympc_solver *s, const double *Alin_x, const double *blin_x, int nlx, const double *Alin_u,
                                          const double *blin_u, int nlu, int first, int count) {
     return set_lin_batch(s, Alin_x, blin_x, nlx, Alin_u, blin_u, nlu, false, first, count);

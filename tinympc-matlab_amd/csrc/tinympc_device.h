@@ -193,7 +193,10 @@ struct SolveParams {
     // (iref_lr: per-instance references, layout A only -- see below; shares the slot so that the kernels' argument layout stays as it was)
     union { const double *ctab; const double *iref_lr; };  // ctab: PhiS_l | PsiS_l (l < chunk_levels), each [16][chunk_ks(nx)]: powers S*2^l of the sweeps' state blocks
     union { int chunk_len; int ilin_nl; };  // (ilin_nl: rows per instance of ilin; layout A never reads chunk_len)
-    int chunk_count, chunk_levels;
+    // (ilin_knots: the per-knot form of the per-instance linear rows, k_admm_solve_ifamk -- knot slots per group of ilin, see below; layout A
+    // never reads chunk_count)
+    union { int chunk_count; int ilin_knots; };
+    int chunk_levels;
     int families;         // layout C / the specialised layout D: run the cone / linear families too (the other layouts use k_admm_solve_fam)
     int adaptive;         // the specialised layout D: adaptive rho (the other layouts use k_admm_solve_adapt)
     int const_tables;     // bounds and references are the same at every knot (layout B keeps them in registers)
@@ -259,6 +262,11 @@ struct SolveParams {
     // In front of a group's 3 * ilin_nl row vectors lie its INST_FAM_SLOPE_ROWS cone-slope vectors (tinympc_set_cone_slopes_batch): per round q
     // of the shared cone structure the slope of the cone each lane's row belongs to, 0 for a row in no cone of the round -- mu[W] of the
     // shared description, per instance (k_build_inst_slopes). A group's block is inst_fam_group_doubles(ilin_nl) doubles.
+    // Per-knot linear rows (tinympc_set_linear_constraints_knots_batch; layout A's InstFamiliesKnots variant, k_admm_solve_ifamk): behind the
+    // slope vectors a group's block holds ilin_knots = N SLOTS of 3 * ilin_nl row vectors a_k | b_k | 1 / ||a_k||^2, in the sweep's own skew:
+    // slot 0 is knot 0 on the state lanes (absent rows on the input lanes), slot i+1 what forward step i finishes -- knot i+1 on the state
+    // lanes, knot i on the input lanes --, so that a step reads whole 512-byte lines. Built by k_build_inst_lin_knots; a block is
+    // inst_fam_block_doubles(ilin_nl, ilin_knots) doubles, and one slot of padding lies behind the last group's (the sweep fetches a slot ahead).
 };
 
 // Per-instance references and bounds of a batched handle (k_store_inst_refs, k_build_inst_tables; tinympc_kernels.hip). The references
@@ -306,12 +314,24 @@ struct InstLinParams {
     const double *Ax, *bx, *Au, *bu;
     size_t ax_stride, bx_stride, au_stride, bu_stride;
     double *dst;
+    // the per-knot form (k_build_inst_lin_knots; 0 above): knots = N slots per group; knot i of an instance's state rows lies i * ax_knot /
+    // i * bx_knot doubles behind its knot 0, of its input rows i * au_knot / i * bu_knot (strides of 0: the same rows at every knot)
+    int knots;
+    size_t ax_knot, bx_knot, au_knot, bu_knot;
 };
 // A group's block of the store: one cone-slope vector per round (INST_FAM_SLOPE_ROWS = MAX_ROUNDS, below), then 3 nl row vectors -- the
 // slopes first, so that their address does not depend on the row count (k_admm_solve_ifam reads them inside its ADMM loop).
 constexpr int INST_FAM_SLOPE_ROWS = 4;
 __host__ __device__ constexpr size_t inst_fam_group_doubles(int nl) { return (size_t)(3 * (nl > 0 ? nl : 1) + INST_FAM_SLOPE_ROWS) * 64; }
 __host__ __device__ inline size_t inst_lin_doubles(int groups, int nl) { return (size_t)groups * inst_fam_group_doubles(nl); }
+// ... and in the per-knot form (knots > 0 slots of 3 nl row vectors per group; knots = 0: the block above), with the slot of padding
+// behind the last group that the forward sweep's fetch one slot ahead reads and never uses
+__host__ __device__ constexpr size_t inst_fam_block_doubles(int nl, int knots) {
+    return (size_t)(3 * (nl > 0 ? nl : 1) * (knots > 0 ? knots : 1) + INST_FAM_SLOPE_ROWS) * 64;
+}
+__host__ __device__ inline size_t inst_lin_store_doubles(int groups, int nl, int knots) {
+    return (size_t)groups * inst_fam_block_doubles(nl, knots) + (knots > 0 ? (size_t)3 * (nl > 0 ? nl : 1) * 64 : 0);
+}
 // Per-instance cone slopes (tinympc_set_cone_slopes_batch). k_store_inst_slopes keeps the verb's values: raw [batch][ncx + ncu] <- cx | cu of
 // instances [first, first+count) (strides of 0: one block for every instance -- the shared slopes). k_build_inst_slopes scatters them
 // through the shared structure into the store's slope vectors: lane r of round q takes raw[inst][map[q][r]], 0 where map is -1 (the row
@@ -325,6 +345,7 @@ struct InstSlopeParams {
     size_t raw_stride;
     double *dst;             // the store (SolveParams::ilin)
     signed char map[INST_FAM_SLOPE_ROWS][64];
+    int knots;               // the store's knot slots per group (inst_fam_block_doubles; 0: rows constant over the horizon)
 };
 struct InstTableParams {
     int nx, nu, N, W, KT, groups;
@@ -515,6 +536,7 @@ hipError_t launch_check_positive(const double *v, int n, int *flag, hipStream_t 
 // Per-instance linear rows: the store's rows of p's instances, and the validation of the verb's input where it lies -- *flag <- 1 if a
 // row of A is all zero or holds a value that is not finite, or a b is NaN or -inf (the strides of p; dst is not touched)
 hipError_t launch_build_inst_lin(const InstLinParams &p, hipStream_t stream);
+hipError_t launch_build_inst_lin_knots(const InstLinParams &p, hipStream_t stream);
 hipError_t launch_check_inst_lin(const InstLinParams &p, int *flag, hipStream_t stream);
 // Per-instance cone slopes: the validation of the verb's input where it lies -- *flag <- 1 if a slope is NaN, infinite or <= 0 --, the
 // copy into the raw array and the store's slope vectors of every group (InstSlopeParams)
@@ -534,7 +556,8 @@ hipError_t launch_advance_ref_steps(int *steps, int n, int delta, hipStream_t st
 // SolveParams::ops then is [batch][ops_doubles(W, KT)].
 // A seventh, InstFamilies, is Families with every instance's own linear rows (k_admm_solve_ifam, tinympc_ifam_a.hip: SolveParams::ilin)
 // on the per-instance reference and clamp rows of InstBounds.
-enum class SolveExt { Box, Families, Adaptive, InstRefs, InstBounds, InstModels, InstFamilies };
+// An eighth, InstFamiliesKnots, is InstFamilies with the rows of every KNOT (k_admm_solve_ifamk, tinympc_ifamk_a.hip: SolveParams::ilin_knots)
+enum class SolveExt { Box, Families, Adaptive, InstRefs, InstBounds, InstModels, InstFamilies, InstFamiliesKnots };
 hipError_t launch_solve_a(const SolveParams &p, SolveExt ext, int W, int KT, size_t lds_bytes, hipStream_t stream);
 // Layout B: four wavefronts per workgroup sharing the tables in LDS, G and D in LDS, V as an
 // L2-resident ping-pong pair in HBM (4 waves per CU). Only W = 16, N >= 8.

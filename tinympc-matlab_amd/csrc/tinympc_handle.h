@@ -111,6 +111,10 @@ struct InstState {
     // constant over the horizon and the cones are ones layout D's families kernel takes, on layout D's ILIN form (lin_wants_d).
     bool lin = false;
     int lin_nlx = 0, lin_nlu = 0, lin_nl = 0;
+    // ... and its third state, rows per KNOT (tinympc_set_linear_constraints_knots_batch): lin_knots = N while it is on, 0 otherwise. The store
+    // then holds N slots of rows per group (inst_fam_block_doubles), the mode runs on layout A's InstFamiliesKnots variant only
+    // (lin_wants_d is false), and a whole-batch tinympc_set_linear_constraints_batch or the shared verb ends it.
+    int lin_knots = 0;
     // layout D's per-instance linear-row form (16 lanes; compiled in or run-time specialised on the shape AND lin_nl): -1 not asked yet,
     // 0 no, 1 yes -- the answer for d_lin_nl rows; another count (a whole-batch call) makes it unknown again (resolve_plan). The cones are
     // no part of the specialisation: whether their structure is one the form takes is asked at every launch (lin_wants_d).
@@ -134,6 +138,7 @@ struct InstState {
     size_t craw_cap = 0;
     bool slopes_dirty = true, shared_rows_dirty = true;  // the store's slope vectors / its copy of the shared rows are out of date
     int fam_rows_nl = 0;                     // rows per instance the store holds now (SolveParams::ilin_nl; 0: no store yet)
+    int fam_rows_knots = 0;                  // ... and its knot slots per group (SolveParams::ilin_knots; 0: rows constant over the horizon)
     int dirty_lo = 0, dirty_hi = 0;
     bool refs() const { return x || u; }
     const double *lr_rows() const { return lr + (size_t)tinympc::INST_LR_PAD * 64; }  // SolveParams::iref_lr on layout A

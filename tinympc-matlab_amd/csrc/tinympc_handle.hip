@@ -572,13 +572,14 @@ int refresh_inst_families(tinympc_solver *s) {
     if (!in.fam() || s->layout_m) return TINYMPC_OK;
     int rc;
     const int nl = s->ifam_nl(), IPW = 64 / s->W;
-    const size_t need = inst_lin_doubles(s->groups, nl);
+    const int knots = in.lin ? in.lin_knots : 0;  // (the per-knot form: the rows' verb laid the larger blocks out; here only the slopes)
+    const size_t need = inst_lin_store_doubles(s->groups, nl, knots);
     if (need > in.lrows_cap) {  // (only ever here while the row half is off: its verb sizes the store itself; the old block stays on the handle's free list)
         if ((rc = dalloc(s, &in.lrows, need))) return rc;
         in.lrows_cap = need;
         in.fam_rows_nl = 0;
     }
-    if (nl != in.fam_rows_nl) {  // a new store, or another row count: the groups' blocks have moved
+    if (nl != in.fam_rows_nl || knots != in.fam_rows_knots) {  // a new store, or another row count: the groups' blocks have moved
         in.slopes_dirty = true;
         if (!in.lin) in.shared_rows_dirty = true;
     }
@@ -610,6 +611,7 @@ int refresh_inst_families(tinympc_solver *s) {
         const int ncx = s->n_cone_x, ncu = s->n_cone_u, nc = ncx + ncu;
         InstSlopeParams q{};
         q.W = s->W; q.nl = nl; q.ncx = ncx; q.ncu = ncu; q.batch = s->batch; q.groups = s->groups;
+        q.knots = knots;
         q.dst = in.lrows;
         for (int r = 0; r < INST_FAM_SLOPE_ROWS; ++r)
             for (int l = 0; l < 64; ++l) q.map[r][l] = -1;
@@ -634,6 +636,7 @@ int refresh_inst_families(tinympc_solver *s) {
         in.slopes_dirty = false;
     }
     in.fam_rows_nl = nl;
+    in.fam_rows_knots = knots;
     return TINYMPC_OK;
 }
 

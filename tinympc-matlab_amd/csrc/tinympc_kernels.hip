@@ -5,6 +5,7 @@
 //   k_build_tables          per-knot clamp bounds / linear-cost reference terms
 //   k_build_inst_tables     the same rows per instance (per-instance references / bounds of a batched handle; reference tracks)
 //   k_build_inst_lin        per-instance linear rows: the store layout A's InstFamilies variant reads (k_check_inst_lin validates the input)
+//   k_build_inst_lin_knots  ... and its per-knot form, the store of the InstFamiliesKnots variant
 //   k_build_inst_slopes     per-instance cone slopes: the same store's slope vectors (k_check_inst_slopes validates, k_store_inst_slopes keeps the input)
 //   k_advance_ref_steps     reference tracks: every instance's step moves on the device (k_check_ref_steps validates device input)
 //   k_build_adapt           adaptive rho: the sensitivity rows of the sweep operators and [A'; B']
@@ -790,6 +791,49 @@ hipError_t launch_build_inst_lin(const InstLinParams &p, hipStream_t stream) {
     hipLaunchKernelGGL(k_build_inst_lin, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, stream, p);
     return hipGetLastError();
 }
+// The per-knot form (tinympc_set_linear_constraints_knots_batch): the store k_admm_solve_ifamk reads, [group][slopes | N slots of 3 nl][64],
+// for instances [first, first+count) -- one thread per (instance, slot, row k, lane of the instance). The slots follow the forward sweep's
+// skew: slot 0 holds knot 0 on the state lanes and absent rows on the input lanes, slot i+1 knot i+1 on the state lanes and knot i on the
+// input lanes (what step i finishes), so that a step reads whole lines. Values as k_build_inst_lin writes them -- the same unfused norm --
+// but for the third vector, which holds 1 / ||a_k||^2: the division the constant form's kernel does once per solve, done here once per
+// row (the same correctly rounded division: the same bits).
+__global__ void __launch_bounds__(256) k_build_inst_lin_knots(const InstLinParams p) {
+    const int W = p.W, IPW = 64 / W, nx = p.nx, nu = p.nu, K = p.knots;
+    const size_t per_slot = (size_t)p.nl * W, per = per_slot * K, total = per * p.count;
+    const double inf = __longlong_as_double(0x7FF0000000000000LL);
+    for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
+        const size_t b = idx / per;
+        const int slot = (int)((idx % per) / per_slot);
+        const int k = (int)((idx % per_slot) / W), r = (int)(idx % W);
+        const size_t inst = (size_t)p.first + b;
+        double a = 0.0, bv = inf, nrm = 1.0;
+        if (inst < (size_t)p.batch && r < nx && k < p.nlx) {  // state lanes: knot `slot`
+            const double *A = p.Ax + b * p.ax_stride + (size_t)slot * p.ax_knot;
+            nrm = 0.0;
+            for (int c = 0; c < nx; ++c) { const double v = A[k + (size_t)c * p.nlx]; nrm = add_square_unfused(nrm, v); }
+            a = A[k + (size_t)r * p.nlx];
+            bv = p.bx[b * p.bx_stride + (size_t)slot * p.bx_knot + k];
+        } else if (inst < (size_t)p.batch && r >= nx && r < nx + nu && k < p.nlu && slot >= 1) {  // input lanes: knot `slot - 1`
+            const double *A = p.Au + b * p.au_stride + (size_t)(slot - 1) * p.au_knot;
+            nrm = 0.0;
+            for (int c = 0; c < nu; ++c) { const double v = A[k + (size_t)c * p.nlu]; nrm = add_square_unfused(nrm, v); }
+            a = A[k + (size_t)(r - nx) * p.nlu];
+            bv = p.bu[b * p.bu_stride + (size_t)(slot - 1) * p.bu_knot + k];
+        }
+        double *row = p.dst + (inst / IPW) * inst_fam_block_doubles(p.nl, K) +
+                      ((size_t)INST_FAM_SLOPE_ROWS + 3 * ((size_t)slot * p.nl + k)) * 64 + (inst % IPW) * W + r;
+        row[0] = a;
+        row[64] = bv;
+        row[128] = 1.0 / nrm;
+    }
+}
+hipError_t launch_build_inst_lin_knots(const InstLinParams &p, hipStream_t stream) {
+    const size_t total = (size_t)p.nl * p.W * p.knots * p.count;
+    if (total == 0) return hipSuccess;
+    const size_t blocks = (total + 255) / 256;
+    hipLaunchKernelGGL(k_build_inst_lin_knots, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, stream, p);
+    return hipGetLastError();
+}
 // ... and the validation of the verb's arrays where they lie, one thread per (instance, row): *flag <- 1 if a row of A is all zero or
 // holds a value that is not finite, or its b is NaN or -inf (+inf switches the row off)
 __global__ void __launch_bounds__(256) k_check_inst_lin(const InstLinParams p, int *flag) {
@@ -849,7 +893,7 @@ __global__ void __launch_bounds__(256) k_store_inst_slopes(const InstSlopeParams
 __global__ void __launch_bounds__(256) k_build_inst_slopes(const InstSlopeParams p) {
     const int W = p.W, IPW = 64 / W, nc = p.ncx + p.ncu;
     const size_t total = (size_t)p.groups * INST_FAM_SLOPE_ROWS * 64;
-    const size_t gd = inst_fam_group_doubles(p.nl);
+    const size_t gd = inst_fam_block_doubles(p.nl, p.knots);  // (the per-knot form: larger blocks, the slope vectors still in front)
     for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
         const size_t g = idx / (INST_FAM_SLOPE_ROWS * 64);
         const int q = (int)((idx / 64) % INST_FAM_SLOPE_ROWS), lane = (int)(idx % 64);

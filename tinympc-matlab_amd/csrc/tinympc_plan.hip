@@ -170,8 +170,9 @@ bool lin_runs(const tinympc_solver *s) {
 // where the handle runs layout D, 16 lanes per instance, references and bounds constant over the horizon (shared or per instance: no
 // trajectories, tracks or per-knot bounds), and a cone structure layout D's shared families kernel takes (decide_layout_d_variants: no
 // rounds of overlapping cones). Whether the kernel exists for the mode's row count is inst.d_lin (resolve_plan).
+// Rows per knot (tinympc_set_linear_constraints_knots_batch) have no layout D form: they stay on layout A's InstFamiliesKnots variant.
 bool lin_wants_d(const tinympc_solver *s) {
-    return lin_runs(s) && s->specialise_asked && s->layout_d && s->W == 16 && s->iref_goal() && family_structure(s).nround <= 1;
+    return lin_runs(s) && !s->inst.lin_knots && s->specialise_asked && s->layout_d && s->W == 16 && s->iref_goal() && family_structure(s).nround <= 1;
 }
 bool lin_on_d(const tinympc_solver *s) {
     return lin_wants_d(s) && s->inst.d_lin == 1 && s->inst.d_lin_nl == s->ifam_nl() && s->inst.d_lin_cones == s->inst.cones;
@@ -193,6 +194,7 @@ namespace host {
 //                                      (the mode of tinympc_set_model_batch AND tinympc_set_rho_batch: one form, rho always read per instance)
 //   per-instance linear rows           D's ILIN form (only after tinympc_prepare: 16 lanes, references and bounds constant over the horizon, cones
 //                                      without rounds, a horizon and row count its per-wavefront plan holds)  >  A's InstFamilies variant,
+//                                      (rows per knot: its InstFamiliesKnots variant, never layout D),
 //                                      whatever else is per instance (references, bounds) or shared (cones); with
 //                                      per-instance models / rho, adaptive rho, layout M or a cone structure beyond the generic kernels, launch() refuses
 LaunchPlan current_plan(const tinympc_solver *s) {
@@ -421,8 +423,9 @@ int launch(tinympc_solver *s, bool timed) {
         if (!s->inst.lin)
             return fail(TINYMPC_ERR_UNSUPPORTED, "per-instance cone slopes (set_cone_slopes_batch) are not supported %s; "
                         "tinympc_set_cone_constraints returns to shared slopes", why);
-        return fail(TINYMPC_ERR_UNSUPPORTED, "per-instance linear constraints (set_linear_constraints_batch)%s are not supported %s; "
-                    "tinympc_set_linear_constraints returns to shared rows%s", s->inst.cones ? " and cone slopes (set_cone_slopes_batch)" : "", why,
+        return fail(TINYMPC_ERR_UNSUPPORTED, "per-instance linear constraints (%s)%s are not supported %s; "
+                    "tinympc_set_linear_constraints returns to shared rows%s", s->inst.lin_knots ? "set_linear_constraints_knots_batch" : "set_linear_constraints_batch",
+                    s->inst.cones ? " and cone slopes (set_cone_slopes_batch)" : "", why,
                     s->inst.cones ? ", tinympc_set_cone_constraints to shared slopes" : "");
     }
     if (s->inst_tables() && !pl.inst_refs) {  // never a solve with the shared references / bounds / model in their place
@@ -515,6 +518,7 @@ int launch(tinympc_solver *s, bool timed) {
     }
     p.adapt = s->dadapt; p.rho_inst = s->drho_inst;
     if (pl.inst_lin) { p.ilin = s->inst.lrows; p.ilin_nl = s->ifam_nl(); }  // (share the slots of adapt / chunk_len, which this kernel never reads)
+    if (pl.inst_lin && s->inst.lin_knots) p.ilin_knots = s->inst.lin_knots;  // (rows per knot: the store's slots per group, in chunk_count's slot)
     if (pl.inst_models) p.rho_inst = s->inst.mrho;  // (the model kernels read rho per instance: the handle's, or what tinympc_set_rho_batch set)
     if (pl.inst_refs) {
         p.iref_lr = pl.kernel == KernelId::A ? s->inst.lr_rows() : s->inst.lrg;
@@ -575,7 +579,7 @@ int launch(tinympc_solver *s, bool timed) {
         case KernelId::FAM_A:  // (the families and adaptive rho share the persistent state -- G, canonical V, D -- with every other kernel)
         case KernelId::ADAPT_A: {
             const SolveExt ext = pl.kernel == KernelId::FAM_A ? SolveExt::Families : pl.kernel == KernelId::ADAPT_A ? SolveExt::Adaptive
-                                 : pl.inst_lin ? SolveExt::InstFamilies : pl.inst_models ? SolveExt::InstModels : pl.inst_bounds ? SolveExt::InstBounds : pl.inst_refs ? SolveExt::InstRefs : SolveExt::Box;
+                                 : pl.inst_lin ? (s->inst.lin_knots ? SolveExt::InstFamiliesKnots : SolveExt::InstFamilies) : pl.inst_models ? SolveExt::InstModels : pl.inst_bounds ? SolveExt::InstBounds : pl.inst_refs ? SolveExt::InstRefs : SolveExt::Box;
             HIP_TRY(launch_solve_a(p, ext, s->W, s->KT, s->lds_bytes_a, s->stream));
             break;
         }
@@ -626,7 +630,7 @@ int tinympc_get_jit_info(tinympc_solver *s, char *buf, int len) {
     buf[0] = '\0';
     if ((rc = jit_info_text(s, buf, len))) return rc;
     if (s->inst.tracks()) strncat(buf, " reference-track", (size_t)len - strlen(buf) - 1);  // (a half is in track mode)
-    if (s->inst.lin) strncat(buf, " per-instance-linear", (size_t)len - strlen(buf) - 1);
+    if (s->inst.lin) strncat(buf, s->inst.lin_knots ? " per-knot-linear" : " per-instance-linear", (size_t)len - strlen(buf) - 1);
     if (s->inst.cones) strncat(buf, " per-instance-cones", (size_t)len - strlen(buf) - 1);
     return TINYMPC_OK;
 }
@@ -650,7 +654,7 @@ static int jit_info_text(tinympc_solver *s, char *buf, int len) {
             if ((rc = bind_device(s))) return rc;
             solve_jit_describe(s->W, s->nx, s->nu, s->N, true, true, false, buf, (size_t)len, true, false, s->ifam_nl(), s->inst.cones);
             strncat(buf, words, (size_t)len - strlen(buf) - 1);
-        } else if (pl.inst_lin && lin_runs(s) && s->specialise_asked && s->layout_d && s->W == 16 && s->iref_goal() && family_structure(s).nround > 1) {
+        } else if (pl.inst_lin && lin_runs(s) && !s->inst.lin_knots && s->specialise_asked && s->layout_d && s->W == 16 && s->iref_goal() && family_structure(s).nround > 1) {
             // asked for, and only the cones keep the mode off layout D: layout A, and why
             snprintf(buf, (size_t)len, "refused(cones that share rows run in rounds: layout D's per-instance form takes cones without rounds) layout=%c%s",
                      pl.layout, words);

@@ -178,8 +178,8 @@ int tinympc_session_begin(tinympc_solver *s) {
         return fail(TINYMPC_ERR_UNSUPPORTED, "session: per-instance models (set_model_batch)%s are not supported; tinympc_clear_model_batch returns to the shared model",
                     s->inst.rho_verb ? " with per-instance rho (set_rho_batch)" : "");
     if (s->inst.lin)
-        return fail(TINYMPC_ERR_UNSUPPORTED, "session: per-instance linear constraints (set_linear_constraints_batch) are not supported; "
-                    "tinympc_set_linear_constraints returns to shared rows");
+        return fail(TINYMPC_ERR_UNSUPPORTED, "session: per-instance linear constraints (%s) are not supported; "
+                    "tinympc_set_linear_constraints returns to shared rows", s->inst.lin_knots ? "set_linear_constraints_knots_batch" : "set_linear_constraints_batch");
     if (s->inst.cones)
         return fail(TINYMPC_ERR_UNSUPPORTED, "session: per-instance cone slopes (set_cone_slopes_batch) are not supported; "
                     "tinympc_set_cone_constraints returns to shared slopes");

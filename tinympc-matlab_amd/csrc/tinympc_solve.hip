@@ -108,6 +108,9 @@ hipError_t launch_solve_a(const SolveParams &p, SolveExt ext, int W, int KT, siz
         case SolveExt::InstFamilies:
             if (!p.iref_lr || !p.iref_pn || !p.ibnd || !p.ilin || !p.fam) return hipErrorInvalidValue;
             return launch_solve_a_e<SolveExt::InstFamilies>(p, W, KT, lds_bytes, stream);
+        case SolveExt::InstFamiliesKnots:
+            if (!p.iref_lr || !p.iref_pn || !p.ibnd || !p.ilin || !p.fam || p.ilin_knots != p.N) return hipErrorInvalidValue;
+            return launch_solve_a_e<SolveExt::InstFamiliesKnots>(p, W, KT, lds_bytes, stream);
     }
     return hipErrorInvalidValue;
 }

@@ -3,7 +3,8 @@
 // in its own source, as before: k_admm_solve (tinympc_solve.hip, the box path), k_admm_solve_fam (tinympc_solve_fam.hip, the
 // cone / linear slack families), k_admm_solve_adapt (tinympc_solve_adapt.hip, adaptive rho), k_admm_solve_iref
 // (tinympc_solve.hip, per-instance references), k_admm_solve_ibnd (tinympc_solve.hip, per-instance bounds) and k_admm_solve_imod
-// (tinympc_imod_a.hip, per-instance models) and k_admm_solve_ifam (tinympc_ifam_a.hip, per-instance linear rows). Each source instantiates
+// (tinympc_imod_a.hip, per-instance models) and k_admm_solve_ifam (tinympc_ifam_a.hip, per-instance linear rows) and k_admm_solve_ifamk
+// (tinympc_ifamk_a.hip, per-instance linear rows per knot). Each source instantiates
 // launch_solve_a_e for its variant; launch_solve_a (tinympc_solve.hip) dispatches to them.
 // (The body is not a __device__ __forceinline__ function: the compiler optimises such a function on its own before inlining
 // it, and the box kernel's generated code then changes even for a verbatim move.)
@@ -15,6 +16,12 @@ namespace tinympc {
 
 struct FwdOperands { double g, vold, lo, hi, dv, gc, gl; };  // (gc, gl: families only)
 struct BwdOperands { double bg, bv, blr, lx; };              // (lx: families only)
+// (per-knot linear rows: the rows of one knot slot a lane keeps in registers -- a | b | 1 / ||a||^2 of the first R rows; R = 1 and unused elsewhere)
+// KNOT_REG_ROWS rows of the step's slot and as many of the next step's: 12 doubles per lane. Four and four -- the 24 doubles
+// k_admm_solve_ifam keeps -- spill at 16 lanes: 8 to 42 vector registers in the <16, 16> forms, 5 scalars in the narrower ones (the
+// fetch one step ahead keeps both sets AND the step's other operands alive at once); two and two leave every form without a spill.
+constexpr int KNOT_REG_ROWS = 2;
+template <int R> struct KnotRows { double a[R], b[R], in[R]; };
 __device__ __forceinline__ double amax2(double m, double v) { return fmax(m, fabs(v)); }
 
 // GMEM: the working copy of the state lives in p.scratch (HBM) instead of LDS -- the fallback for horizons
@@ -33,6 +40,8 @@ template <int W, int KT, bool TLDS, bool GMEM = false>
 __global__ void __launch_bounds__(64) k_admm_solve_imod(const SolveParams p);
 template <int W, int KT, bool TLDS, bool GMEM = false>
 __global__ void __launch_bounds__(64) k_admm_solve_ifam(const SolveParams p);
+template <int W, int KT, bool TLDS, bool GMEM = false>
+__global__ void __launch_bounds__(64) k_admm_solve_ifamk(const SolveParams p);
 
 template <SolveExt E, int W, int KT, bool TLDS, bool GMEM>
 void (*kernel_a())(const SolveParams) {
@@ -42,7 +51,8 @@ void (*kernel_a())(const SolveParams) {
     else if constexpr (E == SolveExt::InstRefs) return k_admm_solve_iref<W, KT, TLDS, GMEM>;
     else if constexpr (E == SolveExt::InstBounds) return k_admm_solve_ibnd<W, KT, TLDS, GMEM>;
     else if constexpr (E == SolveExt::InstModels) return k_admm_solve_imod<W, KT, TLDS, GMEM>;
-    else return k_admm_solve_ifam<W, KT, TLDS, GMEM>;
+    else if constexpr (E == SolveExt::InstFamilies) return k_admm_solve_ifam<W, KT, TLDS, GMEM>;
+    else return k_admm_solve_ifamk<W, KT, TLDS, GMEM>;
 }
 
 template <SolveExt E, int W, int KT>
@@ -78,5 +88,6 @@ extern template hipError_t launch_solve_a_e<SolveExt::InstRefs>(const SolveParam
 extern template hipError_t launch_solve_a_e<SolveExt::InstBounds>(const SolveParams &, int, int, size_t, hipStream_t);  // tinympc_solve.hip
 extern template hipError_t launch_solve_a_e<SolveExt::InstModels>(const SolveParams &, int, int, size_t, hipStream_t);  // tinympc_imod_a.hip
 extern template hipError_t launch_solve_a_e<SolveExt::InstFamilies>(const SolveParams &, int, int, size_t, hipStream_t);  // tinympc_ifam_a.hip
+extern template hipError_t launch_solve_a_e<SolveExt::InstFamiliesKnots>(const SolveParams &, int, int, size_t, hipStream_t);  // tinympc_ifamk_a.hip
 
 }  // namespace tinympc

@@ -1,5 +1,5 @@
 // tinympc_solve_a_body.h -- the body of layout A's three solve kernels (k_admm_solve, k_admm_solve_fam, k_admm_solve_adapt;
-// tinympc_solve_a.h; and k_admm_solve_iref, k_admm_solve_ibnd, k_admm_solve_imod, k_admm_solve_ifam). Included INSIDE each kernel, with the kernel's template parameters W, KT,
+// tinympc_solve_a.h; and k_admm_solve_iref, k_admm_solve_ibnd, k_admm_solve_imod, k_admm_solve_ifam, k_admm_solve_ifamk). Included INSIDE each kernel, with the kernel's template parameters W, KT,
 // TLDS, GMEM, its parameter p and the variant E (SolveExt) in scope; the families', adaptive rho's and per-instance references' and
 // bounds' additions are compiled only into their variant.
 // No include guard: it is meant to be included once per kernel.
@@ -7,7 +7,12 @@
     // this lane's INSTANCE's, from p.ilin, [group][3 nl][64] -- one 512-byte line per row vector and wavefront -- instead of the shared
     // description's; and whose cone SLOPES are the instance's too (tinympc_set_cone_slopes_batch), one vector per round in front of the
     // group's rows. The cones' structure -- roles, last rows, round masks --, the enable flags and everything else as in the families' variant
-    constexpr bool IFAM = E == SolveExt::InstFamilies;
+    // per-instance linear rows PER KNOT: that variant with one difference -- the store holds a slot of 3 nl row vectors for every step of the
+    // forward sweep (SolveParams::ilin_knots = N of them per group, slot 0 = knot 0 on the state lanes, slot i+1 = what step i finishes: the
+    // sweep's own skew, k_build_inst_lin_knots), the third vector already 1 / ||a_k||^2, and `families` takes the slot. The registers that
+    // hold the constant rows for the whole solve hold the first KNOT_REG_ROWS rows of the step's slot and of the next step's, fetched a step ahead
+    constexpr bool IFAMK = E == SolveExt::InstFamiliesKnots;
+    constexpr bool IFAM = E == SolveExt::InstFamilies || IFAMK;
     constexpr bool FAM = E == SolveExt::Families || IFAM, ADAPT = E == SolveExt::Adaptive;
     // per-instance references: this instance's linref rows and pNref from p.iref_lr / iref_pn (HBM / L2, the lane's own 512-byte line
     // per knot) instead of the shared tables; everything else as on the box path
@@ -125,7 +130,8 @@
                 const double *rd = q == 0 ? p.fam : p.fam + fam_round_offset(W, KT, q);
                 const double *ctq = q == 0 ? p.fam + 4 * W + M : rd + 2 * W + M;
                 r_role[q] = (int)rd[r];
-                r_mu[q] = IFAM ? p.ilin[(size_t)grp * inst_fam_group_doubles(p.ilin_nl) + (size_t)q * 64 + lane] : rd[W + r];
+                if constexpr (IFAMK) r_mu[q] = p.ilin[(size_t)grp * inst_fam_block_doubles(p.ilin_nl, p.ilin_knots) + (size_t)q * 64 + lane];
+                else r_mu[q] = IFAM ? p.ilin[(size_t)grp * inst_fam_group_doubles(p.ilin_nl) + (size_t)q * 64 + lane] : rd[W + r];
                 r_imu[q] = (r_mu[q] != 0.0) ? 1.0 / r_mu[q] : 0.0;
                 for (int k = 0; k < nxu; ++k)
                     if (ctq[(size_t)r * KT + k] != 0.0) r_head[q] = k;
@@ -142,7 +148,8 @@
     constexpr int LW = IFAM ? 64 : W, LB = IFAM ? INST_FAM_SLOPE_ROWS * 64 : 1;
     const double *lin_shared = p.fam + 4 * W + 3 * M;
     const int nl = IFAM ? p.ilin_nl : FAM ? (int)lin_shared[0] : 0;
-    const double *lin_rows = IFAM ? p.ilin + ((size_t)grp * inst_fam_group_doubles(nl) + j * W) : lin_shared;
+    const double *lin_rows = IFAMK ? p.ilin + ((size_t)grp * inst_fam_block_doubles(nl, p.ilin_knots) + j * W)
+                             : IFAM ? p.ilin + ((size_t)grp * inst_fam_group_doubles(nl) + j * W) : lin_shared;
     // (per-instance slopes: round q's vector of this wavefront leads its block, at lin_rows + q 64 -- an address without the row count)
     const double mu = IFAM ? lin_rows[r] : FAM ? p.fam[W + r] : 0.0;
     const double inv_mu = (mu != 0.0) ? 1.0 / mu : 0.0;  // (mu = 0: row in no cone)
@@ -150,7 +157,7 @@
     // ten) read the rest from the family buffer (L2) where they are used
     double ak[FAM_REG_ROWS], bk[FAM_REG_ROWS], ink[FAM_REG_ROWS];  // ink = 1 / ||a_k||^2
 #pragma unroll
-    for (int k = 0; k < (FAM && !RED ? FAM_REG_ROWS : 0); ++k) {
+    for (int k = 0; k < (FAM && !RED && !IFAMK ? FAM_REG_ROWS : 0); ++k) {
         // (the per-instance store holds nl >= 1 rows, not the shared description's capacity: a register beyond nl repeats row 0, never used;
         // a handle without any linear row holds one absent row there, a = 0, b = +inf, norm 1)
         const int kr = IFAM ? (k < nl ? k : 0) : k;
@@ -158,6 +165,23 @@
         bk[k] = lin_rows[LB + (size_t)(3 * kr + 1) * LW + r];
         ink[k] = 1.0 / lin_rows[LB + (size_t)(3 * kr + 2) * LW + r];
     }
+    // rows per knot: REGR rows of the step's slot and of the next step's in registers (the rest is read per use, as above), slot s of this
+    // lane at lin_rows + LB + s kslot + r
+    constexpr int REGR = IFAMK ? KNOT_REG_ROWS : FAM_REG_ROWS;
+    constexpr int KR = IFAMK && !RED && REGR > 0 ? REGR : 1;
+    const size_t kslot = IFAMK ? (size_t)3 * nl * 64 : 0;
+    KnotRows<KR> KA{}, KB{};  // the step's slot and the next step's, in turns
+    auto load_knot = [&](KnotRows<KR> &d, const double *kp) {
+        if constexpr (IFAMK && !RED) {
+#pragma unroll
+            for (int k = 0; k < REGR; ++k) {  // (a register beyond nl is written too, so that none of them is carried from step to step)
+                const bool has = k < nl;    // (uniform)
+                d.a[k] = has ? kp[(size_t)(3 * k + 0) * 64] : 0.0;
+                d.b[k] = has ? kp[(size_t)(3 * k + 1) * 64] : 0.0;
+                d.in[k] = has ? kp[(size_t)(3 * k + 2) * 64] : 0.0;
+            }
+        }
+    };
     // rounds of the cone list beyond the first (cones that share rows are projected one after another, as upstream does)
     const int nround = FAM ? (int)p.fam[fam_nround_offset(W, KT)] : 0;
     // wave-uniform switches: is either family in use at all?
@@ -215,7 +239,8 @@
 
     // Families: the two extra families for one (row, knot) element with rollout value `val`: returns the row's contribution to
     // the linear cost and the new duals.
-    auto families = [&](double val, double gc_old, double gl_old, double &gc_new, double &gl_new) -> double {
+    // (rows per knot: kreg holds the first REGR rows of the element's slot, krow points at the slot -- vector v of it at krow[v 64])
+    auto families = [&](double val, double gc_old, double gl_old, double &gc_new, double &gl_new, const KnotRows<KR> &kreg, const double *krow) -> double {
         double lx = 0.0;
         gc_new = gc_old;
         gl_new = gl_old;
@@ -248,8 +273,14 @@
                 double sv = s0;
 #pragma unroll 1
                 for (int k = 0; k < nl; ++k) {  // (uniform trip count; the rows' coefficients from the family buffer in L2)
-                    const double a_k = lin_rows[LB + (size_t)(3 * k + 0) * LW + r], b_k = lin_rows[LB + (size_t)(3 * k + 1) * LW + r];
-                    const double in_k = 1.0 / lin_rows[LB + (size_t)(3 * k + 2) * LW + r];
+                    double a_k, b_k, in_k;
+                    if constexpr (IFAMK) {  // (the knot's slot; its third vector holds the reciprocal)
+                        a_k = krow[(size_t)(3 * k + 0) * 64]; b_k = krow[(size_t)(3 * k + 1) * 64];
+                        in_k = krow[(size_t)(3 * k + 2) * 64];
+                    } else {
+                        a_k = lin_rows[LB + (size_t)(3 * k + 0) * LW + r]; b_k = lin_rows[LB + (size_t)(3 * k + 1) * LW + r];
+                        in_k = 1.0 / lin_rows[LB + (size_t)(3 * k + 2) * LW + r];
+                    }
                     const double prod = a_k * sv;
                     const double dx = group_sum<W>(is_x ? prod : 0.0), du = group_sum<W>(is_u ? prod : 0.0);  // a_k' x | a_k' u
                     sv = halfspace_project_element(sv, is_x ? dx : du, a_k, b_k, in_k);
@@ -292,16 +323,25 @@
             const double s0 = val + gl_old;
             double sv = s0;
 #pragma unroll
-            for (int k = 0; k < FAM_REG_ROWS; ++k) {
+            for (int k = 0; k < REGR; ++k) {
                 if (k < nl) {                                            // wave-uniform
-                    const double dot = group_matvec<W, KT>(ty, ak[k] * sv, 0.0);
-                    sv = halfspace_project_element(sv, dot, ak[k], bk[k], ink[k]);
+                    double a_r, b_r, in_r;
+                    if constexpr (IFAMK) { a_r = kreg.a[k]; b_r = kreg.b[k]; in_r = kreg.in[k]; }
+                    else { a_r = ak[k]; b_r = bk[k]; in_r = ink[k]; }
+                    const double dot = group_matvec<W, KT>(ty, a_r * sv, 0.0);
+                    sv = halfspace_project_element(sv, dot, a_r, b_r, in_r);
                 }
             }
 #pragma unroll 1
-            for (int k = FAM_REG_ROWS; k < nl; ++k) {                    // (uniform trip count)
-                const double a_k = lin_rows[LB + (size_t)(3 * k + 0) * LW + r], b_k = lin_rows[LB + (size_t)(3 * k + 1) * LW + r];
-                const double in_k = 1.0 / lin_rows[LB + (size_t)(3 * k + 2) * LW + r];
+            for (int k = REGR; k < nl; ++k) {                            // (uniform trip count)
+                double a_k, b_k, in_k;
+                if constexpr (IFAMK) {
+                    a_k = krow[(size_t)(3 * k + 0) * 64]; b_k = krow[(size_t)(3 * k + 1) * 64];
+                    in_k = krow[(size_t)(3 * k + 2) * 64];
+                } else {
+                    a_k = lin_rows[LB + (size_t)(3 * k + 0) * LW + r]; b_k = lin_rows[LB + (size_t)(3 * k + 1) * LW + r];
+                    in_k = 1.0 / lin_rows[LB + (size_t)(3 * k + 2) * LW + r];
+                }
                 const double dot = group_matvec<W, KT>(ty, a_k * sv, 0.0);
                 sv = halfspace_project_element(sv, dot, a_k, b_k, in_k);
             }
@@ -351,7 +391,14 @@
             pri = is_x ? fabs(x0v - snew) : 0.0;
             dua = is_x ? fabs(vold - snew) : 0.0;
             double gcn, gln, lx;
-            if constexpr (FAM) lx = families(x0v, gGC[lane], gGL[lane], gcn, gln);
+            const double *krow0 = nullptr;
+            KnotRows<KR> K0{};
+            if constexpr (IFAMK) {  // knot 0's slot for this call, and slot 1 for step 0 of the sweep behind it
+                krow0 = lin_rows + LB + r;
+                load_knot(K0, krow0);
+                load_knot(KA, krow0 + kslot);
+            }
+            if constexpr (FAM) lx = families(x0v, gGC[lane], gGL[lane], gcn, gln, K0, krow0);
             if (check) gV[on ? lane : gdummy] = vold;
             sG[on ? 64 + lane : ldummy] = s - snew;
             sV[on ? 64 + lane : ldummy] = snew;
@@ -384,7 +431,9 @@
             double *pwc = gGC + (pgv - gV), *pwl = gGL + (pgv - gV), *pwx = gLX + (pgv - gV);
             if constexpr (FAM) { A.gc = pgc[0]; A.gl = pgl[0]; }
             double gprev = 0.0;  // adaptive: g_i of the state rows; the x_0 column has no -g_0 term (y_vector starts at g_1)
-            auto fstep = [&](const FwdOperands &cur, FwdOperands &nxt) {
+            const double *pk = nullptr;  // rows per knot: the slot of the step (the slot behind the last step's is padding)
+            if constexpr (IFAMK) pk = lin_rows + LB + kslot + r;
+            auto fstep = [&](const FwdOperands &cur, FwdOperands &nxt, const KnotRows<KR> &kcur, KnotRows<KR> &knxt) {
                 const double w = is_x ? xcur : cur.dv;
                 pg += 64;  // operands of the next step, fetched while this step's mat-vec runs
                 pt += BRS;
@@ -398,11 +447,13 @@
                     nxt.g = pg[0]; nxt.vold = pg[VOFF]; nxt.lo = pt[0]; nxt.hi = pt[TOFF]; nxt.dv = pd[0];
                 }
                 if constexpr (FAM) { nxt.gc = pgc[0]; nxt.gl = pgl[0]; }
+                const double *krow = nullptr;
+                if constexpr (IFAMK) { krow = pk; pk += kslot; load_knot(knxt, pk); }
                 const double out = group_matvec<W, KT>(mf, w, cf);  // state lanes: x_{i+1}; input lanes: u_i
                 double gnew, snew;
                 project_element(out, cur.g, cur.lo, cur.hi, cur.vold, gnew, snew, pri, dua);
                 double gcn, gln, lx;
-                if constexpr (FAM) lx = families(out, cur.gc, cur.gl, gcn, gln);
+                if constexpr (FAM) lx = families(out, cur.gc, cur.gl, gcn, gln, kcur, krow);
                 if (check) *pgv = cur.vold;
                 ps[0] = gnew;
                 ps[VOFF] = snew;
@@ -429,16 +480,16 @@
                 // rolled: unrolled by two, the step with the adaptation's residuals needs more registers -- 265 VGPRs in the
                 // <16, 16> GMEM form, one wavefront per SIMD instead of two
                 for (int i = 0; i < N - 1; ++i) {
-                    fstep(A, B);
+                    fstep(A, B, KA, KB);
                     A = B;
                 }
             } else {
                 int i = 0;
                 for (; i + 2 <= N - 1; i += 2) {
-                    fstep(A, B);
-                    fstep(B, A);
+                    fstep(A, B, KA, KB);
+                    fstep(B, A, KB, KA);
                 }
-                if (i < N - 1) fstep(A, B);
+                if (i < N - 1) fstep(A, B, KA, KB);
             }
             x_last = xcur;   // x_{N-1} on state lanes
             g_last = gprev;  // g_{N-1}

@@ -461,6 +461,54 @@ class TinyMPC:
         if nlu:
             self.settings["en_input_linear"] = True
 
+    def set_linear_constraints_knots_batch(self, Alin_x, blin_x, Alin_u, blin_u, first: int = 0):
+        """Per-KNOT linear constraints a_i'x_i <= b_i / a_i'u_i <= b_i for instances first, first+1, ...: numpy arrays of shape
+        (nlx, nx, N, count), (nlx, N, count), (nlu, nu, N-1, count), (nlu, N-1, count) -- or contiguous float64 CUDA tensors with the same
+        memory layout, (count, N, nx, nlx), (count, N, nlx), (count, N-1, nu, nlu), (count, N-1, nlu); an empty side is None. The row counts
+        belong to the batch, the values to the knot and the instance; b = +inf switches one row off at one knot. The first call names the
+        whole batch, later calls may replace a sub-range; set_linear_constraints() returns every instance to shared rows, a whole-batch
+        set_linear_constraints_batch() to rows constant over the horizon. Enables the linear family of every non-empty side and keeps the
+        ADMM state: re-send the shifted rows between two mpc_step() ticks. Batched solvers only; runs on layout A."""
+        self._check_setup()
+        sides = []
+        for A, b, cols, knots, name in ((Alin_x, blin_x, self.nx, self.N, "x"), (Alin_u, blin_u, self.nu, self.N - 1, "u")):
+            empty = A is None or (hasattr(A, "numel") and A.numel() == 0) or (not hasattr(A, "numel") and np.asarray(A).size == 0)
+            if empty:
+                sides.append((None, None, 0, None, False))
+                continue
+            if hasattr(A, "data_ptr") and getattr(A, "is_cuda", False):
+                import torch
+                if not (hasattr(b, "data_ptr") and getattr(b, "is_cuda", False)):
+                    raise TinyMPCError(_lib.ERR_INVALID_INPUT, "per-knot linear rows: all must be CUDA tensors, or none")
+                ok = A.dtype == torch.float64 and b.dtype == torch.float64 and A.is_contiguous() and b.is_contiguous() and A.dim() == 4 and \
+                    b.dim() == 3 and A.shape[1] == knots and A.shape[2] == cols and tuple(b.shape) == (A.shape[0], knots, A.shape[3])
+                if not ok:
+                    raise TinyMPCError(_lib.ERR_INVALID_INPUT, "per-knot linear rows on the device must be contiguous float64 tensors of shape "
+                                       "(count, %d, %d, nl%s) and (count, %d, nl%s), got %s and %s"
+                                       % (knots, cols, name, knots, name, tuple(A.shape), tuple(b.shape)))
+                sides.append((C.c_void_p(A.data_ptr()), C.c_void_p(b.data_ptr()), int(A.shape[3]), int(A.shape[0]), True, (A, b)))
+            else:
+                A, b = np.asarray(A, dtype=np.float64), np.asarray(b, dtype=np.float64)
+                if A.ndim != 4 or A.shape[1] != cols or A.shape[2] != knots or b.shape != (A.shape[0], knots, A.shape[3]):
+                    raise TinyMPCError(_lib.ERR_INVALID_INPUT, "per-knot linear rows must be nl%s x %d x %d x count and nl%s x %d x count, got %s and %s"
+                                       % (name, cols, knots, name, knots, A.shape, b.shape))
+                A, b = _f(A), _f(b)
+                sides.append((_p(A), _p(b), int(A.shape[0]), int(A.shape[3]), False, (A, b)))
+        (pax, pbx, nlx, cx, dx, *keep_x), (pau, pbu, nlu, cu, du, *keep_u) = sides
+        if nlx and nlu and (cx != cu or dx != du):
+            raise TinyMPCError(_lib.ERR_INVALID_INPUT, "per-knot linear rows: both sides must have the same count and be on the same side of the bus")
+        on_device = dx if nlx else du
+        count = cx if nlx else cu if nlu else 0
+        if on_device:
+            import torch
+            torch.cuda.current_stream((keep_x or keep_u)[0][0].device).synchronize()  # (the set_x0_batch contract)
+        f = self._L.tinympc_set_linear_constraints_knots_batch_device if on_device else self._L.tinympc_set_linear_constraints_knots_batch
+        _lib.check(f(self._h, pax, pbx, nlx, pau, pbu, nlu, int(first), int(count)))
+        if nlx:
+            self.settings["en_state_linear"] = True
+        if nlu:
+            self.settings["en_input_linear"] = True
+
     def set_cone_slopes_batch(self, cx, cu, first: int = 0):
         """Per-instance cone slopes for instances first, first+1, ... on the cone structure set_cone_constraints() installed: numpy arrays
         of shape (ncx, count) / (ncu, count) in the order of the cone list -- or contiguous float64 CUDA tensors (count, ncx) /

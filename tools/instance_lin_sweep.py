@@ -21,7 +21,17 @@ Layout D (--d --parent-lib PATH): the same workload on a handle that called prep
               per-wavefront LDS term does to the plan
 Every measurement is a fresh process; the legs alternate, `--rounds` times each. The bar: inst-D lies below parent-A in EVERY round;
 the margin is reported against the spread of parent-A's rounds.
-    python tools/instance_lin_sweep.py --d --parent-lib /path/to/parent/libtinympc_hip.so"""
+    python tools/instance_lin_sweep.py --d --parent-lib /path/to/parent/libtinympc_hip.so
+
+Rows per knot (--knots [--parent-lib PATH] [--alt-lib PATH]): the same workload on layout A, with
+  const-A     the rows per instance, constant over the horizon (tinympc_set_linear_constraints_batch): k_admm_solve_ifam -- the yardstick
+  knots-same  the same rows repeated over the knots through tinympc_set_linear_constraints_knots_batch: k_admm_solve_ifamk
+  knots-vary  rows that differ per knot and instance through the same verb
+  parent-A    const-A on the library of the parent commit at --parent-lib: did the yardstick stay inside the parent's spread?
+  alt-same, alt-vary   the two knot legs on another build of this tree at --alt-lib (a variant of the kernel to compare against)
+and the wall time of tinympc_set_linear_constraints_knots_batch and of its _device form for the whole batch. No ratio is a condition;
+medians and spreads are reported, and the knot legs' distance to const-A.
+    python tools/instance_lin_sweep.py --knots --parent-lib /path/to/parent/libtinympc_hip.so"""
 import argparse
 import ctypes as C
 import json
@@ -37,6 +47,7 @@ sys.path.insert(0, ROOT)
 
 LEGS = ["shared-A", "per-inst"]
 D_LEGS = ["parent-A", "inst-D", "shared-D", "parent-A-4", "inst-D-4"]
+K_LEGS = ["const-A", "knots-same", "knots-vary"]
 
 
 def rows(prob, batch, seed=7, n=1):
@@ -128,6 +139,120 @@ def sweep_d(a):
                  float(np.median(ms[new])) / float(np.median(ms[old]))))
     print("distance to the floor: inst-D median %.4f against shared-D median %.4f (ratio %.3f)"
           % (float(np.median(ms["inst-D"])), float(np.median(ms["shared-D"])), float(np.median(ms["inst-D"])) / float(np.median(ms["shared-D"]))))
+
+
+def knot_rows(prob, batch, vary, seed=7):
+    """One state row and one input row per knot and instance in the knot verb's shapes: rows()'s, repeated (vary = False), or random unit
+    rows per knot and instance with the same offsets (vary = True)."""
+    ax, bx, au, bu = rows(prob, batch, seed)
+    N = prob.N
+    if not vary:
+        return (np.repeat(np.repeat(ax[:, :, None, None], N, axis=2), batch, axis=3), np.repeat(np.repeat(bx[:, None, None], N, axis=1), batch, axis=2),
+                np.repeat(np.repeat(au[:, :, None, None], N - 1, axis=2), batch, axis=3), np.repeat(np.repeat(bu[:, None, None], N - 1, axis=1), batch, axis=2))
+    rng = np.random.default_rng(seed + 1)
+    Ax, Au = rng.standard_normal((1, prob.nx, N, batch)), rng.standard_normal((1, prob.nu, N - 1, batch))
+    Ax, Au = Ax / np.linalg.norm(Ax, axis=1, keepdims=True), Au / np.linalg.norm(Au, axis=1, keepdims=True)
+    return Ax, np.einsum("kcnb,c->knb", Ax, prob.x0) + 0.3, Au, np.full((1, N - 1, batch), 0.2)
+
+
+def child_k(pkg, a):
+    """One process of the --knots sweep: one leg's kernel time on whatever library this process loaded; the knots-vary leg also times the
+    verb. One line."""
+    prob = pkg.problems.quadrotor(a.N)
+    os.environ.pop("TINYMPC_LAYOUT", None)
+    s = pkg.TinyMPC()
+    s.setup(prob.A, prob.B, prob.Q, prob.R, prob.N, batch=a.batch, rho=prob.rho, abs_pri_tol=0.0, abs_dua_tol=0.0, max_iter=a.iters)
+    s.set_bound_constraints(prob.x_min, prob.x_max, prob.u_min, prob.u_max)
+    if a.child in ("const-A", "parent-A"):
+        s.set_linear_constraints_batch(*(np.repeat(m[..., None], a.batch, axis=-1) for m in rows(prob, a.batch)))
+    else:
+        s.set_linear_constraints_knots_batch(*knot_rows(prob, a.batch, a.child.endswith("vary")))
+    s.set_x0_batch(pkg.problems.quadrotor_batch_x0(a.batch))
+    s.solve_timed()  # warm-up: first launch, table builds
+    out = dict(leg=a.child, kernel_ms=float(np.median([s.solve_timed() for _ in range(a.reps)])),
+               kernel="%s %s" % (s.launch_info()["layout"], s.jit_info()))
+    if a.child == "knots-vary":
+        L, dp = pkg.load_library(), pkg._lib.c_double_p
+        host = [np.asfortranarray(m) for m in knot_rows(prob, a.batch, True)]
+        dev = device_copy(pkg, host)
+        fresh = pkg.TinyMPC()
+        fresh.setup(prob.A, prob.B, prob.Q, prob.R, prob.N, batch=a.batch, rho=prob.rho)
+        wall, wall_dev = [], []
+        for _ in range(1 + a.reps):
+            t0 = time.perf_counter()
+            rc = L.tinympc_set_linear_constraints_knots_batch(fresh._h, host[0].ctypes.data_as(dp), host[1].ctypes.data_as(dp), 1,
+                                                              host[2].ctypes.data_as(dp), host[3].ctypes.data_as(dp), 1, 0, a.batch)
+            wall.append(1e3 * (time.perf_counter() - t0))
+            assert rc == 0, pkg._lib.last_error()
+        for _ in range(a.reps if dev else 0):
+            t0 = time.perf_counter()
+            rc = L.tinympc_set_linear_constraints_knots_batch_device(fresh._h, dev[0], dev[1], 1, dev[2], dev[3], 1, 0, a.batch)
+            wall_dev.append(1e3 * (time.perf_counter() - t0))
+            assert rc == 0, pkg._lib.last_error()
+        out.update(verb_host_ms=wall, verb_device_ms=wall_dev)
+        fresh.reset()
+    s.reset()
+    print("LIN-CHILD " + json.dumps(out), flush=True)
+
+
+def sweep_k(a):
+    """Starts the children of the --knots sweep (it never opens the GPU itself) and prints the table."""
+    legs = list(K_LEGS)
+    libs = {}
+    if a.parent_lib:
+        legs.append("parent-A")
+        libs["parent-A"] = a.parent_lib
+    if a.alt_lib:
+        legs += ["alt-same", "alt-vary"]
+        libs["alt-same"] = libs["alt-vary"] = a.alt_lib
+    for path in libs.values():
+        if not os.path.exists(path):
+            raise SystemExit("no library at " + path)
+    recs = {leg: [] for leg in legs}
+    for rnd in range(a.rounds):
+        for leg in legs if rnd % 2 == 0 else legs[::-1]:
+            env = dict(os.environ)
+            env.pop("TINYMPC_LAYOUT", None)
+            env.pop("TINYMPC_HIP_LIBRARY", None)
+            if leg in libs:
+                env["TINYMPC_HIP_LIBRARY"] = os.path.abspath(libs[leg])
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--knots", "--child", leg, "--batch", str(a.batch), "--N", str(a.N),
+                                "--iters", str(a.iters), "--reps", str(a.reps)], env=env, capture_output=True, text=True, timeout=300)
+            line = [l for l in r.stdout.splitlines() if l.startswith("LIN-CHILD ")]
+            if r.returncode != 0 or not line:
+                raise SystemExit("round %d (%s) failed with %d:\n%s\n%s" % (rnd, leg, r.returncode, r.stdout[-2000:], r.stderr[-2000:]))
+            recs[leg].append(json.loads(line[0][len("LIN-CHILD "):]))
+            print("# round %d %-10s %.4f ms" % (rnd, leg, recs[leg][-1]["kernel_ms"]), flush=True)
+    print("per-knot linear rows on layout A: %d quadrotors N=%d x %d forced iterations, 1 state row + 1 input row; kernel ms (median of %d "
+          "launches per round, %d rounds, a fresh process each, legs alternating)" % (a.batch, a.N, a.iters, a.reps, a.rounds))
+    ms = {leg: [r["kernel_ms"] for r in recs[leg]] for leg in legs}
+    for leg in legs:
+        print("%-10s | %s | median %.4f | spread %.4f - %.4f | %s" % (leg, " ".join("%.4f" % v for v in ms[leg]), float(np.median(ms[leg])),
+                                                                     min(ms[leg]), max(ms[leg]), recs[leg][0]["kernel"]))
+    base = float(np.median(ms["const-A"]))
+    steps = a.iters * (a.N - 1)
+    for leg in legs:
+        if leg in ("const-A", "parent-A"):
+            continue
+        med = float(np.median(ms[leg]))
+        waves = (a.batch + 3) // 4  # (16 lanes per instance: four instances per wavefront)
+        mb = waves * 3 * 512 / 1e6  # one slot of 3 nl = 3 vectors of 512 bytes per wavefront and forward step
+        print("%-10s against const-A: ratio of medians %.3f, +%.4f ms over %d forward steps; the slots read are %d wavefronts x 3 lines x 512 B = "
+              "%.2f MB per step, %.2f GB per solve (%.1f TB/s if the difference were that traffic alone)"
+              % (leg, med / base, med - base, steps, waves, mb, mb * steps / 1e3, mb * steps / 1e6 / ((med - base) / 1e3) if med > base else float("nan")))
+    if "parent-A" in ms:
+        med, lo, hi = base, min(ms["parent-A"]), max(ms["parent-A"])
+        print("const-A median inside parent-A's spread: %s (%.4f against %.4f - %.4f; ratio of medians %.3f)"
+              % ("yes" if lo <= med <= hi else "NO", med, lo, hi, med / float(np.median(ms["parent-A"]))))
+    for key, name in (("verb_host_ms", "set_linear_constraints_knots_batch"), ("verb_device_ms", "set_linear_constraints_knots_batch_device")):
+        first = [r[key][0] for r in recs["knots-vary"] if r[key]]
+        rest = [v for r in recs["knots-vary"] for v in (r[key][1:] if key == "verb_host_ms" else r[key])]
+        if not rest:
+            print("%-42s not measured (no device memory could be filled)" % name)
+            continue
+        print("%-42s %d instances, wall ms: %s median %.3f (min %.3f, max %.3f)"
+              % (name, a.batch, ("first call %s | repeats" % " ".join("%.3f" % v for v in first)) if key == "verb_host_ms" else "calls",
+                 float(np.median(rest)), min(rest), max(rest)))
 
 
 def device_copy(pkg, arrays):
@@ -234,11 +359,13 @@ def main():
     ap.add_argument("--child", default="", help=argparse.SUPPRESS)
     ap.add_argument("--d", action="store_true")
     ap.add_argument("--parent-lib", default="")
+    ap.add_argument("--knots", action="store_true")
+    ap.add_argument("--alt-lib", default="")
     a = ap.parse_args()
     if not a.child:
-        return sweep_d(a) if a.d else sweep(a)
+        return sweep_k(a) if a.knots else sweep_d(a) if a.d else sweep(a)
     import __graft_entry__ as ge
-    (child_d if a.d else child)(ge.load_package(), a)
+    (child_k if a.knots else child_d if a.d else child)(ge.load_package(), a)
 
 
 if __name__ == "__main__":
