@@ -354,8 +354,17 @@ int tinympc_set_linear_constraints_batch_device(tinympc_solver *s, const double 
  * nothing. reset_workspace, update_settings, every reference, track and bound verb (shared or per instance), set_cone_constraints,
  * set_cone_slopes_batch, the solve verbs, mpc_step_batch and prepare keep mode and rows; per-instance cone slopes combine with it (the
  * other half of the same mode, the same store).
- * The mode runs on layout A only, before and after tinympc_prepare: tinympc_get_layout says 'A', tinympc_get_jit_info carries
- * " per-knot-linear" (in place of " per-instance-linear") and claims no refusal of a specialisation, since none exists. Refusals are
+ * The mode runs on layout A (tinympc_get_layout 'A', " per-knot-linear" in tinympc_get_jit_info in place of " per-instance-linear")
+ * unless tinympc_prepare was called on the handle (before or after this verb): then batches that run the register-resident throughput
+ * kernel (layout D) keep it under the conditions of tinympc_set_linear_constraints_batch -- nx+nu <= 16, references and bounds constant
+ * over the horizon (shared or per instance), no two cones share a row -- where every wavefront's share of a compute unit's LDS holds
+ * its four instances' rows of ALL knots, 3 max(nlx, nlu) N vectors of 64 doubles: one row per side up to N = 22, two up to N = 12,
+ * three up to N = 8. The kernel is compiled in for the quadrotor at N = 20 with one row, specialised at run time otherwise. Without
+ * tinympc_prepare, with trajectories, tracks, per-knot bounds, wider systems, cones in rounds, or after a refused plan
+ * (tinympc_get_jit_info then reads "refused(<reason>) ... per-knot-linear") the mode stays on layout A, and a handle moves between the
+ * two from one launch to the next as its configuration changes; the ADMM state, the rows' duals included, is shared, so a warm start
+ * carries over. On layout D, too, an instance whose rows are equal at every knot gives, bit for bit, what
+ * tinympc_set_linear_constraints_batch gives for those rows there. Refusals are
  * those of tinympc_set_linear_constraints_batch: with per-instance models or rho, adaptive rho, nx+nu > 64 or more cones / rounds than
  * the generic kernels hold a solve returns TINYMPC_ERR_UNSUPPORTED (never a solve with other rows), and so does tinympc_session_begin.
  * Single-instance handles (batch == 1): TINYMPC_ERR_UNSUPPORTED -- their kernels read the shared description.

@@ -267,6 +267,8 @@ struct SolveParams {
     // slot 0 is knot 0 on the state lanes (absent rows on the input lanes), slot i+1 what forward step i finishes -- knot i+1 on the state
     // lanes, knot i on the input lanes --, so that a step reads whole 512-byte lines. Built by k_build_inst_lin_knots; a block is
     // inst_fam_block_doubles(ilin_nl, ilin_knots) doubles, and one slot of padding lies behind the last group's (the sweep fetches a slot ahead).
+    // Layout D's per-instance linear-row form reads the same store in its per-knot variant (tinympc_solve_d.hip, IKNOT): a wavefront stages
+    // its group's N slots into its own LDS region, verbatim -- the skew is that of its forward step too, and the third vector is the reciprocal.
 };
 
 // Per-instance references and bounds of a batched handle (k_store_inst_refs, k_build_inst_tables; tinympc_kernels.hip). The references
@@ -486,7 +488,7 @@ bool solve_e_supported(int nx, int nu, int N, bool const_tables, bool families, 
 hipError_t launch_solve_e(const SolveParams &p, const FamilyStructure &fs, hipStream_t stream);
 void solve_e_describe(int nx, int nu, int N, bool const_tables, bool families, const FamilyStructure &fs, char *buf, size_t len);
 void solve_jit_describe(int W, int nx, int nu, int N, bool const_tables, bool families, bool adaptive, char *buf, size_t len, bool goal = false,
-                        bool models = false, int ilin = 0, bool icone = false);
+                        bool models = false, int ilin = 0, bool icone = false, int knots = 0);
 // Layout F (tinympc_solve_f.hip, run-time specialised only): the latency kernel with compile-time shape and structure
 bool solve_f_plan(int nx, int nu, int N, bool const_tables, bool families, const FamilyStructure &fs, int *chunk_len, int *chunks, int *wpg, size_t *lds_bytes);
 bool solve_f_supported(int nx, int nu, int N, bool const_tables, bool families, const FamilyStructure &fs);  // plans AND compiles
@@ -635,15 +637,16 @@ hipError_t launch_solve_m(const SolveParams &p, hipStream_t stream);
 // ilin: the per-instance linear-row form (-DTINY_JIT_ILIN=<nl> with families and goal: the families' variant reading every instance's own
 // rows, SolveParams::ilin, staged per wavefront; 16 lanes, constant tables; 0: off). With TINYMPC_JIT=0 only a compiled-in one.
 // icone (with ilin): ... and every instance's own cone slope (-DTINY_JIT_ICONE=1: the per-instance families form with the slope half on)
+// knots (with ilin): ... the rows of every knot (-DTINY_JIT_IKNOT=1; knots = N, the slots per group of SolveParams::ilin, staged whole; 0: off)
 bool solve_jit_supported(int W, int nx, int nu, int N, bool const_tables, bool families = false, bool adaptive = false, bool goal = false,
-                         bool models = false, int ilin = 0, bool icone = false);
-hipError_t launch_solve_jit(const SolveParams &p, int W, hipStream_t stream, bool models = false, int ilin = 0, bool icone = false);
+                         bool models = false, int ilin = 0, bool icone = false, int knots = 0);
+hipError_t launch_solve_jit(const SolveParams &p, int W, hipStream_t stream, bool models = false, int ilin = 0, bool icone = false, int knots = 0);
 bool solve_jit_refill_supported(int W, int nx, int nu, int N, bool const_tables);   // (compiles the slot-refill variant on first use)
 int solve_jit_resident_wavefronts(int W, int nx, int nu, int N, bool const_tables);  // wavefronts of the shape's plan the device holds at once
 int solve_jit_workgroups(int W, int nx, int nu, int N, bool const_tables, int groups, bool families = false, bool adaptive = false, bool goal = false,
-                         bool models = false, int ilin = 0, bool icone = false);
+                         bool models = false, int ilin = 0, bool icone = false, int knots = 0);
 size_t solve_jit_lds_bytes(int W, int nx, int nu, int N, bool const_tables, bool families = false, bool adaptive = false, bool goal = false,
-                           bool models = false, int ilin = 0, bool icone = false);  // per workgroup, from the plan  // 8 wavefronts per workgroup, 4 on the long-horizon plan
+                           bool models = false, int ilin = 0, bool icone = false, int knots = 0);  // per workgroup, from the plan  // 8 wavefronts per workgroup, 4 on the long-horizon plan
 #endif  // !__HIPCC_RTC__
 
 // Doubles of working state per group in layout A (G and V with N+2 rows, D with 64 dummy slots).

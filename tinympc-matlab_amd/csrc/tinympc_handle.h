@@ -112,14 +112,15 @@ struct InstState {
     bool lin = false;
     int lin_nlx = 0, lin_nlu = 0, lin_nl = 0;
     // ... and its third state, rows per KNOT (tinympc_set_linear_constraints_knots_batch): lin_knots = N while it is on, 0 otherwise. The store
-    // then holds N slots of rows per group (inst_fam_block_doubles), the mode runs on layout A's InstFamiliesKnots variant only
-    // (lin_wants_d is false), and a whole-batch tinympc_set_linear_constraints_batch or the shared verb ends it.
+    // then holds N slots of rows per group (inst_fam_block_doubles), the mode runs on layout A's InstFamiliesKnots variant -- or, under
+    // lin_wants_d's conditions and where its per-wavefront plan holds the N slots, on the per-knot variant of layout D's ILIN form --, and a whole-batch tinympc_set_linear_constraints_batch or the shared verb ends it.
     int lin_knots = 0;
     // layout D's per-instance linear-row form (16 lanes; compiled in or run-time specialised on the shape AND lin_nl): -1 not asked yet,
     // 0 no, 1 yes -- the answer for d_lin_nl rows; another count (a whole-batch call) makes it unknown again (resolve_plan). The cones are
     // no part of the specialisation: whether their structure is one the form takes is asked at every launch (lin_wants_d).
     int d_lin = -1, d_lin_nl = 0;
     bool d_lin_cones = false;                // ... and for the slope half on / off (ICONE: the form that reads the slope per instance)
+    int d_lin_knots = 0;                     // ... and for rows per knot (lin_knots of the answer) or rows constant over the horizon (0)
     double *lrows = nullptr;
     size_t lrows_cap = 0;                    // doubles lrows was allocated for
     double *lstage = nullptr;                // device staging of host input (the shared rows of a sub-range first call: a block of their own, freed in the call)

@@ -170,12 +170,15 @@ bool lin_runs(const tinympc_solver *s) {
 // where the handle runs layout D, 16 lanes per instance, references and bounds constant over the horizon (shared or per instance: no
 // trajectories, tracks or per-knot bounds), and a cone structure layout D's shared families kernel takes (decide_layout_d_variants: no
 // rounds of overlapping cones). Whether the kernel exists for the mode's row count is inst.d_lin (resolve_plan).
-// Rows per knot (tinympc_set_linear_constraints_knots_batch) have no layout D form: they stay on layout A's InstFamiliesKnots variant.
+// Rows per knot (tinympc_set_linear_constraints_knots_batch) take the same way: the form's per-knot variant (lin_d_knots), whose
+// per-wavefront plan holds N slots of rows -- where it does not fit the mode stays on layout A's InstFamiliesKnots variant.
+int lin_d_knots(const tinympc_solver *s) { return s->inst.lin ? s->inst.lin_knots : 0; }
 bool lin_wants_d(const tinympc_solver *s) {
-    return lin_runs(s) && !s->inst.lin_knots && s->specialise_asked && s->layout_d && s->W == 16 && s->iref_goal() && family_structure(s).nround <= 1;
+    return lin_runs(s) && s->specialise_asked && s->layout_d && s->W == 16 && s->iref_goal() && family_structure(s).nround <= 1;
 }
 bool lin_on_d(const tinympc_solver *s) {
-    return lin_wants_d(s) && s->inst.d_lin == 1 && s->inst.d_lin_nl == s->ifam_nl() && s->inst.d_lin_cones == s->inst.cones;
+    return lin_wants_d(s) && s->inst.d_lin == 1 && s->inst.d_lin_nl == s->ifam_nl() && s->inst.d_lin_cones == s->inst.cones &&
+           s->inst.d_lin_knots == lin_d_knots(s);
 }
 
 }  // namespace
@@ -194,7 +197,8 @@ namespace host {
 //                                      (the mode of tinympc_set_model_batch AND tinympc_set_rho_batch: one form, rho always read per instance)
 //   per-instance linear rows           D's ILIN form (only after tinympc_prepare: 16 lanes, references and bounds constant over the horizon, cones
 //                                      without rounds, a horizon and row count its per-wavefront plan holds)  >  A's InstFamilies variant,
-//                                      (rows per knot: its InstFamiliesKnots variant, never layout D),
+//                                      (rows per knot: the form's per-knot variant, N slots of rows per wavefront -- one row up to N=22, two up
+//                                      to N=12, three up to N=8  >  A's InstFamiliesKnots variant),
 //                                      whatever else is per instance (references, bounds) or shared (cones); with
 //                                      per-instance models / rho, adaptive rho, layout M or a cone structure beyond the generic kernels, launch() refuses
 LaunchPlan current_plan(const tinympc_solver *s) {
@@ -238,8 +242,9 @@ LaunchPlan current_plan(const tinympc_solver *s) {
             pl.layout = 'D';
             pl.jit = true;
             const int ilin = pl.inst_lin ? s->ifam_nl() : 0;  // (the ILIN form: the families' kernel whichever sides are enabled)
-            pl.workgroups = solve_jit_workgroups(s->W, s->nx, s->nu, s->N, ct, s->groups, fam || ilin, adaptive, pl.inst_refs, pl.inst_models, ilin, ilin && s->inst.cones);
-            pl.lds_bytes = solve_jit_lds_bytes(s->W, s->nx, s->nu, s->N, ct, fam || ilin, adaptive, pl.inst_refs, pl.inst_models, ilin, ilin && s->inst.cones);
+            pl.workgroups = solve_jit_workgroups(s->W, s->nx, s->nu, s->N, ct, s->groups, fam || ilin, adaptive, pl.inst_refs, pl.inst_models, ilin, ilin && s->inst.cones,
+                                                 ilin ? lin_d_knots(s) : 0);
+            pl.lds_bytes = solve_jit_lds_bytes(s->W, s->nx, s->nu, s->N, ct, fam || ilin, adaptive, pl.inst_refs, pl.inst_models, ilin, ilin && s->inst.cones, ilin ? lin_d_knots(s) : 0);
             break;
         }
         case KernelId::D_COMPILED:
@@ -299,12 +304,14 @@ int resolve_plan(tinympc_solver *s) {
         if (s->inst.d_models < 0 && models_want_d(s))
             s->inst.d_models = solve_jit_supported(s->W, s->nx, s->nu, s->N, true, false, false, false, true) ? 1 : 0;
         // ... and the linear-row form's, for the mode's row count (compiled in for the quadrotor N=20 with one row, specialised now
-        // otherwise; a refusal leaves the mode on layout A). Another count is another specialisation: asked again.
-        if (s->inst.fam() && (s->inst.d_lin_nl != s->ifam_nl() || s->inst.d_lin_cones != s->inst.cones)) s->inst.d_lin = -1;
+        // otherwise; a refusal leaves the mode on layout A). Another count is another specialisation: asked again -- and so is the other
+        // of rows constant over the horizon and rows per knot (compiled in for the same quadrotor with one row).
+        if (s->inst.fam() && (s->inst.d_lin_nl != s->ifam_nl() || s->inst.d_lin_cones != s->inst.cones || s->inst.d_lin_knots != lin_d_knots(s))) s->inst.d_lin = -1;
         if (s->inst.d_lin < 0 && lin_wants_d(s)) {
             s->inst.d_lin_nl = s->ifam_nl();
             s->inst.d_lin_cones = s->inst.cones;
-            s->inst.d_lin = solve_jit_supported(s->W, s->nx, s->nu, s->N, true, true, false, true, false, s->ifam_nl(), s->inst.cones) ? 1 : 0;
+            s->inst.d_lin_knots = lin_d_knots(s);
+            s->inst.d_lin = solve_jit_supported(s->W, s->nx, s->nu, s->N, true, true, false, true, false, s->ifam_nl(), s->inst.cones, lin_d_knots(s)) ? 1 : 0;
         }
         return TINYMPC_OK;
     }
@@ -547,7 +554,7 @@ int launch(tinympc_solver *s, bool timed) {
             HIP_TRY(launch_solve_m(p, s->stream));
             break;
         case KernelId::D_JIT:  // (box path, families with everything in registers, or adaptive rho per lane)
-            HIP_TRY(launch_solve_jit(p, s->W, s->stream, pl.inst_models, pl.inst_lin ? s->ifam_nl() : 0, pl.inst_lin && s->inst.cones));
+            HIP_TRY(launch_solve_jit(p, s->W, s->stream, pl.inst_models, pl.inst_lin ? s->ifam_nl() : 0, pl.inst_lin && s->inst.cones, pl.inst_lin ? lin_d_knots(s) : 0));
             break;
         case KernelId::D_COMPILED:
             if (lean_applies(s, pl) && !p.x0_mirror && !p.u0_host && !p.refill_next)
@@ -647,14 +654,14 @@ static int jit_info_text(tinympc_solver *s, char *buf, int len) {
         if (pl.kernel == KernelId::D_JIT) {
             if ((rc = bind_device(s))) return rc;
             const int ilin = pl.inst_lin ? s->ifam_nl() : 0;
-            solve_jit_describe(s->W, s->nx, s->nu, s->N, true, ilin != 0, false, buf, (size_t)len, true, pl.inst_models, ilin, ilin && s->inst.cones);
+            solve_jit_describe(s->W, s->nx, s->nu, s->N, true, ilin != 0, false, buf, (size_t)len, true, pl.inst_models, ilin, ilin && s->inst.cones, ilin ? lin_d_knots(s) : 0);
             strncat(buf, words, (size_t)len - strlen(buf) - 1);
             strncat(buf, " goal", (size_t)len - strlen(buf) - 1);
-        } else if (pl.inst_lin && lin_wants_d(s) && s->inst.d_lin == 0 && s->inst.d_lin_nl == s->ifam_nl() && s->inst.d_lin_cones == s->inst.cones) {  // asked for and refused: layout A, and why
+        } else if (pl.inst_lin && lin_wants_d(s) && s->inst.d_lin == 0 && s->inst.d_lin_nl == s->ifam_nl() && s->inst.d_lin_cones == s->inst.cones && s->inst.d_lin_knots == lin_d_knots(s)) {  // asked for and refused: layout A, and why
             if ((rc = bind_device(s))) return rc;
-            solve_jit_describe(s->W, s->nx, s->nu, s->N, true, true, false, buf, (size_t)len, true, false, s->ifam_nl(), s->inst.cones);
+            solve_jit_describe(s->W, s->nx, s->nu, s->N, true, true, false, buf, (size_t)len, true, false, s->ifam_nl(), s->inst.cones, lin_d_knots(s));
             strncat(buf, words, (size_t)len - strlen(buf) - 1);
-        } else if (pl.inst_lin && lin_runs(s) && !s->inst.lin_knots && s->specialise_asked && s->layout_d && s->W == 16 && s->iref_goal() && family_structure(s).nround > 1) {
+        } else if (pl.inst_lin && lin_runs(s) && s->specialise_asked && s->layout_d && s->W == 16 && s->iref_goal() && family_structure(s).nround > 1) {
             // asked for, and only the cones keep the mode off layout D: layout A, and why
             snprintf(buf, (size_t)len, "refused(cones that share rows run in rounds: layout D's per-instance form takes cones without rounds) layout=%c%s",
                      pl.layout, words);

@@ -273,26 +273,29 @@ constexpr int D_IMOD_WAVE_DOUBLES = 4 * D_IMOD_STRIDE;
 // number of slack slots in LDS; -1 if the shape does not fit the plan (cu_waves wavefronts per CU: 8, or 4 for the
 // long-horizon plan with one wavefront per SIMD and 512 registers)
 // (ilin: the row count of the per-instance linear-row form, 0 otherwise -- 3 ilin vectors of 64 doubles per WAVEFRONT in place of the
-// workgroup's D_FAM_DOUBLES)
-__host__ __device__ constexpr int d_vl(int nu, int N, bool ct, int wpg, int cu_waves = 8, bool fam = false, bool adapt = false, bool imod = false, int ilin = 0) {
+// workgroup's D_FAM_DOUBLES; knots: the slots of its per-knot form, N of them, each 3 ilin vectors -- 0: rows constant over the horizon)
+__host__ __device__ constexpr int d_ilin_wave_doubles(int ilin, int knots) { return 3 * ilin * 64 * (knots > 0 ? knots : 1); }
+__host__ __device__ constexpr int d_vl(int nu, int N, bool ct, int wpg, int cu_waves = 8, bool fam = false, bool adapt = false, bool imod = false, int ilin = 0,
+                                       int knots = 0) {
     const int ns = N - 1;
     const int wg_doubles = D_LDS_PER_CU / 8 * wpg / cu_waves - (imod ? 0 : D_OPS_DOUBLES + D_START_DOUBLES) - (ct ? 0 : d_tab_doubles(N)) - (fam && !ilin ? D_FAM_DOUBLES : 0) - (adapt ? D_ADAPT_DOUBLES : 0);
 #if TINY_TRIM_DSTORE
     const int wave_doubles = wg_doubles / wpg - d_d_doubles(nu, N) - D_DUMP_DOUBLES(nu) - (imod ? D_IMOD_WAVE_DOUBLES : 0);
 #else
-    const int wave_doubles = wg_doubles / wpg - d_d_doubles(nu, N) - (imod ? D_IMOD_WAVE_DOUBLES : 0) - 3 * ilin * 64;
+    const int wave_doubles = wg_doubles / wpg - d_d_doubles(nu, N) - (imod ? D_IMOD_WAVE_DOUBLES : 0) - d_ilin_wave_doubles(ilin, knots);
 #endif
     if (wave_doubles < 0) return -1;
     const int vlmax = wave_doubles / 64;
     const int want = ns > D_VREG_MAX ? ns - D_VREG_MAX : 0;
     return want <= vlmax ? want : -1;
 }
-__host__ __device__ constexpr size_t d_lds_bytes(int nu, int N, bool ct, int wpg, int vl, bool fam = false, bool adapt = false, bool imod = false, int ilin = 0) {
+__host__ __device__ constexpr size_t d_lds_bytes(int nu, int N, bool ct, int wpg, int vl, bool fam = false, bool adapt = false, bool imod = false, int ilin = 0,
+                                                 int knots = 0) {
     return sizeof(double) * ((size_t)(imod ? 0 : D_OPS_DOUBLES + D_START_DOUBLES) + (ct ? 0 : d_tab_doubles(N)) + (fam && !ilin ? D_FAM_DOUBLES : 0) + (adapt ? D_ADAPT_DOUBLES : 0) +
 #if TINY_TRIM_DSTORE
                              (size_t)wpg * (vl * 64 + D_DUMP_DOUBLES(nu) + d_d_doubles(nu, N) + (imod ? D_IMOD_WAVE_DOUBLES : 0)));
 #else
-                             (size_t)wpg * (vl * 64 + d_d_doubles(nu, N) + (imod ? D_IMOD_WAVE_DOUBLES : 0) + 3 * ilin * 64));
+                             (size_t)wpg * (vl * 64 + d_d_doubles(nu, N) + (imod ? D_IMOD_WAVE_DOUBLES : 0) + d_ilin_wave_doubles(ilin, knots)));
 #endif
 }
 
@@ -392,7 +395,7 @@ __device__ __forceinline__ bool wave_may_converge_d32(unsigned long long bad, un
 // arithmetic of an instance is that of the plain kernel (bit-identical results: tests/test_hip_parity.py); what changes is that
 // a wavefront's time is the sum of what its rows worked, not four times its slowest instance.
 template <int NX, int NU, int N, bool CT, int WPG, int VL, bool FAM = false, bool ADAPT = false, bool TWO_PER_SIMD = true, bool HOSTX = false,
-          bool REFILL = false, bool IGOAL = false, bool IMOD = false, int ILIN = 0, bool ICONE = false>
+          bool REFILL = false, bool IGOAL = false, bool IMOD = false, int ILIN = 0, bool ICONE = false, bool IKNOT = false>
 #else
 // IGOAL: the per-instance goal form (every instance's references and bounds constant over the horizon; k_admm_solve_d_gbnd) -- the
 // four table constants lr_c, pNref, lo_c and hi_c come per lane from SolveParams::iref_lr / iref_pn / ibnd ([instance][16], ibnd's hi
@@ -406,14 +409,19 @@ template <int NX, int NU, int N, bool CT, int WPG, int VL, bool FAM = false, boo
 // ICONE (with ILIN): the cone slope mu is the lane's instance's too (tinympc_set_cone_slopes_batch: the store's round-0 vector; a handle
 // without linear rows runs the form with one absent row); without it the form's code is what it was before the slopes' half existed. Cones, role and the enable flags stay those of the shared description, the four table constants come per lane as in the goal form
 // (layout A's variant of the mode always runs on per-instance reference and clamp rows). The per-element arithmetic is FAM's.
+// IKNOT (with ILIN): the rows of every KNOT (tinympc_set_linear_constraints_knots_batch after tinympc_prepare) -- the group's block of
+// SolveParams::ilin holds N slots of 3 nl vectors in the forward sweep's own skew (k_build_inst_lin_knots: slot 0 is knot 0 on the state
+// lanes, slot q+1 what forward step q finishes), the third vector already 1 / ||a_k||^2. The wavefront stages the whole block, verbatim,
+// and `families` reads the slot of its call: the horizon is unrolled, so a slot is a compile-time offset of the same three reads.
 template <int NX, int NU, int N, bool CT, int WPG, int VL, bool FAM = false, bool ADAPT = false, bool TWO_PER_SIMD = true, bool HOSTX = false,
-          bool REFILL = false, bool IGOAL = false, bool IMOD = false, int ILIN = 0, bool ICONE = false>
+          bool REFILL = false, bool IGOAL = false, bool IMOD = false, int ILIN = 0, bool ICONE = false, bool IKNOT = false>
 #endif
 __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double *smem) {
     static_assert(!(FAM && ADAPT), "adaptive rho and the constraint families exclude each other (as in the C ABI)");
     static_assert(!IMOD || (IGOAL && CT && !FAM && !ADAPT && !REFILL && !HOSTX && !TINY_LEAN),
                   "per-instance models: the goal form of the box path (its rows are always built per instance), plain sweeps");
     static_assert(!ICONE || ILIN > 0, "per-instance cone slopes: with the per-instance rows' form (one absent row where there are none)");
+    static_assert(!IKNOT || ILIN > 0, "rows per knot: a form of the per-instance rows");
     static_assert(ILIN == 0 || (ILIN > 0 && ILIN <= MAX_LIN_ROWS && FAM && IGOAL && CT && !ADAPT && !IMOD && !REFILL && !HOSTX && !TINY_LEAN),
                   "per-instance linear rows: the families' variant in the goal form (references and bounds constant over the horizon), plain sweeps");
 #if TINY_REFILL
@@ -463,11 +471,15 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
     double *sV = sAd + (ADAPT ? D_ADAPT_DOUBLES : 0) + (size_t)wv * (VL * 64 + D_DUMP_DOUBLES(NU) + d_d_doubles(NU, N));
     double *sD = sV + VL * 64 + D_DUMP_DOUBLES(NU);  // (rows -1 and -2 of d: written by the dump lanes of the lean backward sweeps, never read)
 #else
-    double *sV = sAd + (ADAPT ? D_ADAPT_DOUBLES : 0) + (size_t)wv * (VL * 64 + d_d_doubles(NU, N) + (IMOD ? D_IMOD_WAVE_DOUBLES : 0) + 3 * ILIN * 64);
+    double *sV = sAd + (ADAPT ? D_ADAPT_DOUBLES : 0) + (size_t)wv * (VL * 64 + d_d_doubles(NU, N) + (IMOD ? D_IMOD_WAVE_DOUBLES : 0) + d_ilin_wave_doubles(ILIN, IKNOT ? N : 0));
     double *sD = sV + VL * 64;
 #endif
     double *sOpsW = sD + d_d_doubles(NU, N);  // IMOD: [4 instances][D_IMOD_STRIDE]
-    double *sLinW = sD + d_d_doubles(NU, N);  // ILIN: [3 nl][64], this wavefront's group of SolveParams::ilin (never together with IMOD)
+    double *sLinW = sD + d_d_doubles(NU, N);  // ILIN: [3 nl][64], this wavefront's group of SolveParams::ilin (never together with IMOD); IKNOT: [N slots][3 nl][64]
+    // (a slot's rows lie LIN_SLOT doubles behind the last slot's: 0 where the rows are constant over the horizon -- one code path)
+    constexpr int LIN_SLOT = IKNOT ? 3 * ILIN * 64 : 0;
+    static_assert(!IKNOT || sizeof(double) * (D_OPS_DOUBLES + D_START_DOUBLES + VL * 64 + d_d_doubles(NU, N) + d_ilin_wave_doubles(ILIN, N)) < 65536,
+                  "rows per knot: the last slot's reads stay below the 16-bit ds offset field, whatever constant part of the address the compiler folds in");
 
     // ---- workgroup-shared: the two sweep operators, transposed to [k][r] (conflict-free row reads), and the tables
     if constexpr (IMOD) {
@@ -502,7 +514,14 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
             sAd[i] = (k < KT) ? p.adapt[(size_t)tbl * W * KT + (size_t)rr * KT + k] : 0.0;
         }
     }
-    if constexpr (ILIN > 0) {
+    if constexpr (IKNOT) {
+        // ... per wavefront: its group's N slots of 3 nl vectors, verbatim -- the slots are in the sweep's skew and the third vector is the
+        // reciprocal already (k_build_inst_lin_knots; lanes beyond the batch: a = 0, b = +inf, reciprocal 1 -- the row is off)
+        if (grp_ok) {
+            const double *const rows_g = p.ilin + (size_t)grp * inst_fam_block_doubles(ILIN, N) + INST_FAM_SLOPE_ROWS * 64;
+            for (int i = lane; i < d_ilin_wave_doubles(ILIN, N); i += 64) sLinW[i] = rows_g[i];
+        }
+    } else if constexpr (ILIN > 0) {
         // ... per wavefront: the 3 nl vectors of its own group, in the kernel's lane order as k_build_inst_lin wrote them (lanes beyond the
         // batch: a = 0, b = +inf, norm 1 -- the row is off); the third vector as its reciprocal, like the shared copy below
         if (grp_ok) {
@@ -598,7 +617,7 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
         mu = p.fam[W + r];
         // (ICONE: the lane's INSTANCE's slope, tinympc_set_cone_slopes_batch -- round 0's vector in front of the group's rows in SolveParams::ilin;
         // read once, here: the iteration loop gains no load. The form takes cones without rounds.)
-        if constexpr (ICONE) mu = grp_ok ? p.ilin[(size_t)grp * inst_fam_group_doubles(ILIN) + lane] : mu;
+        if constexpr (ICONE) mu = grp_ok ? p.ilin[(size_t)grp * (IKNOT ? inst_fam_block_doubles(ILIN, N) : inst_fam_group_doubles(ILIN)) + lane] : mu;
         inv_mu = (mu != 0.0) ? 1.0 / mu : 0.0;  // (mu = 0: row in no cone)
         famc = p.fam[2 * W + r] != 0.0;
         faml = p.fam[3 * W + r] != 0.0;
@@ -608,7 +627,9 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
     }
     // One (row, knot) element of the two extra families, exactly as in k_admm_solve_fam / k_admm_solve_c: returns the element's
     // contribution to the linear cost and the new duals. All 16 lanes of the instance take part (no EXEC masking in this kernel).
-    auto families = [&](double val, double gc_old, double gl_old, double &gc_new, double &gl_new) -> double {
+    // (slot: the knot slot of the call's element in the per-knot form -- 0 for knot 0, q + 1 for forward step q; a constant at every call)
+    auto families = [&](double val, double gc_old, double gl_old, double &gc_new, double &gl_new, int slot) -> double {
+        const double *const sLinK = sLinW + slot * LIN_SLOT;
         double lxv = 0.0;
         gc_new = gc_old;
         gl_new = gl_old;
@@ -617,7 +638,7 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
             // that the scheduler interleaves the three independent mat-vec chains and the two projection sequences -- a lone
             // wavefront issues a dependent FP64 instruction every ~7 cycles, an independent one every ~5.
             const double svc = val + gc_old, s0 = val + gl_old;
-            const double a_k = ILIN ? sLinW[lane] : sLin[r], b_k = ILIN ? sLinW[64 + lane] : sLin[W + r], in_k = ILIN ? sLinW[2 * 64 + lane] : sLin[2 * W + r];
+            const double a_k = ILIN ? sLinK[lane] : sLin[r], b_k = ILIN ? sLinK[64 + lane] : sLin[W + r], in_k = ILIN ? sLinK[2 * 64 + lane] : sLin[2 * W + r];
             const double a2 = group_matvec<W, KT>(cn, svc * svc, 0.0);
             const double t = group_matvec<W, KT>(ct_, svc, 0.0);
             const double dot = group_matvec<W, KT>(ty, a_k * s0, 0.0);
@@ -650,9 +671,9 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
             double sv = s0;
 #pragma unroll 1
             for (int k = 0; k < nl; ++k) {  // (uniform trip count)
-                const double a_k = ILIN ? sLinW[(3 * k + 0) * 64 + lane] : sLin[(3 * k + 0) * W + r];
-                const double b_k = ILIN ? sLinW[(3 * k + 1) * 64 + lane] : sLin[(3 * k + 1) * W + r];
-                const double in_k = ILIN ? sLinW[(3 * k + 2) * 64 + lane] : sLin[(3 * k + 2) * W + r];
+                const double a_k = ILIN ? sLinK[(3 * k + 0) * 64 + lane] : sLin[(3 * k + 0) * W + r];
+                const double b_k = ILIN ? sLinK[(3 * k + 1) * 64 + lane] : sLin[(3 * k + 1) * W + r];
+                const double in_k = ILIN ? sLinK[(3 * k + 2) * 64 + lane] : sLin[(3 * k + 2) * W + r];
                 const double dot = group_matvec<W, KT>(ty, a_k * sv, 0.0);
                 sv = halfspace_project_element(sv, dot, a_k, b_k, in_k);
             }
@@ -1052,7 +1073,7 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
         }
         if constexpr (FAM) {  // knot 0 of the state rows (its lx only reaches p_0, which nothing reads; the duals persist)
             double gcn, gln;
-            (void)families(x0v, GC0, GL0, gcn, gln);
+            (void)families(x0v, GC0, GL0, gcn, gln, 0);
             if (is_x) {
                 GC0 = gcn;
                 GL0 = gln;
@@ -1187,7 +1208,7 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
             }
             if constexpr (FAM) {  // xcur: x_{q+1} on state lanes, u_q on input lanes -- this slot's element
                 double gcn, gln;
-                const double l = families(xcur, GCr[q], GLr[q], gcn, gln);
+                const double l = families(xcur, GCr[q], GLr[q], gcn, gln, q + 1);
                 if (row_ok) {
                     GCr[q] = gcn;
                     GLr[q] = gln;
@@ -1798,10 +1819,14 @@ TINY_KERNEL_NAME(const tinympc::SolveParams p) {
 #ifndef TINY_JIT_ICONE
 #define TINY_JIT_ICONE 0
 #endif
+#ifndef TINY_JIT_IKNOT
+#define TINY_JIT_IKNOT 0
+#endif
     constexpr int ILJ = TINY_JIT_ILIN;  // per-instance linear rows: the mode's row count (with -DTINY_JIT_FAM=1 -DTINY_JIT_IGOAL=1); 0: off
-    constexpr int VLJ = tinympc::d_vl(TINY_JIT_NU, TINY_JIT_N, CTJ, WPGJ, 4 * TINY_JIT_WPS, FAMJ, ADJ, IMJ, ILJ);
+    constexpr int KNJ = TINY_JIT_IKNOT != 0 ? TINY_JIT_N : 0;  // ... in the per-knot form (-DTINY_JIT_IKNOT=1): the slots a wavefront stages
+    constexpr int VLJ = tinympc::d_vl(TINY_JIT_NU, TINY_JIT_N, CTJ, WPGJ, 4 * TINY_JIT_WPS, FAMJ, ADJ, IMJ, ILJ, KNJ);
     static_assert(VLJ >= 0, "shape does not fit the layout-D plan");
-    __shared__ __attribute__((aligned(16))) double smem_jit[tinympc::d_lds_bytes(TINY_JIT_NU, TINY_JIT_N, CTJ, WPGJ, VLJ, FAMJ, ADJ, IMJ, ILJ) / sizeof(double)];
+    __shared__ __attribute__((aligned(16))) double smem_jit[tinympc::d_lds_bytes(TINY_JIT_NU, TINY_JIT_N, CTJ, WPGJ, VLJ, FAMJ, ADJ, IMJ, ILJ, KNJ) / sizeof(double)];
 #if TINY_REFILL
 #ifndef TINY_JIT_REFILL
 #define TINY_JIT_REFILL 0
@@ -1812,7 +1837,7 @@ TINY_KERNEL_NAME(const tinympc::SolveParams p) {
 #define TINY_JIT_IGOAL 0
 #endif
     tinympc::k_admm_solve_d_body<TINY_JIT_NX, TINY_JIT_NU, TINY_JIT_N, CTJ, WPGJ, VLJ, FAMJ, ADJ, TINY_JIT_WPS == 2, false, false,
-                                 TINY_JIT_IGOAL != 0 || IMJ, IMJ, ILJ, TINY_JIT_ICONE != 0>(p, smem_jit);
+                                 TINY_JIT_IGOAL != 0 || IMJ, IMJ, ILJ, TINY_JIT_ICONE != 0, TINY_JIT_IKNOT != 0>(p, smem_jit);
 #endif
 }
 namespace tinympc {

@@ -468,7 +468,11 @@ class TinyMPC:
         belong to the batch, the values to the knot and the instance; b = +inf switches one row off at one knot. The first call names the
         whole batch, later calls may replace a sub-range; set_linear_constraints() returns every instance to shared rows, a whole-batch
         set_linear_constraints_batch() to rows constant over the horizon. Enables the linear family of every non-empty side and keeps the
-        ADMM state: re-send the shifted rows between two mpc_step() ticks. Batched solvers only; runs on layout A."""
+        ADMM state: re-send the shifted rows between two mpc_step() ticks. Batched solvers only. Runs on layout A -- or, after prepare()
+        (before or after this call), on the per-knot variant of layout D's per-instance linear-row form: nx+nu <= 16, references and
+        bounds constant over the horizon, cones that share no row, and a horizon and row count whose rows of all knots fit a wavefront's
+        share of the LDS (one row per side up to N = 22, two up to N = 12, three up to N = 8); launch_info()["layout"] and jit_info()
+        (" per-knot-linear", with "refused(...)" in front after a refused plan) say which."""
         self._check_setup()
         sides = []
         for A, b, cols, knots, name in ((Alin_x, blin_x, self.nx, self.N, "x"), (Alin_u, blin_u, self.nu, self.N - 1, "u")):
@@ -813,8 +817,8 @@ class TinyMPC:
         first solve that needs it (seconds the first time a shape is seen). It also says that run-time specialisation is welcome on this
         handle: a batch with per-instance models (set_model_batch, before or after this call) then runs on layout D's per-instance
         model form -- nx+nu <= 16, references and bounds constant over the horizon, a horizon that form holds -- instead of layout A,
-        and a batch with per-instance linear rows (set_linear_constraints_batch, before or after this call) on layout D's per-instance
-        linear-row form under the same conditions (launch_info()["layout"] and jit_info() say which). Per-instance cone slopes
+        and a batch with per-instance linear rows (set_linear_constraints_batch or set_linear_constraints_knots_batch, before or after
+        this call) on layout D's per-instance linear-row form under the same conditions (launch_info()["layout"] and jit_info() say which). Per-instance cone slopes
         (set_cone_slopes_batch) are the other half of that mode and run on the same form, whose cone slope is always the instance's;
         cones that share rows stay on layout A."""
         self._check_setup()

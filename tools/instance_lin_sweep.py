@@ -31,7 +31,16 @@ Rows per knot (--knots [--parent-lib PATH] [--alt-lib PATH]): the same workload 
   alt-same, alt-vary   the two knot legs on another build of this tree at --alt-lib (a variant of the kernel to compare against)
 and the wall time of tinympc_set_linear_constraints_knots_batch and of its _device form for the whole batch. No ratio is a condition;
 medians and spreads are reported, and the knot legs' distance to const-A.
-    python tools/instance_lin_sweep.py --knots --parent-lib /path/to/parent/libtinympc_hip.so"""
+    python tools/instance_lin_sweep.py --knots --parent-lib /path/to/parent/libtinympc_hip.so
+
+Rows per knot on layout D (--knots --d --parent-lib PATH): the --knots workload, rows that differ per knot and instance, on a handle
+that called prepare(), with
+  parent-A    the handle on the library of the parent commit at PATH: layout A's k_admm_solve_ifamk, where the mode ran before layout D
+              had a form for it -- the yardstick
+  knots-D     the same handle on this tree's library: the per-knot variant of layout D's per-instance linear-row form
+  const-D     rows constant over the horizon on layout D's per-instance linear-row form -- the floor; context, not a condition
+Every measurement is a fresh process; the legs alternate, `--rounds` times each. The bar: knots-D lies below parent-A in EVERY round.
+    python tools/instance_lin_sweep.py --knots --d --parent-lib /path/to/parent/libtinympc_hip.so"""
 import argparse
 import ctypes as C
 import json
@@ -48,6 +57,7 @@ sys.path.insert(0, ROOT)
 LEGS = ["shared-A", "per-inst"]
 D_LEGS = ["parent-A", "inst-D", "shared-D", "parent-A-4", "inst-D-4"]
 K_LEGS = ["const-A", "knots-same", "knots-vary"]
+KD_LEGS = ["parent-A", "knots-D", "const-D"]
 
 
 def rows(prob, batch, seed=7, n=1):
@@ -255,6 +265,65 @@ def sweep_k(a):
                  float(np.median(rest)), min(rest), max(rest)))
 
 
+def child_kd(pkg, a):
+    """One process of the --knots --d sweep: one leg's kernel time on whatever library this process loaded. One line."""
+    prob = pkg.problems.quadrotor(a.N)
+    os.environ.pop("TINYMPC_LAYOUT", None)
+    s = pkg.TinyMPC()
+    s.setup(prob.A, prob.B, prob.Q, prob.R, prob.N, batch=a.batch, rho=prob.rho, abs_pri_tol=0.0, abs_dua_tol=0.0, max_iter=a.iters)
+    s.set_bound_constraints(prob.x_min, prob.x_max, prob.u_min, prob.u_max)
+    if a.child == "const-D":
+        s.set_linear_constraints_batch(*(np.repeat(m[..., None], a.batch, axis=-1) for m in rows(prob, a.batch)))
+    else:
+        s.set_linear_constraints_knots_batch(*knot_rows(prob, a.batch, True))
+    s.prepare()
+    s.set_x0_batch(pkg.problems.quadrotor_batch_x0(a.batch))
+    s.solve_timed()  # warm-up: first launch, table builds
+    out = dict(leg=a.child, kernel_ms=float(np.median([s.solve_timed() for _ in range(a.reps)])),
+               kernel="%s %s" % (s.launch_info()["layout"], s.jit_info()), lds_bytes=s.launch_info()["lds_bytes"],
+               workgroups=s.launch_info()["workgroups"])
+    s.reset()
+    print("LIN-CHILD " + json.dumps(out), flush=True)
+
+
+def sweep_kd(a):
+    """Starts the children of the --knots --d sweep (it never opens the GPU itself) and prints the table."""
+    if not a.parent_lib or not os.path.exists(a.parent_lib):
+        raise SystemExit("--knots --d needs --parent-lib: libtinympc_hip.so built from the parent commit")
+    recs = {leg: [] for leg in KD_LEGS}
+    for rnd in range(a.rounds):
+        for leg in KD_LEGS if rnd % 2 == 0 else KD_LEGS[::-1]:
+            env = dict(os.environ)
+            env.pop("TINYMPC_LAYOUT", None)
+            env.pop("TINYMPC_HIP_LIBRARY", None)
+            if leg.startswith("parent"):
+                env["TINYMPC_HIP_LIBRARY"] = os.path.abspath(a.parent_lib)
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--knots", "--d", "--child", leg, "--batch", str(a.batch), "--N", str(a.N),
+                                "--iters", str(a.iters), "--reps", str(a.reps)], env=env, capture_output=True, text=True, timeout=300)
+            line = [l for l in r.stdout.splitlines() if l.startswith("LIN-CHILD ")]
+            if r.returncode != 0 or not line:
+                raise SystemExit("round %d (%s) failed with %d:\n%s\n%s" % (rnd, leg, r.returncode, r.stdout[-2000:], r.stderr[-2000:]))
+            recs[leg].append(json.loads(line[0][len("LIN-CHILD "):]))
+            print("# round %d %-10s %.4f ms" % (rnd, leg, recs[leg][-1]["kernel_ms"]), flush=True)
+    print("per-knot linear rows on layout D: %d quadrotors N=%d x %d forced iterations, 1 state row + 1 input row that differ per knot and "
+          "instance (const-D: constant over the horizon), every handle after prepare(); kernel ms (median of %d launches per round, %d rounds, a "
+          "fresh process each, legs alternating)" % (a.batch, a.N, a.iters, a.reps, a.rounds))
+    ms = {leg: [r["kernel_ms"] for r in recs[leg]] for leg in KD_LEGS}
+    for leg in KD_LEGS:
+        print("%-10s | %s | median %.4f | spread %.4f - %.4f | %d workgroups, %d bytes of LDS each | %s"
+              % (leg, " ".join("%.4f" % v for v in ms[leg]), float(np.median(ms[leg])), min(ms[leg]), max(ms[leg]), recs[leg][0]["workgroups"],
+                 recs[leg][0]["lds_bytes"], recs[leg][0]["kernel"]))
+    on_d = recs["knots-D"][0]["kernel"].startswith("D ")
+    below = all(n < o for n, o in zip(ms["knots-D"], ms["parent-A"]))
+    print("knots-D on layout D: %s; below parent-A in every round: %s (largest %.4f against smallest %.4f, parent-A's spread %.4f; ratio of medians %.3f)"
+          % ("yes" if on_d else "NO", "yes" if below else "NO", max(ms["knots-D"]), min(ms["parent-A"]), max(ms["parent-A"]) - min(ms["parent-A"]),
+             float(np.median(ms["knots-D"])) / float(np.median(ms["parent-A"]))))
+    med, floor = float(np.median(ms["knots-D"])), float(np.median(ms["const-D"]))
+    waves = (a.batch + 3) // 4  # (16 lanes per instance: four instances per wavefront)
+    print("distance to the floor: knots-D median %.4f against const-D median %.4f (ratio %.3f, +%.4f ms); the staging reads %d wavefronts x "
+          "%d slots x 3 vectors x 512 B = %.1f MB per launch" % (med, floor, med / floor, med - floor, waves, a.N, waves * a.N * 3 * 512 / 1e6))
+
+
 def device_copy(pkg, arrays):
     """Device copies of `arrays` through the HIP runtime the library itself uses, or None where that runtime cannot be found."""
     pkg.load_library()
@@ -363,9 +432,9 @@ def main():
     ap.add_argument("--alt-lib", default="")
     a = ap.parse_args()
     if not a.child:
-        return sweep_k(a) if a.knots else sweep_d(a) if a.d else sweep(a)
+        return sweep_kd(a) if a.knots and a.d else sweep_k(a) if a.knots else sweep_d(a) if a.d else sweep(a)
     import __graft_entry__ as ge
-    (child_k if a.knots else child_d if a.d else child)(ge.load_package(), a)
+    (child_kd if a.knots and a.d else child_k if a.knots else child_d if a.d else child)(ge.load_package(), a)
 
 
 if __name__ == "__main__":
