@@ -209,7 +209,9 @@ int tinympc_setup_batch(tinympc_solver **out, const double *A, const double *B, 
                         const double *Q, const double *R, double rho, int nx, int nu, int N,
                         int batch, int device, int verbose);
 
-/* x0s is nx x count (column b = instance first+b), host memory. */
+/* x0s is nx x count (column b = instance first+b), host memory. Single-instance handles: the same as tinympc_set_x0 for launched
+ * AND resident solves (both forms also bring the pinned copy up to date that a resident solve hands to its session), except that
+ * they need the device and so end an open session. */
 int tinympc_set_x0_batch(tinympc_solver *s, const double *x0s, int first, int count);
 /* Same, from device memory on the handle's GPU (e.g. a torch tensor's data_ptr). Contract: whatever
  * PRODUCED d_x0s on another stream must have completed before the call (the copy runs on the handle's own

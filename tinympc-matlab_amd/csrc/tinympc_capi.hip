@@ -1008,6 +1008,13 @@ int tinympc_set_x0_batch(tinympc_solver *s, const double *x0s, int first, int co
     if (first < 0 || count < 0 || first + count > s->batch)
         return fail(TINYMPC_ERR_INVALID_INPUT, "instance range [%d, %d) outside batch of %d", first, first + count, s->batch);
     if ((rc = bind_device(s))) return rc;
+    if (s->host_path() && count == 1) {
+        // A single-instance handle keeps x0 twice: dx0 for launches, the pinned h_x0 for resident solves (tinympc_solve hands it to the
+        // session) -- this verb brings BOTH up to date, as tinympc_set_x0 does through the kernel's mirror. (A launch of
+        // tinympc_solve_async may still be reading the pinned buffer: wait for it first, as tinympc_set_x0 does.)
+        if (s->host_sol_state == 1 && (rc = tinympc_synchronize(s))) return rc;
+        std::memcpy(s->h_x0, x0s, sizeof(double) * s->nx);
+    }
     s->x0_on_host = false;
     return upload(s, s->dx0 + (size_t)first * s->nx, x0s, (size_t)count * s->nx);
 }
@@ -1021,6 +1028,8 @@ int tinympc_set_x0_batch_device(tinympc_solver *s, const double *d_x0s, int firs
     if ((rc = bind_device(s))) return rc;
     s->x0_on_host = false;
     HIP_TRY(hipMemcpyAsync(s->dx0 + (size_t)first * s->nx, d_x0s, sizeof(double) * count * s->nx, hipMemcpyDeviceToDevice, s->stream));
+    // (a single-instance handle: the pinned copy that resident solves read follows on the same stream, behind any launch still reading it)
+    if (s->host_path() && count == 1) HIP_TRY(hipMemcpyAsync(s->h_x0, s->dx0, sizeof(double) * s->nx, hipMemcpyDeviceToHost, s->stream));
     // The copy runs on the handle's own (non-blocking) stream: wait for it here, so that the caller may free or reuse
     // d_x0s as soon as the call returns -- the same ownership rule as every host-pointer verb. (Work that PRODUCES
     // d_x0s on another stream must have completed before the call; see the header.)

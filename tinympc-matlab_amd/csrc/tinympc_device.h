@@ -41,6 +41,25 @@ __host__ __device__ inline size_t tables_doubles(int W, int N) { return 3 * tabl
 // also cost every tick the L2's other dirty lines and, as an acquire, its cached operators and tables.
 #if defined(__HIPCC__) || defined(__HIPCC_RTC__)
 __device__ __forceinline__ void host_store(double *p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
+
+// The completion stamp behind such stores is raised in three steps, in this order:
+//   1. host_stores_retired(): EVERY thread waits until its own host_store()s have been acknowledged (s_waitcnt vmcnt(0), nothing else: a
+//      write-through store is counted until the memory system has taken it). The write-out's stores come from every wavefront and go
+//      to different L2 channels; without the wait they may still be in flight when the stamp goes out, and a host that polls the stamp
+//      reads stale words behind it. A workgroup-scope release fence does NOT do this: outside tgsplit mode it emits no wait on vmcnt.
+//   2. __syncthreads(): every wavefront has passed step 1.
+//   3. host_stamp_store() by one thread: a relaxed system-scope store, written through like the others.
+// No agent- or system-scope fence anywhere in it: that would write the L2 back and invalidate it (buffer_wbl2 / buffer_inv), which is
+// what the write-through stores are there to avoid. Each helper leaves a fixed comment in the assembly; tools/stamp_lint.py finds the
+// stamp by it and checks the order of the generated code on every path (the build and tests/test_stamp_order.py run it).
+__device__ __forceinline__ void host_stores_retired() {
+    asm volatile("; tinympc host stores retired" ::: "memory");
+    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0); expcnt and lgkmcnt left alone
+}
+__device__ __forceinline__ void host_stamp_store(double *p, double v) {
+    asm volatile("; tinympc completion stamp" ::: "memory");
+    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
 #endif
 
 struct PrecomputeParams {

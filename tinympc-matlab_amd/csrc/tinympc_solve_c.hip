@@ -833,15 +833,18 @@ __global__ void __launch_bounds__(CTHREADS) k_admm_solve_c(const SolveParams p) 
 
     if (p.host_sol && (session || p.host_seq != 0.0)) {  // (uniform) everything above is in pinned memory: raise the flag
         // Everything the host reads after the stamp was stored with host_store() (system scope: written through, nothing of it stays dirty in
-        // the L2): once every thread's stores have been handed over (s_waitcnt vmcnt(0) -- a workgroup-scope release) the stamp may follow
-        // them. Rounds 2-4 had plain stores and a system-scope fence here (__threadfence_system + a release store), which wrote back the
-        // L2's dirty lines -- the solution just stored to HBM included -- and INVALIDATED the caches, twice per tick: the next tick then
-        // fetched its operators and tables from HBM again.
+        // the L2): once every thread's own stores have been acknowledged (host_stores_retired: s_waitcnt vmcnt(0)) and every wavefront
+        // has got there (the barrier), the stamp may follow them. The workgroup-scope release orders the compiler and the LDS only -- it
+        // emits NO wait on vmcnt here, and through round 5 it stood alone: stores of other wavefronts, bound for other L2 channels,
+        // could still be in flight behind the stamp. Rounds 2-4 had plain stores and a system-scope fence here (__threadfence_system +
+        // a release store), which wrote back the L2's dirty lines -- the solution just stored to HBM included -- and INVALIDATED the
+        // caches, twice per tick: the next tick then fetched its operators and tables from HBM again.
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        host_stores_retired();
         __syncthreads();
         // (a system-scope atomic store: written through at once -- a plain store might be combined or delayed)
         if (tid == 0)
-            __hip_atomic_store(p.host_sol + (size_t)N * nx + (size_t)(N - 1) * nu + 6, session ? expect : p.host_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            host_stamp_store(p.host_sol + (size_t)N * nx + (size_t)(N - 1) * nu + 6, session ? expect : p.host_seq);
     }
     if constexpr (!SESSION) break;
     // The next tick warm-starts from the registers. A converged solve returns before v <- vnew (admm.cpp:181-197): its

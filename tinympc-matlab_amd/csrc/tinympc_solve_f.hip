@@ -777,11 +777,15 @@ __device__ __forceinline__ void k_admm_solve_f_body(const SolveParams &p, double
 #endif
     if (p.host_sol && (SESSION || p.host_seq != 0.0)) {  // (uniform) everything above is in pinned memory: raise the completion stamp
         // Everything the host reads after the stamp was stored with host_store() (system scope: written through, nothing of it stays dirty in
-        // the L2): once every thread's stores have been handed over (s_waitcnt vmcnt(0) -- a workgroup-scope release) the stamp may follow
-        // them. Rounds 2-4 had plain stores and a system-scope fence here (__threadfence_system + a release store), which wrote back the
-        // L2's dirty lines -- the solution just stored to HBM included -- and INVALIDATED the caches, twice per tick: the next tick then
-        // fetched its operators and tables from HBM again.
+        // the L2): once every thread's own stores have been acknowledged (host_stores_retired: s_waitcnt vmcnt(0)) and every wavefront
+        // has got there (the barrier), the stamp may follow them. The workgroup-scope release orders the compiler and the LDS only -- it
+        // emits NO wait on vmcnt here, and through round 5 it stood alone: stores of other wavefronts, bound for other L2 channels,
+        // could still be in flight behind the stamp. (The early answer above needs none of this: its lines check themselves.) Rounds
+        // 2-4 had plain stores and a system-scope fence here (__threadfence_system + a release store), which wrote back the L2's dirty
+        // lines -- the solution just stored to HBM included -- and INVALIDATED the caches, twice per tick: the next tick then fetched its
+        // operators and tables from HBM again.
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        host_stores_retired();
         __syncthreads();
         // (a system-scope atomic store: written through at once -- a plain store might be combined or delayed)
         if (threadIdx.x == 0) {
@@ -795,7 +799,7 @@ __device__ __forceinline__ void k_admm_solve_f_body(const SolveParams &p, double
                 host_store(hs + 7, (double)packed);
                 t_prev_out = t_out;
             }
-            __hip_atomic_store(hs + 6, SESSION ? expect : p.host_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            host_stamp_store(hs + 6, SESSION ? expect : p.host_seq);
         }
     }
     if constexpr (!SESSION) break;

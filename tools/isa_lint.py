@@ -24,12 +24,21 @@ def _regs(tok: str):
     return set(range(int(m.group(1)), int(m.group(2)) + 1))
 
 
-def lint(asm_text: str):
-    """Returns (number of DPP FMAs checked, list of violations)."""
-    # pass 1: the instruction stream as items -- ("label", name) | ("instr", mnemonic, dest_regs, wait_states, branch_target, line, text)
+NO_FALL_THROUGH = ("s_branch", "s_endpgm", "s_setpc_b64")  # nothing runs on into the label below one of these
+
+
+def parse(asm_text: str, marks=()):
+    """The instruction stream of a .s file as items -- ("label", name) | ("instr", mnemonic, dest_regs, wait_states, branch_target, line, text) --
+    and, per label, the indices of the branches that jump to it. Comments and directives are dropped, except that a comment line which
+    contains one of `marks` (fixed comments that the sources leave through an empty asm statement) becomes an instruction of no wait
+    states whose mnemonic is that mark. Shared by the lints of this directory (tools/stamp_lint.py)."""
     items = []
     for ln, raw in enumerate(asm_text.splitlines(), 1):
         line = raw.split(";")[0].strip() if not raw.strip().startswith(";;") else ""
+        if not line and marks and raw.lstrip().startswith(";"):
+            for mark in marks:
+                if mark in raw:
+                    items.append(("instr", mark, set(), 0, None, ln, raw.strip()))
         if not line or line.startswith(".") and not line.endswith(":"):
             continue
         if line.endswith(":"):
@@ -48,6 +57,12 @@ def lint(asm_text: str):
     for i, it in enumerate(items):
         if it[0] == "instr" and it[4]:
             sites.setdefault(it[4], []).append(i)
+    return items, sites
+
+
+def lint(asm_text: str):
+    """Returns (number of DPP FMAs checked, list of violations)."""
+    items, sites = parse(asm_text)
 
     def walk(i, waited, src, depth):
         """Walks back from item i (inclusive) along every path that can reach the DPP instruction: None if `src` is not written by a
@@ -65,7 +80,7 @@ def lint(asm_text: str):
                 if not sites.get(it[1]) and i == 0:
                     return "branch target inside the hazard window (nothing known about what runs before it)"
                 i -= 1
-                if i >= 0 and items[i][0] == "instr" and items[i][1] in ("s_branch", "s_endpgm", "s_setpc_b64"):
+                if i >= 0 and items[i][0] == "instr" and items[i][1] in NO_FALL_THROUGH:
                     return None  # nothing falls through into the label
                 continue
             _, m2, dest, ws, _, _, _ = it
