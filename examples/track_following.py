@@ -1,9 +1,21 @@
 """Reference tracks: 512 quadrotors, each following its own figure-eight with its own phase. Every instance's whole trajectory (T = 300
 knots) is uploaded ONCE and kept on the device; a control tick is one mpc_step -- x0 up, first controls down -- and the library moves
 every instance one knot along its track after the tick's solve (set_ref_auto_advance). Some instances are sent back to the start of
-their track mid-run (set_ref_step_batch on a sub-range: an RL environment that resets), the others carry on."""
+their track mid-run (set_ref_step_batch on a sub-range: an RL environment that resets), the others carry on.
+
+    python track_following.py [--prepare]
+--prepare: the handle is set up on the throughput layout (TINYMPC_LAYOUT=D, unless the environment names another) and calls
+prepare(), which welcomes run-time specialised kernels: the tracks then run on layout D's per-instance trajectory form (the wavefront's
+own reference rows in its LDS region) instead of layout A. The same loop, the same results to rounding; the kernel line says which ran."""
+import os
+import sys
+
 import numpy as np
 from _common import TinyMPC, problems
+
+prepare = "--prepare" in sys.argv[1:]
+if prepare:
+    os.environ.setdefault("TINYMPC_LAYOUT", "D")
 
 prob = problems.quadrotor(20)
 batch, T, ticks = 512, 300, 120
@@ -26,6 +38,8 @@ solver.setup(prob.A, prob.B, prob.Q, prob.R, N, batch=batch, rho=prob.rho, max_i
 solver.set_bound_constraints(prob.x_min, prob.x_max, prob.u_min, prob.u_max)
 solver.set_x_ref_track_batch(tracks)  # the one upload: nx x T x batch
 solver.set_ref_auto_advance(1)        # every mpc_step moves every instance one knot on, after its solve
+if prepare:
+    solver.prepare()  # (behind the track verbs: the kernel for tracks is decided, and specialised, here and not in the first tick)
 print("kernel:", solver.launch_info()["layout"], "|", solver.jit_info())
 
 x = np.asfortranarray(tracks[:, 0, :])  # every quadrotor starts on its curve

@@ -226,8 +226,14 @@ int tinympc_set_x0_batch_device(tinympc_solver *s, const double *d_x0s, int firs
  * for a half (x or u) turns per-instance mode on for that half; instances outside the range keep the handle's shared
  * reference of that moment. A later tinympc_set_x_ref / tinympc_set_u_ref returns that half to shared mode for every
  * instance. reset_workspace, update_settings, set_bound_constraints, the solve verbs and mpc_step_batch keep them.
- * Goals run on layout D where the handle runs layout D (compiled in or run-time specialised), everything else on layout A;
- * with the cone / linear families, adaptive rho or nx+nu > 64 a solve returns TINYMPC_ERR_UNSUPPORTED (never a solve with
+ * Goals run on layout D where the handle runs layout D (compiled in or run-time specialised). Trajectories (either half, cols = N /
+ * N-1) run on layout A -- or, on a handle that called tinympc_prepare (before or after these verbs), on layout D's per-instance
+ * trajectory form: where the handle runs layout D with nx+nu <= 16, bounds are constant over the horizon (shared or per instance), the
+ * model and rho are the shared ones, and the horizon's N+2 reference rows fit a wavefront's share of LDS beside its other state (the
+ * plan's arithmetic decides; for the quadrotor, nu = 4, that is a horizon of about 60 -- N = 50 is compiled in, other shapes are
+ * specialised at run time). Whatever misses a condition stays on layout A; tinympc_get_layout and tinympc_get_jit_info
+ * (" per-instance-trajectories", or "refused(...)" with the reason) say which ran.
+ * With the cone / linear families, adaptive rho or nx+nu > 64 a solve returns TINYMPC_ERR_UNSUPPORTED (never a solve with
  * the shared reference). The _device forms refuse memory that is not device memory of the handle's GPU.
  * Single-instance handles: the same as tinympc_set_x_ref / tinympc_set_u_ref. The input has been copied when the call
  * returns. */
@@ -248,7 +254,9 @@ int tinympc_set_u_ref_batch_device(tinympc_solver *s, const double *d_Urefs, int
  * Track mode is per half. The first track call of a half must name the whole batch (first = 0, count = batch); later calls may
  * replace a sub-range with the same T, a whole-batch call may change T; replacing a track does not touch the steps. A half in track
  * mode IS a half with per-instance trajectories: it turns per-instance references on for that half, runs on layout A (even with
- * T = 1: never layout D's goal form), " reference-track" is appended to tinympc_get_jit_info, and every refusal of per-instance
+ * T = 1: never layout D's goal form) -- or, after tinympc_prepare and under tinympc_set_x_ref_batch's conditions, on layout D's
+ * per-instance trajectory form (tinympc_mpc_step_batch with auto-advance included: the rows are rebuilt per tick as on layout A) --,
+ * " reference-track" is appended to tinympc_get_jit_info, and every refusal of per-instance
  * references applies unchanged (the cone / linear families, adaptive rho, nx+nu > 64: a solve returns TINYMPC_ERR_UNSUPPORTED;
  * tinympc_session_begin likewise). tinympc_set_x_ref / _u_ref returns the half to shared references; a whole-batch
  * tinympc_set_x_ref_batch / _u_ref_batch returns it to plain per-instance references, while one on a sub-range returns
@@ -593,7 +601,11 @@ int tinympc_get_jit_info(tinympc_solver *s, char *buf, int len);
  * F: 5-25 % fewer microseconds per iteration than the generic latency kernel, resident session included) instead of staying on the
  * generic one, which needs no compiler; and a batch with per-instance models (tinympc_set_model_batch, in either order) runs on layout
  * D's per-instance model form where one exists instead of layout A, and a batch with per-instance linear rows
- * (tinympc_set_linear_constraints_batch, in either order) on layout D's per-instance linear-row form likewise. No reference
+ * (tinympc_set_linear_constraints_batch, in either order) on layout D's per-instance linear-row form likewise; and a batch with
+ * per-instance reference trajectories or tracks (tinympc_set_x_ref_batch / _u_ref_batch with cols = N / N-1, the track verbs, in either
+ * order) on layout D's per-instance trajectory form -- nx+nu <= 16, bounds constant over the horizon, no per-instance models or rho, no
+ * cone / linear families, no adaptive rho, a horizon whose reference rows fit a wavefront's LDS share; otherwise layout A as without
+ * this call. No reference
  * counterpart (the reference has one code path). */
 int tinympc_prepare(tinympc_solver *s);
 

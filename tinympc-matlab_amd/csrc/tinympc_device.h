@@ -269,6 +269,8 @@ struct SolveParams {
     // reference-dependent table rows of every instance, in the solve kernel's lane order (k_build_inst_tables) -- iref_lr
     // [groups][N+2][64] (row k+1 = knot k, the same padding rows as the shared tables), iref_pn [groups][64] = [instance][W].
     // Layout D's goal form (k_admm_solve_d_gbnd, -DTINY_JIT_IGOAL=1): iref_lr is knot 0's linref, [instance][W]. NULL otherwise.
+    // Layout D's trajectory form (-DTINY_JIT_ITRAJ=1): iref_lr is layout A's store itself, [groups][N+2][64] without the pad rows in
+    // front (a wavefront stages its group's block into its own LDS region); iref_pn and ibnd are the goal form's.
     union { const double *ftab; const double *iref_pn; };
     // Per-instance clamp rows (ibnd, in the mail slot above), built by k_build_inst_tables with k_build_tables' expressions -- from every
     // instance's own bounds (tinympc_set_bound_constraints_batch) or from the shared ones. Layout A's InstBounds variant (per-instance
@@ -507,7 +509,7 @@ bool solve_e_supported(int nx, int nu, int N, bool const_tables, bool families, 
 hipError_t launch_solve_e(const SolveParams &p, const FamilyStructure &fs, hipStream_t stream);
 void solve_e_describe(int nx, int nu, int N, bool const_tables, bool families, const FamilyStructure &fs, char *buf, size_t len);
 void solve_jit_describe(int W, int nx, int nu, int N, bool const_tables, bool families, bool adaptive, char *buf, size_t len, bool goal = false,
-                        bool models = false, int ilin = 0, bool icone = false, int knots = 0);
+                        bool models = false, int ilin = 0, bool icone = false, int knots = 0, bool traj = false);
 // Layout F (tinympc_solve_f.hip, run-time specialised only): the latency kernel with compile-time shape and structure
 bool solve_f_plan(int nx, int nu, int N, bool const_tables, bool families, const FamilyStructure &fs, int *chunk_len, int *chunks, int *wpg, size_t *lds_bytes);
 bool solve_f_supported(int nx, int nu, int N, bool const_tables, bool families, const FamilyStructure &fs);  // plans AND compiles
@@ -657,15 +659,18 @@ hipError_t launch_solve_m(const SolveParams &p, hipStream_t stream);
 // rows, SolveParams::ilin, staged per wavefront; 16 lanes, constant tables; 0: off). With TINYMPC_JIT=0 only a compiled-in one.
 // icone (with ilin): ... and every instance's own cone slope (-DTINY_JIT_ICONE=1: the per-instance families form with the slope half on)
 // knots (with ilin): ... the rows of every knot (-DTINY_JIT_IKNOT=1; knots = N, the slots per group of SolveParams::ilin, staged whole; 0: off)
+// traj (with goal): the per-instance trajectory form (-DTINY_JIT_ITRAJ=1: the goal form reading every instance's own linref rows,
+// SolveParams::iref_lr = layout A's store [groups][N + 2][64], staged per wavefront; 16 lanes, box path). With TINYMPC_JIT=0 only a compiled-in one.
 bool solve_jit_supported(int W, int nx, int nu, int N, bool const_tables, bool families = false, bool adaptive = false, bool goal = false,
-                         bool models = false, int ilin = 0, bool icone = false, int knots = 0);
-hipError_t launch_solve_jit(const SolveParams &p, int W, hipStream_t stream, bool models = false, int ilin = 0, bool icone = false, int knots = 0);
+                         bool models = false, int ilin = 0, bool icone = false, int knots = 0, bool traj = false);
+hipError_t launch_solve_jit(const SolveParams &p, int W, hipStream_t stream, bool models = false, int ilin = 0, bool icone = false, int knots = 0,
+                            bool traj = false);
 bool solve_jit_refill_supported(int W, int nx, int nu, int N, bool const_tables);   // (compiles the slot-refill variant on first use)
 int solve_jit_resident_wavefronts(int W, int nx, int nu, int N, bool const_tables);  // wavefronts of the shape's plan the device holds at once
 int solve_jit_workgroups(int W, int nx, int nu, int N, bool const_tables, int groups, bool families = false, bool adaptive = false, bool goal = false,
-                         bool models = false, int ilin = 0, bool icone = false, int knots = 0);
+                         bool models = false, int ilin = 0, bool icone = false, int knots = 0, bool traj = false);
 size_t solve_jit_lds_bytes(int W, int nx, int nu, int N, bool const_tables, bool families = false, bool adaptive = false, bool goal = false,
-                           bool models = false, int ilin = 0, bool icone = false, int knots = 0);  // per workgroup, from the plan  // 8 wavefronts per workgroup, 4 on the long-horizon plan
+                           bool models = false, int ilin = 0, bool icone = false, int knots = 0, bool traj = false);  // per workgroup, from the plan  // 8 wavefronts per workgroup, 4 on the long-horizon plan
 #endif  // !__HIPCC_RTC__
 
 // Doubles of working state per group in layout A (G and V with N+2 rows, D with 64 dummy slots).

@@ -62,6 +62,10 @@ struct InstState {
     // replaced by goals keeps the handle on layout A (nothing looks at the whole batch's data again)
     bool x_const = false, u_const = false, bounds_const = false;
     int d_goal = -1;  // the run-time specialised goal kernel (16 lanes beyond the compiled-in shapes, 32 / 64 lanes): -1 not asked yet, 0 no, 1 yes
+    // layout D's per-instance trajectory form (ITRAJ: 16 lanes, compiled in or run-time specialised; trajectories and tracks of a handle that
+    // called tinympc_prepare, bounds constant over the horizon): -1 not asked yet, 0 no (the horizon's rows do not fit a wavefront's LDS
+    // share, or the specialiser refused: the mode stays on layout A), 1 yes
+    int d_traj = -1;
     // every instance's value, column-major [batch] blocks of nx x N (Xi, xmin, xmax) / nu x (N-1) (Ui, umin, umax)
     double *Xi = nullptr, *Ui = nullptr, *xmin = nullptr, *xmax = nullptr, *umin = nullptr, *umax = nullptr;
     double *lr = nullptr, *pn = nullptr;     // linref rows (inst_lr_doubles), pNref [instance][W]
@@ -396,6 +400,7 @@ struct LaunchPlan {
     bool inst_bounds = false;                // ... per-instance bounds (layout A's InstBounds variant)
     bool inst_models = false;                // ... per-instance models (layout A's InstModels variant; inst_refs and inst_bounds are set with it)
     bool inst_lin = false;                   // ... per-instance linear rows (layout A's InstFamilies variant, or layout D's ILIN form: D_JIT; inst_refs and inst_bounds are set with it)
+    bool inst_traj = false;                  // ... per-instance trajectories / tracks on layout D's ITRAJ form (D_JIT; inst_refs is set with it)
     bool jit = false;                        // a run-time specialisation (tinympc_jit.hip) rather than a compiled-in kernel
     bool host_exchange = false;              // the kernel serves the pinned-host paths (x0 in, solution / completion stamp out)
     int workgroups = 0;

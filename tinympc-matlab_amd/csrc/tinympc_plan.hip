@@ -161,6 +161,19 @@ bool models_want_d(const tinympc_solver *s) {
            !s->st.adaptive_rho;
 }
 
+// Per-instance trajectories and tracks on layout D: opt-in like the models' form (tinympc_prepare -- without it they stay on layout A, which
+// needs no specialisation), where the handle runs layout D, 16 lanes per instance, at least one half of the references is a per-instance
+// trajectory or track (where every half is constant over the horizon the goal form keeps precedence), bounds constant over the horizon
+// (shared or per instance), box path, the shared model and rho. Whether the kernel exists -- the horizon's rows fit a wavefront's LDS
+// share -- is inst.d_traj (resolve_plan).
+bool traj_wants_d(const tinympc_solver *s) {
+    const InstState &in = s->inst;
+    const bool traj = (in.x && !in.x_const) || (in.u && !in.u_const);
+    const bool bounds_const = in.bounds ? in.bounds_const : s->xmin_const && s->xmax_const && s->umin_const && s->umax_const;
+    return traj && bounds_const && !in.models && !in.fam() && s->specialise_asked && s->layout_d && !s->layout_m && s->W == 16 && !s->families_active() &&
+           !s->st.adaptive_rho;
+}
+
 // Per-instance linear rows (tinympc_set_linear_constraints_batch): layout A's InstFamilies variant, or layout D's ILIN form (below). What
 // neither can carry is refused at the launch (lin_refusal), never solved with shared rows.
 bool lin_runs(const tinympc_solver *s) {
@@ -217,8 +230,11 @@ LaunchPlan current_plan(const tinympc_solver *s) {
         // form with every wavefront's four operator blocks in its own LDS region; compiled in or run-time specialised: KernelId::D_JIT)
         const bool goal = s->layout_d && s->iref_goal() && !s->inst.models;
         const bool d_models = models_want_d(s) && s->inst.d_models == 1;
+        // trajectories and tracks: layout A's InstRefs / InstBounds variants, or -- under the same opt-in -- layout D's trajectory form (the
+        // goal form with every wavefront's own linref rows in its LDS region: KernelId::D_JIT)
+        pl.inst_traj = !goal && traj_wants_d(s) && s->inst.d_traj == 1;
         pl.kernel = (goal && !s->d_jit && s->W == 16 && solve_d_supported(s->nx, s->nu, s->N, true)) ? KernelId::D_COMPILED
-                    : ((goal && s->inst.d_goal == 1) || d_models) ? KernelId::D_JIT : KernelId::A;
+                    : ((goal && s->inst.d_goal == 1) || d_models || pl.inst_traj) ? KernelId::D_JIT : KernelId::A;
         pl.inst_refs = true;
         pl.inst_models = s->inst.models;
         pl.inst_bounds = s->inst.bounds || pl.inst_models;  // (the models' variant always runs on per-instance clamp rows)
@@ -243,8 +259,9 @@ LaunchPlan current_plan(const tinympc_solver *s) {
             pl.jit = true;
             const int ilin = pl.inst_lin ? s->ifam_nl() : 0;  // (the ILIN form: the families' kernel whichever sides are enabled)
             pl.workgroups = solve_jit_workgroups(s->W, s->nx, s->nu, s->N, ct, s->groups, fam || ilin, adaptive, pl.inst_refs, pl.inst_models, ilin, ilin && s->inst.cones,
-                                                 ilin ? lin_d_knots(s) : 0);
-            pl.lds_bytes = solve_jit_lds_bytes(s->W, s->nx, s->nu, s->N, ct, fam || ilin, adaptive, pl.inst_refs, pl.inst_models, ilin, ilin && s->inst.cones, ilin ? lin_d_knots(s) : 0);
+                                                 ilin ? lin_d_knots(s) : 0, pl.inst_traj);
+            pl.lds_bytes = solve_jit_lds_bytes(s->W, s->nx, s->nu, s->N, ct, fam || ilin, adaptive, pl.inst_refs, pl.inst_models, ilin, ilin && s->inst.cones, ilin ? lin_d_knots(s) : 0,
+                                               pl.inst_traj);
             break;
         }
         case KernelId::D_COMPILED:
@@ -303,6 +320,10 @@ int resolve_plan(tinympc_solver *s) {
         // ... and the model form's (compiled in for the quadrotor N=50, specialised now otherwise; a refusal leaves the mode on layout A)
         if (s->inst.d_models < 0 && models_want_d(s))
             s->inst.d_models = solve_jit_supported(s->W, s->nx, s->nu, s->N, true, false, false, false, true) ? 1 : 0;
+        // ... and the trajectory form's (compiled in for the quadrotor N=50, specialised now otherwise; a horizon whose rows fit no plan, or
+        // a refusal, leaves trajectories and tracks on layout A)
+        if (s->inst.d_traj < 0 && traj_wants_d(s))
+            s->inst.d_traj = solve_jit_supported(s->W, s->nx, s->nu, s->N, true, false, false, true, false, 0, false, 0, true) ? 1 : 0;
         // ... and the linear-row form's, for the mode's row count (compiled in for the quadrotor N=20 with one row, specialised now
         // otherwise; a refusal leaves the mode on layout A). Another count is another specialisation: asked again -- and so is the other
         // of rows constant over the horizon and rows per knot (compiled in for the same quadrotor with one row).
@@ -528,7 +549,8 @@ int launch(tinympc_solver *s, bool timed) {
     if (pl.inst_lin && s->inst.lin_knots) p.ilin_knots = s->inst.lin_knots;  // (rows per knot: the store's slots per group, in chunk_count's slot)
     if (pl.inst_models) p.rho_inst = s->inst.mrho;  // (the model kernels read rho per instance: the handle's, or what tinympc_set_rho_batch set)
     if (pl.inst_refs) {
-        p.iref_lr = pl.kernel == KernelId::A ? s->inst.lr_rows() : s->inst.lrg;
+        // (layout A and layout D's trajectory form: the rows of every knot; the goal form: knot 0's)
+        p.iref_lr = (pl.kernel == KernelId::A || pl.inst_traj) ? s->inst.lr_rows() : s->inst.lrg;
         p.iref_pn = s->inst.pn;
         if (pl.kernel != KernelId::A) p.ibnd = s->inst.bndg;  // (the goal form: always per lane)
         else if (pl.inst_bounds) p.ibnd = s->inst.bnd;
@@ -554,7 +576,8 @@ int launch(tinympc_solver *s, bool timed) {
             HIP_TRY(launch_solve_m(p, s->stream));
             break;
         case KernelId::D_JIT:  // (box path, families with everything in registers, or adaptive rho per lane)
-            HIP_TRY(launch_solve_jit(p, s->W, s->stream, pl.inst_models, pl.inst_lin ? s->ifam_nl() : 0, pl.inst_lin && s->inst.cones, pl.inst_lin ? lin_d_knots(s) : 0));
+            HIP_TRY(launch_solve_jit(p, s->W, s->stream, pl.inst_models, pl.inst_lin ? s->ifam_nl() : 0, pl.inst_lin && s->inst.cones, pl.inst_lin ? lin_d_knots(s) : 0,
+                                     pl.inst_traj));
             break;
         case KernelId::D_COMPILED:
             if (lean_applies(s, pl) && !p.x0_mirror && !p.u0_host && !p.refill_next)
@@ -651,7 +674,17 @@ static int jit_info_text(tinympc_solver *s, char *buf, int len) {
         const std::string w = std::string(s->inst.refs() ? " per-instance-refs" : "") + (s->inst.bounds ? " per-instance-bounds" : "") +
                               (pl.inst_models ? " per-instance-models" : "");
         const char *words = w.c_str();
-        if (pl.kernel == KernelId::D_JIT) {
+        if (pl.kernel == KernelId::D_JIT && pl.inst_traj) {  // layout D's trajectory form
+            if ((rc = bind_device(s))) return rc;
+            solve_jit_describe(s->W, s->nx, s->nu, s->N, true, false, false, buf, (size_t)len, true, false, 0, false, 0, true);
+            strncat(buf, words, (size_t)len - strlen(buf) - 1);
+            strncat(buf, " per-instance-trajectories", (size_t)len - strlen(buf) - 1);
+        } else if (pl.kernel == KernelId::A && !pl.inst_lin && !pl.inst_models && traj_wants_d(s) && s->inst.d_traj == 0) {  // asked for and refused: layout A, and why
+            if ((rc = bind_device(s))) return rc;
+            solve_jit_describe(s->W, s->nx, s->nu, s->N, true, false, false, buf, (size_t)len, true, false, 0, false, 0, true);
+            strncat(buf, words, (size_t)len - strlen(buf) - 1);
+            strncat(buf, " per-instance-trajectories", (size_t)len - strlen(buf) - 1);
+        } else if (pl.kernel == KernelId::D_JIT) {
             if ((rc = bind_device(s))) return rc;
             const int ilin = pl.inst_lin ? s->ifam_nl() : 0;
             solve_jit_describe(s->W, s->nx, s->nu, s->N, true, ilin != 0, false, buf, (size_t)len, true, pl.inst_models, ilin, ilin && s->inst.cones, ilin ? lin_d_knots(s) : 0);

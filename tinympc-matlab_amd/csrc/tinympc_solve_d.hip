@@ -275,14 +275,16 @@ constexpr int D_IMOD_WAVE_DOUBLES = 4 * D_IMOD_STRIDE;
 // (ilin: the row count of the per-instance linear-row form, 0 otherwise -- 3 ilin vectors of 64 doubles per WAVEFRONT in place of the
 // workgroup's D_FAM_DOUBLES; knots: the slots of its per-knot form, N of them, each 3 ilin vectors -- 0: rows constant over the horizon)
 __host__ __device__ constexpr int d_ilin_wave_doubles(int ilin, int knots) { return 3 * ilin * 64 * (knots > 0 ? knots : 1); }
+// (itraj: the per-instance trajectory form -- the wavefront's own linref rows, table_rows(N) = N + 2 vectors of 64 doubles, SolveParams::iref_lr's block)
+__host__ __device__ constexpr int d_itraj_wave_doubles(bool itraj, int N) { return itraj ? (N + 2) * 64 : 0; }
 __host__ __device__ constexpr int d_vl(int nu, int N, bool ct, int wpg, int cu_waves = 8, bool fam = false, bool adapt = false, bool imod = false, int ilin = 0,
-                                       int knots = 0) {
+                                       int knots = 0, bool itraj = false) {
     const int ns = N - 1;
     const int wg_doubles = D_LDS_PER_CU / 8 * wpg / cu_waves - (imod ? 0 : D_OPS_DOUBLES + D_START_DOUBLES) - (ct ? 0 : d_tab_doubles(N)) - (fam && !ilin ? D_FAM_DOUBLES : 0) - (adapt ? D_ADAPT_DOUBLES : 0);
 #if TINY_TRIM_DSTORE
     const int wave_doubles = wg_doubles / wpg - d_d_doubles(nu, N) - D_DUMP_DOUBLES(nu) - (imod ? D_IMOD_WAVE_DOUBLES : 0);
 #else
-    const int wave_doubles = wg_doubles / wpg - d_d_doubles(nu, N) - (imod ? D_IMOD_WAVE_DOUBLES : 0) - d_ilin_wave_doubles(ilin, knots);
+    const int wave_doubles = wg_doubles / wpg - d_d_doubles(nu, N) - (imod ? D_IMOD_WAVE_DOUBLES : 0) - d_ilin_wave_doubles(ilin, knots) - d_itraj_wave_doubles(itraj, N);
 #endif
     if (wave_doubles < 0) return -1;
     const int vlmax = wave_doubles / 64;
@@ -290,12 +292,12 @@ __host__ __device__ constexpr int d_vl(int nu, int N, bool ct, int wpg, int cu_w
     return want <= vlmax ? want : -1;
 }
 __host__ __device__ constexpr size_t d_lds_bytes(int nu, int N, bool ct, int wpg, int vl, bool fam = false, bool adapt = false, bool imod = false, int ilin = 0,
-                                                 int knots = 0) {
+                                                 int knots = 0, bool itraj = false) {
     return sizeof(double) * ((size_t)(imod ? 0 : D_OPS_DOUBLES + D_START_DOUBLES) + (ct ? 0 : d_tab_doubles(N)) + (fam && !ilin ? D_FAM_DOUBLES : 0) + (adapt ? D_ADAPT_DOUBLES : 0) +
 #if TINY_TRIM_DSTORE
                              (size_t)wpg * (vl * 64 + D_DUMP_DOUBLES(nu) + d_d_doubles(nu, N) + (imod ? D_IMOD_WAVE_DOUBLES : 0)));
 #else
-                             (size_t)wpg * (vl * 64 + d_d_doubles(nu, N) + (imod ? D_IMOD_WAVE_DOUBLES : 0) + d_ilin_wave_doubles(ilin, knots)));
+                             (size_t)wpg * (vl * 64 + d_d_doubles(nu, N) + (imod ? D_IMOD_WAVE_DOUBLES : 0) + d_ilin_wave_doubles(ilin, knots) + d_itraj_wave_doubles(itraj, N)));
 #endif
 }
 
@@ -395,7 +397,7 @@ __device__ __forceinline__ bool wave_may_converge_d32(unsigned long long bad, un
 // arithmetic of an instance is that of the plain kernel (bit-identical results: tests/test_hip_parity.py); what changes is that
 // a wavefront's time is the sum of what its rows worked, not four times its slowest instance.
 template <int NX, int NU, int N, bool CT, int WPG, int VL, bool FAM = false, bool ADAPT = false, bool TWO_PER_SIMD = true, bool HOSTX = false,
-          bool REFILL = false, bool IGOAL = false, bool IMOD = false, int ILIN = 0, bool ICONE = false, bool IKNOT = false>
+          bool REFILL = false, bool IGOAL = false, bool IMOD = false, int ILIN = 0, bool ICONE = false, bool IKNOT = false, bool ITRAJ = false>
 #else
 // IGOAL: the per-instance goal form (every instance's references and bounds constant over the horizon; k_admm_solve_d_gbnd) -- the
 // four table constants lr_c, pNref, lo_c and hi_c come per lane from SolveParams::iref_lr / iref_pn / ibnd ([instance][16], ibnd's hi
@@ -413,8 +415,13 @@ template <int NX, int NU, int N, bool CT, int WPG, int VL, bool FAM = false, boo
 // SolveParams::ilin holds N slots of 3 nl vectors in the forward sweep's own skew (k_build_inst_lin_knots: slot 0 is knot 0 on the state
 // lanes, slot q+1 what forward step q finishes), the third vector already 1 / ||a_k||^2. The wavefront stages the whole block, verbatim,
 // and `families` reads the slot of its call: the horizon is unrolled, so a slot is a compile-time offset of the same three reads.
+// ITRAJ (with IGOAL): per-instance reference TRAJECTORIES and tracks (tinympc_set_x_ref_batch / _u_ref_batch / the track verbs after
+// tinympc_prepare) -- SolveParams::iref_lr is layout A's store, [group][N + 2][64] in this kernel's lane order (k_build_inst_tables: row
+// k + 1 = knot k), and the wavefront stages its group's block, verbatim, into an LDS region of its own. The backward sweep reads the
+// linref of slot S there, the row the shared !CT form reads in the workgroup's table, one block ahead like the slack; bounds and pNref
+// stay the goal form's (constant over the horizon, per lane). FOLD needs references constant over the horizon: off.
 template <int NX, int NU, int N, bool CT, int WPG, int VL, bool FAM = false, bool ADAPT = false, bool TWO_PER_SIMD = true, bool HOSTX = false,
-          bool REFILL = false, bool IGOAL = false, bool IMOD = false, int ILIN = 0, bool ICONE = false, bool IKNOT = false>
+          bool REFILL = false, bool IGOAL = false, bool IMOD = false, int ILIN = 0, bool ICONE = false, bool IKNOT = false, bool ITRAJ = false>
 #endif
 __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double *smem) {
     static_assert(!(FAM && ADAPT), "adaptive rho and the constraint families exclude each other (as in the C ABI)");
@@ -422,6 +429,8 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
                   "per-instance models: the goal form of the box path (its rows are always built per instance), plain sweeps");
     static_assert(!ICONE || ILIN > 0, "per-instance cone slopes: with the per-instance rows' form (one absent row where there are none)");
     static_assert(!IKNOT || ILIN > 0, "rows per knot: a form of the per-instance rows");
+    static_assert(!ITRAJ || (IGOAL && CT && !FAM && !ADAPT && !IMOD && ILIN == 0 && !REFILL && !HOSTX && !TINY_LEAN),
+                  "per-instance trajectories: the goal form of the box path (bounds constant over the horizon), plain sweeps");
     static_assert(ILIN == 0 || (ILIN > 0 && ILIN <= MAX_LIN_ROWS && FAM && IGOAL && CT && !ADAPT && !IMOD && !REFILL && !HOSTX && !TINY_LEAN),
                   "per-instance linear rows: the families' variant in the goal form (references and bounds constant over the horizon), plain sweeps");
 #if TINY_REFILL
@@ -440,7 +449,7 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
     // into a sweep). FOLD (references constant over the horizon as well): the backward step's input-row operand r_s = -rho * t + lr_c
     // is not formed; the operator's input columns carry -rho and the accumulator starts carry Mb[:, nx:] * lr_c instead (Step::bwd_fold).
     constexpr bool K0 = !FAM && !ADAPT && !REFILL;
-    constexpr bool FOLD = !FAM && !ADAPT && CT;
+    constexpr bool FOLD = !FAM && !ADAPT && CT && !ITRAJ;
 
 #ifdef TINY_CLOCK_STAMP
     const unsigned long long ck_entry = __builtin_amdgcn_s_memrealtime();
@@ -471,11 +480,15 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
     double *sV = sAd + (ADAPT ? D_ADAPT_DOUBLES : 0) + (size_t)wv * (VL * 64 + D_DUMP_DOUBLES(NU) + d_d_doubles(NU, N));
     double *sD = sV + VL * 64 + D_DUMP_DOUBLES(NU);  // (rows -1 and -2 of d: written by the dump lanes of the lean backward sweeps, never read)
 #else
-    double *sV = sAd + (ADAPT ? D_ADAPT_DOUBLES : 0) + (size_t)wv * (VL * 64 + d_d_doubles(NU, N) + (IMOD ? D_IMOD_WAVE_DOUBLES : 0) + d_ilin_wave_doubles(ILIN, IKNOT ? N : 0));
+    double *sV = sAd + (ADAPT ? D_ADAPT_DOUBLES : 0) + (size_t)wv * (VL * 64 + d_d_doubles(NU, N) + (IMOD ? D_IMOD_WAVE_DOUBLES : 0) + d_ilin_wave_doubles(ILIN, IKNOT ? N : 0) +
+                                                                       d_itraj_wave_doubles(ITRAJ, N));
     double *sD = sV + VL * 64;
 #endif
     double *sOpsW = sD + d_d_doubles(NU, N);  // IMOD: [4 instances][D_IMOD_STRIDE]
     double *sLinW = sD + d_d_doubles(NU, N);  // ILIN: [3 nl][64], this wavefront's group of SolveParams::ilin (never together with IMOD); IKNOT: [N slots][3 nl][64]
+    double *sRefW = sD + d_d_doubles(NU, N);  // ITRAJ: [N + 2][64], this wavefront's group of SolveParams::iref_lr (never together with IMOD or ILIN)
+    static_assert(!ITRAJ || sizeof(double) * (D_OPS_DOUBLES + D_START_DOUBLES + VL * 64 + d_d_doubles(NU, N) + d_itraj_wave_doubles(true, N)) < 65536,
+                  "per-instance trajectories: the last row's reads stay below the 16-bit ds offset field, whatever constant part of the address the compiler folds in");
     // (a slot's rows lie LIN_SLOT doubles behind the last slot's: 0 where the rows are constant over the horizon -- one code path)
     constexpr int LIN_SLOT = IKNOT ? 3 * ILIN * 64 : 0;
     static_assert(!IKNOT || sizeof(double) * (D_OPS_DOUBLES + D_START_DOUBLES + VL * 64 + d_d_doubles(NU, N) + d_ilin_wave_doubles(ILIN, N)) < 65536,
@@ -512,6 +525,13 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
             const int which = i >> 8, k = (i >> 4) & 15, rr = i & 15;
             const int tbl = which == 0 ? 3 : which == 1 ? 4 : which - 2;
             sAd[i] = (k < KT) ? p.adapt[(size_t)tbl * W * KT + (size_t)rr * KT + k] : 0.0;
+        }
+    }
+    if constexpr (ITRAJ) {
+        // ... per wavefront: its group's linref rows, verbatim (padding rows, and lanes beyond the batch or the system's rows: zero)
+        if (grp_ok) {
+            const double *const rows_g = p.iref_lr + (size_t)grp * d_itraj_wave_doubles(true, N);
+            for (int i = lane; i < d_itraj_wave_doubles(true, N); i += 64) sRefW[i] = rows_g[i];
         }
     }
     if constexpr (IKNOT) {
@@ -710,7 +730,8 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
     double nrho = -rho;
     const double lo_c = IGOAL ? (inst_ok ? p.ibnd[inst * W + r] : 0.0) : p.tables[W + r];
     const double hi_c = IGOAL ? (inst_ok ? p.ibnd[(size_t)p.groups * 64 + inst * W + r] : 0.0) : p.tables[(size_t)TOFF + W + r];
-    const double lr_c = IGOAL ? (inst_ok ? p.iref_lr[inst * W + r] : 0.0) : p.tables[(size_t)2 * TOFF + W + r];
+    // (ITRAJ: iref_lr is the store of every knot's rows, not [instance][16] -- the form reads its linref from sRefW and has no lr_c)
+    const double lr_c = ITRAJ ? 0.0 : IGOAL ? (inst_ok ? p.iref_lr[inst * W + r] : 0.0) : p.tables[(size_t)2 * TOFF + W + r];
     double rhom = is_x ? nrho : 0.0;
 #if TINY_REFILL
     double x0v = (inst_ok && is_x) ? p.x0[inst * NX + r] : 0.0;
@@ -726,6 +747,7 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
     const double *const sTl = sT + koff * W + r;  // (!CT) row of slot s: sTl[(s + 1) * W]
     const double *const sMf = (IMOD ? sOpsW + j * D_IMOD_STRIDE : sOps) + r, *const sMb = sMf + 256;
     const unsigned aV = lds_addr(sVl), aD = lds_addr(sDr), aT = lds_addr(sTl);
+    const unsigned aR = ITRAJ ? lds_addr(sRefW + koff * 64 + lane) : 0u;  // (ITRAJ) row of slot s: offset (s + 1) * 512 -- the knot the shared table's sTl reads
 #if TINY_LDS_START
     const unsigned aC = lds_addr(sStart + r);
 #endif
@@ -1054,7 +1076,7 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
                 // (the test on 32-bit halves: the 64-bit form keeps two 64-bit constants in vector registers across the run)
                 may = __builtin_amdgcn_readfirstlane((int)wave_may_converge_d32(__ballot(bad), __ballot(active))) != 0;
 #else
-                may = __builtin_amdgcn_readfirstlane((int)(ILIN ? wave_may_converge_d32(__ballot(bad), __ballot(active)) : wave_may_converge_d(__ballot(bad), __ballot(active)))) != 0;
+                may = __builtin_amdgcn_readfirstlane((int)((ILIN || ITRAJ) ? wave_may_converge_d32(__ballot(bad), __ballot(active)) : wave_may_converge_d(__ballot(bad), __ballot(active)))) != 0;
 #endif
             }
 #if TINY_REFILL
@@ -1244,7 +1266,7 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
 #elif TINY_LEAN_PARK
                         may = __builtin_amdgcn_readfirstlane((int)wave_may_converge_d32(__ballot(bad), __ballot(active))) != 0;
 #else
-                        may = __builtin_amdgcn_readfirstlane((int)(ILIN ? wave_may_converge_d32(__ballot(bad), __ballot(active)) : wave_may_converge_d(__ballot(bad), __ballot(active)))) != 0;
+                        may = __builtin_amdgcn_readfirstlane((int)((ILIN || ITRAJ) ? wave_may_converge_d32(__ballot(bad), __ballot(active)) : wave_may_converge_d(__ballot(bad), __ballot(active)))) != 0;
 #endif
                     }
                 }
@@ -1340,10 +1362,22 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
         // ---------------- backward sweep (B1, admm.cpp:13-20); linear cost (L1, :77-82) recomputed from V, G
         {
             const unsigned long long wr_d = __ballot(is_u && active);  // a zombie keeps the d of its last real iteration
+            // (ITRAJ: the linref of a slot is a read of the wavefront's rows, issued a block ahead of its use like the slack's LDS part --
+            // the two the sweep's head needs go out in front of the operator rows; slot S: offset (S + 1) * 512 of aR)
+            double lr_head1, lr_head2, lrcur;  // (assigned and read in the ITRAJ form only: no initialiser, so that no other form's code sees them)
+            // (... and a step's accumulator start, lr + cb on state lanes and cb on input lanes, is ONE fused multiply-add on a lane constant
+            // 1 / 0 -- the same bits as the sum and the select of the shared form: the product is exact, the rows are finite)
+            double xsel;
+            if constexpr (ITRAJ) xsel = is_x ? 1.0 : 0.0;
+            if constexpr (ITRAJ) {
+                lr_head1 = lds_read_async<NS * 512>(aR);  // (slot S: offset (S + 1) * 512)
+                lr_head2 = lds_read_async<(NS - 1) * 512>(aR);
+            }
             load_ops(sMb, m);
             auto lr_of = [&](auto S) -> double {  // linref of slot S (its knot differs by lane type) (+ the families' term)
                 double base;
-                if constexpr (CT) base = lr_c;
+                if constexpr (ITRAJ) base = decltype(S)::value == NS - 1 ? lr_head1 : lr_head2;  // (the head's two; the blocks take lrcur)
+                else if constexpr (CT) base = lr_c;
                 else base = sTl[2 * TOFF + (S.value + 1) * W];
                 if constexpr (FAM) base += LX[S.value];
                 return base;
@@ -1355,7 +1389,9 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
                 double lrT = is_x ? pnref_lin : lr_of(std::integral_constant<int, NS - 1>{});
                 if constexpr (FAM) lrT = is_x ? pnref_lin + LX[NS - 1] : lrT;
                 const double lr2 = lr_of(std::integral_constant<int, NS - 2>{});
-                const double lrmc2 = is_x ? lr2 + cb : cb;
+                double lrmc2;
+                if constexpr (ITRAJ) lrmc2 = fma(lr2, xsel, cb);
+                else lrmc2 = is_x ? lr2 + cb : cb;
                 const double v1 = vget(std::integral_constant<int, NS - 1>{}), v2 = vget(std::integral_constant<int, NS - 2>{});
                 double t;
 #if TINY_LEAN_SHARE
@@ -1419,6 +1455,7 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
                 else return lds_read_async<decltype(S)::value * 512>(aV);
             };
             double v2cur = vreq(std::integral_constant<int, (NS >= 3 ? NS - 3 : 0)>{});
+            if constexpr (ITRAJ) lrcur = lds_read_async<(NS - 2) * 512>(aR);  // (slot NS - 3: the first block's)
             lds_wait_ops(m);
 #if TINY_LEAN_HOIST
             // Knot 0's dual update, G0 = s - snew (V0 is snew by now), placed here by hand: the first backward block follows the asm
@@ -1439,8 +1476,16 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
                 // the block's outputs while the read is still in flight)
                 double v2n = 0.0;
                 if constexpr (s >= 2) v2n = vreq(std::integral_constant<int, s3>{});
-                const double lr2 = lr_of(std::integral_constant<int, s2>{});
-                const double lrmc2 = is_x ? lr2 + cb : cb;
+                double lrn;  // (ITRAJ: the next block's linref, slot s3; block 1's tail feeds nothing -- it keeps slot 0's)
+                if constexpr (ITRAJ) {  // (nested: a condition that depends on the step would capture these in every form's lambda)
+                    if constexpr (s >= 2) lrn = lds_read_async<(s3 + 1) * 512>(aR);
+                }
+                double lr2;
+                if constexpr (ITRAJ) lr2 = lrcur;
+                else lr2 = lr_of(std::integral_constant<int, s2>{});
+                double lrmc2;
+                if constexpr (ITRAJ) lrmc2 = fma(lr2, xsel, cb);
+                else lrmc2 = is_x ? lr2 + cb : cb;
 #if TINY_LEAN_PARK
                 if constexpr (SH_B && s >= VLR) {
                     // The shared block below with the run's split: the register of slot s is Vr[s-VL], or Vx[s-VLR] for a converted slot;
@@ -1497,6 +1542,9 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
                 rnext = rn;
                 acc = an;
                 v2cur = v2n;
+                if constexpr (ITRAJ) {
+                    if constexpr (s >= 2) lrcur = lrn;
+                }
             });
 #if TINY_LEAN_SHARE
             if constexpr (SH_B && VL == 0) Step::bwd_last(Vr[0], px, rcur, m);  // (slot 0 is a register slot: d_0 stays in it)
@@ -1800,6 +1848,9 @@ __global__ void __launch_bounds__(64 * WPG) __attribute__((amdgpu_waves_per_eu(2
 #if TINY_JIT_ILIN && TINY_REFILL
 #error "per-instance linear rows: no slot-refill variant"
 #endif
+#if defined(TINY_JIT_ITRAJ) && TINY_JIT_ITRAJ && TINY_REFILL
+#error "per-instance trajectories: no slot-refill variant"
+#endif
 extern "C" __global__ void __launch_bounds__(64 * TINY_JIT_WPG) __attribute__((amdgpu_waves_per_eu(TINY_JIT_WPS, TINY_JIT_WPS)))
 TINY_KERNEL_NAME(const tinympc::SolveParams p) {
 #ifndef TINY_JIT_CT
@@ -1824,9 +1875,13 @@ TINY_KERNEL_NAME(const tinympc::SolveParams p) {
 #endif
     constexpr int ILJ = TINY_JIT_ILIN;  // per-instance linear rows: the mode's row count (with -DTINY_JIT_FAM=1 -DTINY_JIT_IGOAL=1); 0: off
     constexpr int KNJ = TINY_JIT_IKNOT != 0 ? TINY_JIT_N : 0;  // ... in the per-knot form (-DTINY_JIT_IKNOT=1): the slots a wavefront stages
-    constexpr int VLJ = tinympc::d_vl(TINY_JIT_NU, TINY_JIT_N, CTJ, WPGJ, 4 * TINY_JIT_WPS, FAMJ, ADJ, IMJ, ILJ, KNJ);
+#ifndef TINY_JIT_ITRAJ
+#define TINY_JIT_ITRAJ 0
+#endif
+    constexpr bool ITJ = TINY_JIT_ITRAJ != 0;  // per-instance trajectories (with -DTINY_JIT_IGOAL=1): the wavefront's own linref rows
+    constexpr int VLJ = tinympc::d_vl(TINY_JIT_NU, TINY_JIT_N, CTJ, WPGJ, 4 * TINY_JIT_WPS, FAMJ, ADJ, IMJ, ILJ, KNJ, ITJ);
     static_assert(VLJ >= 0, "shape does not fit the layout-D plan");
-    __shared__ __attribute__((aligned(16))) double smem_jit[tinympc::d_lds_bytes(TINY_JIT_NU, TINY_JIT_N, CTJ, WPGJ, VLJ, FAMJ, ADJ, IMJ, ILJ, KNJ) / sizeof(double)];
+    __shared__ __attribute__((aligned(16))) double smem_jit[tinympc::d_lds_bytes(TINY_JIT_NU, TINY_JIT_N, CTJ, WPGJ, VLJ, FAMJ, ADJ, IMJ, ILJ, KNJ, ITJ) / sizeof(double)];
 #if TINY_REFILL
 #ifndef TINY_JIT_REFILL
 #define TINY_JIT_REFILL 0
@@ -1837,7 +1892,7 @@ TINY_KERNEL_NAME(const tinympc::SolveParams p) {
 #define TINY_JIT_IGOAL 0
 #endif
     tinympc::k_admm_solve_d_body<TINY_JIT_NX, TINY_JIT_NU, TINY_JIT_N, CTJ, WPGJ, VLJ, FAMJ, ADJ, TINY_JIT_WPS == 2, false, false,
-                                 TINY_JIT_IGOAL != 0 || IMJ, IMJ, ILJ, TINY_JIT_ICONE != 0, TINY_JIT_IKNOT != 0>(p, smem_jit);
+                                 TINY_JIT_IGOAL != 0 || IMJ, IMJ, ILJ, TINY_JIT_ICONE != 0, TINY_JIT_IKNOT != 0, ITJ>(p, smem_jit);
 #endif
 }
 namespace tinympc {

@@ -820,7 +820,9 @@ class TinyMPC:
         and a batch with per-instance linear rows (set_linear_constraints_batch or set_linear_constraints_knots_batch, before or after
         this call) on layout D's per-instance linear-row form under the same conditions (launch_info()["layout"] and jit_info() say which). Per-instance cone slopes
         (set_cone_slopes_batch) are the other half of that mode and run on the same form, whose cone slope is always the instance's;
-        cones that share rows stay on layout A."""
+        cones that share rows stay on layout A. Per-instance reference trajectories and tracks (set_x_ref_batch / set_u_ref_batch with
+        a trajectory per instance, set_x_ref_track_batch / set_u_ref_track_batch; before or after this call) run on layout D's
+        per-instance trajectory form under the same conditions on shape and bounds, with the shared model and no constraint families."""
         self._check_setup()
         self._push_settings()
         _lib.check(self._L.tinympc_prepare(self._h))

@@ -12,7 +12,16 @@ Every measurement is a fresh process -- the two libraries alternate, `--rounds` 
 first controls of every tick of leg c must equal leg a's bit for bit (asserted here, for every round), and leg c must be faster than
 leg a in every round (asserted too). The tolerances are 0, so every tick of every leg runs exactly `--iters` iterations: the legs
 differ in how the references arrive and in nothing else. Prints a table.
-    python tools/ref_track_sweep.py --parent-lib /path/to/parent/libtinympc_hip.so [--batch 8192] [--N 50] [--T 200] [--ticks 40]"""
+    python tools/ref_track_sweep.py --parent-lib /path/to/parent/libtinympc_hip.so [--batch 8192] [--N 50] [--T 200] [--ticks 40]
+
+Layout D (--d --parent-lib PATH): leg c alone, on a handle that called prepare(), with
+  cA  on the library of the parent commit at PATH (a parent that has the track verbs): layout A, where tracks ran before layout D had a
+      form for them -- the yardstick
+  cD  on this tree's library: layout D's per-instance trajectory form
+Every measurement is a fresh process; the two libraries alternate, `--rounds` times each. The first controls of every tick of cD must
+lie within 1e-9 of cA's (asserted; another kernel, another order of operations), and the bar is cD below cA in EVERY round (reported,
+and the exit status says it).
+    python tools/ref_track_sweep.py --d --parent-lib /path/to/parent/libtinympc_hip.so"""
 import argparse
 import json
 import os
@@ -73,7 +82,7 @@ def window(track, k, cols):
     return np.asfortranarray(track[:, np.minimum(k + np.arange(cols), track.shape[1] - 1), :])
 
 
-def run_leg(pkg, leg, a):
+def run_leg(pkg, leg, a, prepare=False):
     """One closed loop of WARMUP + a.ticks ticks -> (per-tick wall us of the counted ticks, first controls of every tick, iterations)."""
     P = pkg.problems
     prob = P.quadrotor(a.N)
@@ -82,6 +91,8 @@ def run_leg(pkg, leg, a):
     s = pkg.TinyMPC()
     s.setup(prob.A, prob.B, prob.Q, prob.R, N, batch=batch, rho=prob.rho, max_iter=a.iters, abs_pri_tol=0.0, abs_dua_tol=0.0)
     s.set_bound_constraints(prob.x_min, prob.x_max, prob.u_min, prob.u_max)
+    if prepare:
+        s.prepare()
     if leg == "b":
         dX, dU = DeviceTracks(pkg, X), DeviceTracks(pkg, U)
         L = pkg.load_library()
@@ -122,6 +133,51 @@ def child(pkg, a):
         if leg in ("a", "b", "c") and a.dump:
             np.save(os.path.join(a.dump, "u_%s.npy" % leg), us)
     print("TRACK-CHILD " + json.dumps(out), flush=True)
+
+
+def child_d(pkg, a):
+    """One process of the --d sweep: leg c after prepare() on whatever library it loaded; one JSON line, the first controls in a.dump."""
+    wall, us, iters, info = run_leg(pkg, "c", a, prepare=True)
+    np.save(os.path.join(a.dump, "u_%s.npy" % a.leg), us)
+    print("TRACK-CHILD " + json.dumps(dict(leg=a.leg, tick_us=float(np.median(wall)), iters=iters, kernel=info)), flush=True)
+
+
+def sweep_d(a):
+    """The parent of the --d sweep: starts the children (it never opens the GPU itself), compares their first controls, prints the table."""
+    if not a.parent_lib or not os.path.exists(a.parent_lib):
+        raise SystemExit("needs --parent-lib: libtinympc_hip.so built from the parent commit")
+    rows, worst = {"cA": [], "cD": []}, 0.0
+    with tempfile.TemporaryDirectory() as tmp:
+        for rnd in range(a.rounds):
+            for leg in ("cD", "cA") if rnd % 2 == 0 else ("cA", "cD"):
+                env = dict(os.environ)
+                env.pop("TINYMPC_HIP_LIBRARY", None)
+                if leg == "cA":
+                    env["TINYMPC_HIP_LIBRARY"] = os.path.abspath(a.parent_lib)
+                cmd = [sys.executable, os.path.abspath(__file__), "--d", "--child", "--leg", leg, "--dump", tmp] + \
+                      [w for k in ("batch", "N", "T", "ticks", "iters") for w in ("--" + k, str(getattr(a, k)))]
+                r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=500)
+                line = [l for l in r.stdout.splitlines() if l.startswith("TRACK-CHILD ")]
+                if r.returncode != 0 or not line:
+                    raise SystemExit("round %d (%s) failed with %d:\n%s\n%s" % (rnd, leg, r.returncode, r.stdout[-2000:], r.stderr[-2000:]))
+                rows[leg].append(json.loads(line[0][len("TRACK-CHILD "):]))
+                print("# round %d %-3s %.1f us" % (rnd, leg, rows[leg][-1]["tick_us"]), flush=True)
+            ua, ud = np.load(os.path.join(tmp, "u_cA.npy")), np.load(os.path.join(tmp, "u_cD.npy"))
+            worst = max(worst, float(np.max(np.abs(ud - ua)) / np.max(np.abs(ua))))
+    print("reference tracks on layout D, %d quadrotors N=%d, T=%d, every handle after prepare(), closed loop of %d warm-started mpc_step ticks "
+          "(%d iterations each), wall us per tick (median of the ticks of a round; %d rounds, a fresh process each, the two libraries alternating)"
+          % (a.batch, a.N, a.T, a.ticks, a.iters, a.rounds))
+    for leg, name in (("cA", "cA tracks, the parent's library"), ("cD", "cD tracks, this tree")):
+        v = [r["tick_us"] for r in rows[leg]]
+        print("%-32s | %-36s | median %9.1f | spread %8.1f - %8.1f | %.2f iterations / tick | %s"
+              % (name, " ".join("%.1f" % x for x in v), float(np.median(v)), min(v), max(v), rows[leg][0]["iters"], rows[leg][0]["kernel"]))
+    below = all(d["tick_us"] < p_["tick_us"] for d, p_ in zip(rows["cD"], rows["cA"]))
+    print("cD on layout D: %s; first controls within %.1e of cA's (relative to the largest control); cD below cA in every round: %s (ratio of medians %.3f)"
+          % ("yes" if rows["cD"][0]["kernel"].startswith("D ") else "NO", worst, "yes" if below else "NO",
+             float(np.median([r["tick_us"] for r in rows["cD"]])) / float(np.median([r["tick_us"] for r in rows["cA"]]))))
+    assert worst < 1e-9, "the first controls on layout D differ from layout A's"
+    if not below:
+        raise SystemExit(1)
 
 
 def sweep(a):
@@ -184,11 +240,13 @@ def main():
     ap.add_argument("--parent-lib", default="")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--dump", default="", help=argparse.SUPPRESS)
+    ap.add_argument("--d", action="store_true")
+    ap.add_argument("--leg", default="", help=argparse.SUPPRESS)
     a = ap.parse_args()
     if not a.child:
-        return sweep(a)
+        return sweep_d(a) if a.d else sweep(a)
     import __graft_entry__ as ge
-    child(ge.load_package(), a)
+    (child_d if a.d else child)(ge.load_package(), a)
 
 
 if __name__ == "__main__":
