@@ -232,7 +232,10 @@ int tinympc_set_x0_batch_device(tinympc_solver *s, const double *d_x0s, int firs
  * model and rho are the shared ones, and the horizon's N+2 reference rows fit a wavefront's share of LDS beside its other state (the
  * plan's arithmetic decides; for the quadrotor, nu = 4, that is a horizon of about 60 -- N = 50 is compiled in, other shapes are
  * specialised at run time). Whatever misses a condition stays on layout A; tinympc_get_layout and tinympc_get_jit_info
- * (" per-instance-trajectories", or "refused(...)" with the reason) say which ran.
+ * (" per-instance-trajectories", or "refused(...)" with the reason) say which ran. Inside the per-instance families mode
+ * (tinympc_set_linear_constraints_batch, _knots_batch, tinympc_set_cone_slopes_batch) trajectories sent through THESE verbs keep a
+ * prepared handle on layout D as well (see there); a trajectory shared by the batch that arrives through tinympc_set_x_ref /
+ * tinympc_set_u_ref moves that mode to layout A -- a caller who wants layout D sends it through the batch verb.
  * With the cone / linear families, adaptive rho or nx+nu > 64 a solve returns TINYMPC_ERR_UNSUPPORTED (never a solve with
  * the shared reference). The _device forms refuse memory that is not device memory of the handle's GPU.
  * Single-instance handles: the same as tinympc_set_x_ref / tinympc_set_u_ref. The input has been copied when the call
@@ -255,7 +258,9 @@ int tinympc_set_u_ref_batch_device(tinympc_solver *s, const double *d_Urefs, int
  * replace a sub-range with the same T, a whole-batch call may change T; replacing a track does not touch the steps. A half in track
  * mode IS a half with per-instance trajectories: it turns per-instance references on for that half, runs on layout A (even with
  * T = 1: never layout D's goal form) -- or, after tinympc_prepare and under tinympc_set_x_ref_batch's conditions, on layout D's
- * per-instance trajectory form (tinympc_mpc_step_batch with auto-advance included: the rows are rebuilt per tick as on layout A) --,
+ * per-instance trajectory form, or, inside the per-instance families mode, on that mode's form for trajectories
+ * (tinympc_set_linear_constraints_batch; tinympc_mpc_step_batch with auto-advance included: the rows are rebuilt per tick as on layout A,
+ * and the kernel stages the rebuilt rows) --,
  * " reference-track" is appended to tinympc_get_jit_info, and every refusal of per-instance
  * references applies unchanged (the cone / linear families, adaptive rho, nx+nu > 64: a solve returns TINYMPC_ERR_UNSUPPORTED;
  * tinympc_session_begin likewise). tinympc_set_x_ref / _u_ref returns the half to shared references; a whole-batch
@@ -321,10 +326,16 @@ int tinympc_set_bound_constraints_batch_device(tinympc_solver *s, const double *
  * bound verbs (shared and per instance), set_cone_constraints, the solve verbs and mpc_step_batch keep mode and rows.
  * The mode runs on layout A (tinympc_get_layout 'A', " per-instance-linear" in tinympc_get_jit_info) unless tinympc_prepare was
  * called on the handle (before or after this verb): then batches that run the register-resident throughput kernel (layout D) keep it
- * -- every wavefront holds its four instances' rows -- where nx+nu <= 16, references and bounds are constant over the horizon (shared
- * or per instance), no two cones share a row and the horizon and row count fit that kernel's plan (N <= 22); the kernel is compiled in
- * for the quadrotor at N = 20 with one row, specialised at run time otherwise. Trajectories, tracks, per-knot bounds, wider systems,
- * longer horizons and a refused specialisation (tinympc_get_jit_info then reads "refused(<reason>) per-instance-linear") stay on
+ * -- every wavefront holds its four instances' rows -- where nx+nu <= 16, bounds are constant over the horizon (shared or per
+ * instance), every half of the references is constant over the horizon (shared or per instance) or holds per-instance trajectories
+ * or a track (tinympc_set_x_ref_batch / _u_ref_batch with cols = N / N-1, the track verbs), no two cones share a row and the horizon
+ * and row count fit that kernel's plan (N <= 22); the kernel is compiled in for the quadrotor at N = 20 with one row, specialised at
+ * run time otherwise. With per-instance trajectories or tracks every wavefront also holds its four instances' N+2 reference rows
+ * (tinympc_get_jit_info: "... per-instance-linear per-instance-trajectories"; compiled in for the same quadrotor with one row): the
+ * plan then needs 3 max(nlx, nlu) + N + 2 vectors of 64 doubles beside the wavefront's other state (the quadrotor at N = 20: up to 17
+ * rows per side where references constant over the horizon leave room for 24). A trajectory SHARED by the batch (tinympc_set_x_ref / _set_u_ref with columns that
+ * differ) keeps the mode on layout A: send it through the batch verb to stay on layout D. Per-knot bounds, wider systems,
+ * longer horizons and a refused specialisation (tinympc_get_jit_info then reads "refused(<reason>) ... per-instance-linear") stay on
  * layout A, and a handle moves between the two from one launch to the next as its configuration changes; the ADMM state, the family's
  * duals included, is shared, so a warm start carries over. Either way the mode takes cones -- shared, or with every instance's own
  * slopes (tinympc_set_cone_slopes_batch below: the other half of the same mode) --, fdyn, per-instance references
@@ -366,11 +377,14 @@ int tinympc_set_linear_constraints_batch_device(tinympc_solver *s, const double 
  * other half of the same mode, the same store).
  * The mode runs on layout A (tinympc_get_layout 'A', " per-knot-linear" in tinympc_get_jit_info in place of " per-instance-linear")
  * unless tinympc_prepare was called on the handle (before or after this verb): then batches that run the register-resident throughput
- * kernel (layout D) keep it under the conditions of tinympc_set_linear_constraints_batch -- nx+nu <= 16, references and bounds constant
- * over the horizon (shared or per instance), no two cones share a row -- where every wavefront's share of a compute unit's LDS holds
- * its four instances' rows of ALL knots, 3 max(nlx, nlu) N vectors of 64 doubles: one row per side up to N = 22, two up to N = 12,
- * three up to N = 8. The kernel is compiled in for the quadrotor at N = 20 with one row, specialised at run time otherwise. Without
- * tinympc_prepare, with trajectories, tracks, per-knot bounds, wider systems, cones in rounds, or after a refused plan
+ * kernel (layout D) keep it under the conditions of tinympc_set_linear_constraints_batch -- nx+nu <= 16, bounds constant over the
+ * horizon, references constant over the horizon or per-instance trajectories / tracks, no two cones share a row -- where every
+ * wavefront's share of a compute unit's LDS holds its four instances' rows of ALL knots, 3 max(nlx, nlu) N vectors of 64 doubles: one
+ * row per side up to N = 22, two up to N = 12, three up to N = 8. The kernel is compiled in for the quadrotor at N = 20 with one row,
+ * specialised at run time otherwise. With per-instance trajectories or tracks the wavefront's N+2 reference rows share that space
+ * (" per-knot-linear per-instance-trajectories"): one row per side up to N = 17, two up to N = 10, three up to N = 7 for the
+ * quadrotor (nu = 4); the quadrotor at N = 20 with one row per knot and trajectories has no plan and stays on layout A. Without
+ * tinympc_prepare, with a shared trajectory, per-knot bounds, wider systems, cones in rounds, or after a refused plan
  * (tinympc_get_jit_info then reads "refused(<reason>) ... per-knot-linear") the mode stays on layout A, and a handle moves between the
  * two from one launch to the next as its configuration changes; the ADMM state, the rows' duals included, is shared, so a warm start
  * carries over. On layout D, too, an instance whose rows are equal at every knot gives, bit for bit, what
@@ -409,8 +423,9 @@ int tinympc_set_linear_constraints_knots_batch_device(tinympc_solver *s, const d
  * the half that is off holds the shared values for every instance (one absent row on a handle without linear rows); layout D's form
  * is specialised on the row count and on whether the slopes' half is on. So the mode runs where the rows'
  * mode runs -- layout A (" per-instance-cones" in tinympc_get_jit_info, beside " per-instance-linear" when both halves are on), or,
- * after tinympc_prepare, layout D under the conditions stated above (the kernel is compiled in for the rocket landing nx=6 nu=3 N=10
- * with one row, specialised at run time otherwise; cones that share rows stay on layout A) -- and is refused where that mode is
+ * after tinympc_prepare, layout D under the conditions stated above, per-instance trajectories and tracks included (the kernel is
+ * compiled in for the rocket landing nx=6 nu=3 N=10 with one row and references constant over the horizon, specialised at run time
+ * otherwise -- the landing that follows its reference trajectory per instance among them; cones that share rows stay on layout A) -- and is refused where that mode is
  * refused: with per-instance models or rho, adaptive rho, nx+nu > 64 or more cones / rounds than the generic kernels hold a solve
  * returns TINYMPC_ERR_UNSUPPORTED (never a solve with shared slopes), and so does tinympc_session_begin.
  * Invalid arguments -- a slope that is NaN, infinite or <= 0, a count that differs from the structure's, no cones on the handle, NULL
@@ -604,7 +619,10 @@ int tinympc_get_jit_info(tinympc_solver *s, char *buf, int len);
  * (tinympc_set_linear_constraints_batch, in either order) on layout D's per-instance linear-row form likewise; and a batch with
  * per-instance reference trajectories or tracks (tinympc_set_x_ref_batch / _u_ref_batch with cols = N / N-1, the track verbs, in either
  * order) on layout D's per-instance trajectory form -- nx+nu <= 16, bounds constant over the horizon, no per-instance models or rho, no
- * cone / linear families, no adaptive rho, a horizon whose reference rows fit a wavefront's LDS share; otherwise layout A as without
+ * cone / linear families, no adaptive rho, a horizon whose reference rows fit a wavefront's LDS share; and a batch with BOTH
+ * per-instance linear rows (or rows per knot, or cone slopes) and per-instance trajectories or tracks on the linear-row form that reads
+ * every wavefront's own reference rows, where rows and references fit the wavefront's LDS share together (a trajectory shared by the
+ * batch through tinympc_set_x_ref / _set_u_ref is not one of these: layout A); otherwise layout A as without
  * this call. No reference
  * counterpart (the reference has one code path). */
 int tinympc_prepare(tinympc_solver *s);

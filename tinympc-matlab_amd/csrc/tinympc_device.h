@@ -270,7 +270,8 @@ struct SolveParams {
     // [groups][N+2][64] (row k+1 = knot k, the same padding rows as the shared tables), iref_pn [groups][64] = [instance][W].
     // Layout D's goal form (k_admm_solve_d_gbnd, -DTINY_JIT_IGOAL=1): iref_lr is knot 0's linref, [instance][W]. NULL otherwise.
     // Layout D's trajectory form (-DTINY_JIT_ITRAJ=1): iref_lr is layout A's store itself, [groups][N+2][64] without the pad rows in
-    // front (a wavefront stages its group's block into its own LDS region); iref_pn and ibnd are the goal form's.
+    // front (a wavefront stages its group's block into its own LDS region); iref_pn and ibnd are the goal form's. With -DTINY_JIT_ILIN
+    // beside it (the per-instance families on trajectories) likewise, and ilin is the families' store.
     union { const double *ftab; const double *iref_pn; };
     // Per-instance clamp rows (ibnd, in the mail slot above), built by k_build_inst_tables with k_build_tables' expressions -- from every
     // instance's own bounds (tinympc_set_bound_constraints_batch) or from the shared ones. Layout A's InstBounds variant (per-instance
@@ -661,6 +662,11 @@ hipError_t launch_solve_m(const SolveParams &p, hipStream_t stream);
 // knots (with ilin): ... the rows of every knot (-DTINY_JIT_IKNOT=1; knots = N, the slots per group of SolveParams::ilin, staged whole; 0: off)
 // traj (with goal): the per-instance trajectory form (-DTINY_JIT_ITRAJ=1: the goal form reading every instance's own linref rows,
 // SolveParams::iref_lr = layout A's store [groups][N + 2][64], staged per wavefront; 16 lanes, box path). With TINYMPC_JIT=0 only a compiled-in one.
+// traj with ilin (icone, knots as they are): the per-instance families on the same rows, staged behind the wavefront's linear rows --
+// per-instance trajectories and tracks only: a SHARED trajectory (tinympc_set_x_ref / _set_u_ref) keeps the mode on layout A, callers
+// who want this form send it through the batch verb. The plan holds both per-wavefront terms: the quadrotor at N=20 with one row takes
+// 304 (d) + 192 (rows) + 1,408 (linref rows) of a wavefront's 4,992 doubles (one wavefront per SIMD: the families' registers); with rows
+// per knot it needs 304 + 3,840 + 1,408 and has no plan -- one row per knot fits up to N=17, two up to N=10, three up to N=7.
 bool solve_jit_supported(int W, int nx, int nu, int N, bool const_tables, bool families = false, bool adaptive = false, bool goal = false,
                          bool models = false, int ilin = 0, bool icone = false, int knots = 0, bool traj = false);
 hipError_t launch_solve_jit(const SolveParams &p, int W, hipStream_t stream, bool models = false, int ilin = 0, bool icone = false, int knots = 0,

@@ -111,8 +111,9 @@ struct InstState {
     // instance: lrows is the store the kernel reads, SolveParams::ilin, [group][3 lin_nl][64] with lin_nl = max(lin_nlx, lin_nlu)
     // (k_build_inst_lin; instances the verb never named hold the shared rows of the moment the mode began). Nothing else is kept: the
     // store IS the rows, written inside the call. The mode runs on layout A's InstFamilies variant, always with the per-instance
-    // reference and clamp rows -- or, once the caller has asked for specialised kernels (tinympc_prepare), references and bounds are
-    // constant over the horizon and the cones are ones layout D's families kernel takes, on layout D's ILIN form (lin_wants_d).
+    // reference and clamp rows -- or, once the caller has asked for specialised kernels (tinympc_prepare), bounds are constant over the
+    // horizon, every reference half is constant over the horizon or a per-instance trajectory / track, and the cones are ones layout D's
+    // families kernel takes, on layout D's ILIN form (lin_wants_d; with trajectories: ILIN with ITRAJ, lin_d_traj).
     bool lin = false;
     int lin_nlx = 0, lin_nlu = 0, lin_nl = 0;
     // ... and its third state, rows per KNOT (tinympc_set_linear_constraints_knots_batch): lin_knots = N while it is on, 0 otherwise. The store
@@ -125,6 +126,7 @@ struct InstState {
     int d_lin = -1, d_lin_nl = 0;
     bool d_lin_cones = false;                // ... and for the slope half on / off (ICONE: the form that reads the slope per instance)
     int d_lin_knots = 0;                     // ... and for rows per knot (lin_knots of the answer) or rows constant over the horizon (0)
+    bool d_lin_traj = false;                 // ... and for per-instance trajectories / tracks (ITRAJ with ILIN: the wavefront's own linref rows) or references constant over the horizon
     double *lrows = nullptr;
     size_t lrows_cap = 0;                    // doubles lrows was allocated for
     double *lstage = nullptr;                // device staging of host input (the shared rows of a sub-range first call: a block of their own, freed in the call)
@@ -400,7 +402,7 @@ struct LaunchPlan {
     bool inst_bounds = false;                // ... per-instance bounds (layout A's InstBounds variant)
     bool inst_models = false;                // ... per-instance models (layout A's InstModels variant; inst_refs and inst_bounds are set with it)
     bool inst_lin = false;                   // ... per-instance linear rows (layout A's InstFamilies variant, or layout D's ILIN form: D_JIT; inst_refs and inst_bounds are set with it)
-    bool inst_traj = false;                  // ... per-instance trajectories / tracks on layout D's ITRAJ form (D_JIT; inst_refs is set with it)
+    bool inst_traj = false;                  // ... per-instance trajectories / tracks on layout D's ITRAJ form (D_JIT; inst_refs is set with it; beside inst_lin: the families' form on them)
     bool jit = false;                        // a run-time specialisation (tinympc_jit.hip) rather than a compiled-in kernel
     bool host_exchange = false;              // the kernel serves the pinned-host paths (x0 in, solution / completion stamp out)
     int workgroups = 0;

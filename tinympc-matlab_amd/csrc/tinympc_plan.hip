@@ -180,19 +180,28 @@ bool lin_runs(const tinympc_solver *s) {
     return s->inst.fam() && !s->layout_m && !s->inst.models && !s->st.adaptive_rho && !family_structure(s).beyond_generic();
 }
 // ... on layout D: opt-in like the models' form (tinympc_prepare -- without it the mode stays on layout A, which needs no specialisation),
-// where the handle runs layout D, 16 lanes per instance, references and bounds constant over the horizon (shared or per instance: no
-// trajectories, tracks or per-knot bounds), and a cone structure layout D's shared families kernel takes (decide_layout_d_variants: no
-// rounds of overlapping cones). Whether the kernel exists for the mode's row count is inst.d_lin (resolve_plan).
+// where the handle runs layout D, 16 lanes per instance, bounds constant over the horizon (shared or per instance: no per-knot bounds),
+// every half of the references constant over the horizon (shared or per instance) or a per-instance trajectory / track (lin_d_traj:
+// the form then reads its linref rows per wavefront, ITRAJ -- a SHARED trajectory, tinympc_set_x_ref / _set_u_ref, keeps the mode on
+// layout A), and a cone structure layout D's shared families kernel takes (decide_layout_d_variants: no rounds of overlapping cones).
+// Whether the kernel exists for the mode's row count is inst.d_lin (resolve_plan).
 // Rows per knot (tinympc_set_linear_constraints_knots_batch) take the same way: the form's per-knot variant (lin_d_knots), whose
 // per-wavefront plan holds N slots of rows -- where it does not fit the mode stays on layout A's InstFamiliesKnots variant.
 int lin_d_knots(const tinympc_solver *s) { return s->inst.lin ? s->inst.lin_knots : 0; }
+bool lin_d_traj(const tinympc_solver *s) { return (s->inst.x && !s->inst.x_const) || (s->inst.u && !s->inst.u_const); }
+// (references and bounds as the form takes them: iref_goal() with "constant" relaxed to "or a per-instance trajectory" on each reference half)
+bool lin_refs_fit_d(const tinympc_solver *s) {
+    const InstState &in = s->inst;
+    return (in.x || s->xref_const) && (in.u || s->uref_const) && (in.bounds ? in.bounds_const : s->xmin_const && s->xmax_const && s->umin_const && s->umax_const);
+}
 bool lin_wants_d(const tinympc_solver *s) {
-    return lin_runs(s) && s->specialise_asked && s->layout_d && s->W == 16 && s->iref_goal() && family_structure(s).nround <= 1;
+    return lin_runs(s) && s->specialise_asked && s->layout_d && s->W == 16 && lin_refs_fit_d(s) && family_structure(s).nround <= 1;
 }
-bool lin_on_d(const tinympc_solver *s) {
-    return lin_wants_d(s) && s->inst.d_lin == 1 && s->inst.d_lin_nl == s->ifam_nl() && s->inst.d_lin_cones == s->inst.cones &&
-           s->inst.d_lin_knots == lin_d_knots(s);
+// (the answer inst.d_lin is the one for this mode's row count, slopes, knots and trajectories)
+bool lin_d_answer_current(const tinympc_solver *s) {
+    return s->inst.d_lin_nl == s->ifam_nl() && s->inst.d_lin_cones == s->inst.cones && s->inst.d_lin_knots == lin_d_knots(s) && s->inst.d_lin_traj == lin_d_traj(s);
 }
+bool lin_on_d(const tinympc_solver *s) { return lin_wants_d(s) && s->inst.d_lin == 1 && lin_d_answer_current(s); }
 
 }  // namespace
 
@@ -208,10 +217,12 @@ namespace host {
 //   per-instance models                D's model form (only after tinympc_prepare: 16 lanes, references and bounds constant over the horizon,
 //                                      a horizon its per-wavefront operator plan holds)  >  A (the same refusals)
 //                                      (the mode of tinympc_set_model_batch AND tinympc_set_rho_batch: one form, rho always read per instance)
-//   per-instance linear rows           D's ILIN form (only after tinympc_prepare: 16 lanes, references and bounds constant over the horizon, cones
+//   per-instance linear rows           D's ILIN form (only after tinympc_prepare: 16 lanes, bounds constant over the horizon, every reference half
+//                                      constant over the horizon or a per-instance trajectory / track -- then ILIN with ITRAJ, the wavefront's
+//                                      own linref rows behind its linear rows; a SHARED trajectory stays on layout A --, cones
 //                                      without rounds, a horizon and row count its per-wavefront plan holds)  >  A's InstFamilies variant,
 //                                      (rows per knot: the form's per-knot variant, N slots of rows per wavefront -- one row up to N=22, two up
-//                                      to N=12, three up to N=8  >  A's InstFamiliesKnots variant),
+//                                      to N=12, three up to N=8; beside trajectories N=17, 10, 7 for the quadrotor  >  A's InstFamiliesKnots variant),
 //                                      whatever else is per instance (references, bounds) or shared (cones); with
 //                                      per-instance models / rho, adaptive rho, layout M or a cone structure beyond the generic kernels, launch() refuses
 LaunchPlan current_plan(const tinympc_solver *s) {
@@ -222,6 +233,7 @@ LaunchPlan current_plan(const tinympc_solver *s) {
     if (lin_runs(s)) {
         pl.kernel = lin_on_d(s) ? KernelId::D_JIT : KernelId::A;
         pl.inst_lin = pl.inst_refs = pl.inst_bounds = true;  // (both kernels always run on per-instance reference and clamp rows)
+        pl.inst_traj = pl.kernel == KernelId::D_JIT && lin_d_traj(s);  // (the form on the wavefront's own linref rows)
     } else if (s->inst_tables() && !s->inst.fam() && !s->layout_m && !fam && !adaptive) {
         // goals, where the handle runs layout D: its constant-table kernel (compiled in for the 16-lane shapes that are, run-time
         // specialised otherwise -- wide systems included); trajectories, and goals without such a kernel: layout A. "Goal" means that
@@ -327,12 +339,15 @@ int resolve_plan(tinympc_solver *s) {
         // ... and the linear-row form's, for the mode's row count (compiled in for the quadrotor N=20 with one row, specialised now
         // otherwise; a refusal leaves the mode on layout A). Another count is another specialisation: asked again -- and so is the other
         // of rows constant over the horizon and rows per knot (compiled in for the same quadrotor with one row).
-        if (s->inst.fam() && (s->inst.d_lin_nl != s->ifam_nl() || s->inst.d_lin_cones != s->inst.cones || s->inst.d_lin_knots != lin_d_knots(s))) s->inst.d_lin = -1;
+        // ... and of references constant over the horizon and per-instance trajectories / tracks (compiled in for the same quadrotor with
+        // one row): the trajectory bit is one more part of the answer.
+        if (s->inst.fam() && !lin_d_answer_current(s)) s->inst.d_lin = -1;
         if (s->inst.d_lin < 0 && lin_wants_d(s)) {
             s->inst.d_lin_nl = s->ifam_nl();
             s->inst.d_lin_cones = s->inst.cones;
             s->inst.d_lin_knots = lin_d_knots(s);
-            s->inst.d_lin = solve_jit_supported(s->W, s->nx, s->nu, s->N, true, true, false, true, false, s->ifam_nl(), s->inst.cones, lin_d_knots(s)) ? 1 : 0;
+            s->inst.d_lin_traj = lin_d_traj(s);
+            s->inst.d_lin = solve_jit_supported(s->W, s->nx, s->nu, s->N, true, true, false, true, false, s->ifam_nl(), s->inst.cones, lin_d_knots(s), s->inst.d_lin_traj) ? 1 : 0;
         }
         return TINYMPC_OK;
     }
@@ -662,6 +677,9 @@ int tinympc_get_jit_info(tinympc_solver *s, char *buf, int len) {
     if (s->inst.tracks()) strncat(buf, " reference-track", (size_t)len - strlen(buf) - 1);  // (a half is in track mode)
     if (s->inst.lin) strncat(buf, s->inst.lin_knots ? " per-knot-linear" : " per-instance-linear", (size_t)len - strlen(buf) - 1);
     if (s->inst.cones) strncat(buf, " per-instance-cones", (size_t)len - strlen(buf) - 1);
+    // (the families' form on per-instance trajectories / tracks, taken or asked for and refused: behind the mode's own words)
+    if (s->inst.fam() && lin_wants_d(s) && lin_d_traj(s) && s->inst.d_lin >= 0 && lin_d_answer_current(s))
+        strncat(buf, " per-instance-trajectories", (size_t)len - strlen(buf) - 1);
     return TINYMPC_OK;
 }
 
@@ -674,7 +692,7 @@ static int jit_info_text(tinympc_solver *s, char *buf, int len) {
         const std::string w = std::string(s->inst.refs() ? " per-instance-refs" : "") + (s->inst.bounds ? " per-instance-bounds" : "") +
                               (pl.inst_models ? " per-instance-models" : "");
         const char *words = w.c_str();
-        if (pl.kernel == KernelId::D_JIT && pl.inst_traj) {  // layout D's trajectory form
+        if (pl.kernel == KernelId::D_JIT && pl.inst_traj && !pl.inst_lin) {  // layout D's trajectory form (box path)
             if ((rc = bind_device(s))) return rc;
             solve_jit_describe(s->W, s->nx, s->nu, s->N, true, false, false, buf, (size_t)len, true, false, 0, false, 0, true);
             strncat(buf, words, (size_t)len - strlen(buf) - 1);
@@ -687,14 +705,15 @@ static int jit_info_text(tinympc_solver *s, char *buf, int len) {
         } else if (pl.kernel == KernelId::D_JIT) {
             if ((rc = bind_device(s))) return rc;
             const int ilin = pl.inst_lin ? s->ifam_nl() : 0;
-            solve_jit_describe(s->W, s->nx, s->nu, s->N, true, ilin != 0, false, buf, (size_t)len, true, pl.inst_models, ilin, ilin && s->inst.cones, ilin ? lin_d_knots(s) : 0);
+            solve_jit_describe(s->W, s->nx, s->nu, s->N, true, ilin != 0, false, buf, (size_t)len, true, pl.inst_models, ilin, ilin && s->inst.cones, ilin ? lin_d_knots(s) : 0,
+                               pl.inst_traj);
             strncat(buf, words, (size_t)len - strlen(buf) - 1);
-            strncat(buf, " goal", (size_t)len - strlen(buf) - 1);
-        } else if (pl.inst_lin && lin_wants_d(s) && s->inst.d_lin == 0 && s->inst.d_lin_nl == s->ifam_nl() && s->inst.d_lin_cones == s->inst.cones && s->inst.d_lin_knots == lin_d_knots(s)) {  // asked for and refused: layout A, and why
+            if (!pl.inst_traj) strncat(buf, " goal", (size_t)len - strlen(buf) - 1);  // (the families' form on trajectories, inst_lin with inst_traj: named behind the mode's words)
+        } else if (pl.inst_lin && lin_wants_d(s) && s->inst.d_lin == 0 && lin_d_answer_current(s)) {  // asked for and refused: layout A, and why
             if ((rc = bind_device(s))) return rc;
-            solve_jit_describe(s->W, s->nx, s->nu, s->N, true, true, false, buf, (size_t)len, true, false, s->ifam_nl(), s->inst.cones, lin_d_knots(s));
+            solve_jit_describe(s->W, s->nx, s->nu, s->N, true, true, false, buf, (size_t)len, true, false, s->ifam_nl(), s->inst.cones, lin_d_knots(s), lin_d_traj(s));
             strncat(buf, words, (size_t)len - strlen(buf) - 1);
-        } else if (pl.inst_lin && lin_runs(s) && s->specialise_asked && s->layout_d && s->W == 16 && s->iref_goal() && family_structure(s).nround > 1) {
+        } else if (pl.inst_lin && lin_runs(s) && s->specialise_asked && s->layout_d && s->W == 16 && lin_refs_fit_d(s) && family_structure(s).nround > 1) {
             // asked for, and only the cones keep the mode off layout D: layout A, and why
             snprintf(buf, (size_t)len, "refused(cones that share rows run in rounds: layout D's per-instance form takes cones without rounds) layout=%c%s",
                      pl.layout, words);

@@ -420,6 +420,8 @@ template <int NX, int NU, int N, bool CT, int WPG, int VL, bool FAM = false, boo
 // k + 1 = knot k), and the wavefront stages its group's block, verbatim, into an LDS region of its own. The backward sweep reads the
 // linref of slot S there, the row the shared !CT form reads in the workgroup's table, one block ahead like the slack; bounds and pNref
 // stay the goal form's (constant over the horizon, per lane). FOLD needs references constant over the horizon: off.
+// ITRAJ with ILIN (ICONE and IKNOT as they are): the per-instance families on per-instance trajectories -- both blocks are staged, the
+// trajectory rows behind the linear rows, and every linref of the backward sweep is the row's read plus the families' LX of its slot.
 template <int NX, int NU, int N, bool CT, int WPG, int VL, bool FAM = false, bool ADAPT = false, bool TWO_PER_SIMD = true, bool HOSTX = false,
           bool REFILL = false, bool IGOAL = false, bool IMOD = false, int ILIN = 0, bool ICONE = false, bool IKNOT = false, bool ITRAJ = false>
 #endif
@@ -429,8 +431,8 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
                   "per-instance models: the goal form of the box path (its rows are always built per instance), plain sweeps");
     static_assert(!ICONE || ILIN > 0, "per-instance cone slopes: with the per-instance rows' form (one absent row where there are none)");
     static_assert(!IKNOT || ILIN > 0, "rows per knot: a form of the per-instance rows");
-    static_assert(!ITRAJ || (IGOAL && CT && !FAM && !ADAPT && !IMOD && ILIN == 0 && !REFILL && !HOSTX && !TINY_LEAN),
-                  "per-instance trajectories: the goal form of the box path (bounds constant over the horizon), plain sweeps");
+    static_assert(!ITRAJ || (IGOAL && CT && FAM == (ILIN > 0) && !ADAPT && !IMOD && !REFILL && !HOSTX && !TINY_LEAN),
+                  "per-instance trajectories: the goal form of the box path, or of the per-instance families (bounds constant over the horizon), plain sweeps");
     static_assert(ILIN == 0 || (ILIN > 0 && ILIN <= MAX_LIN_ROWS && FAM && IGOAL && CT && !ADAPT && !IMOD && !REFILL && !HOSTX && !TINY_LEAN),
                   "per-instance linear rows: the families' variant in the goal form (references and bounds constant over the horizon), plain sweeps");
 #if TINY_REFILL
@@ -486,12 +488,13 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
 #endif
     double *sOpsW = sD + d_d_doubles(NU, N);  // IMOD: [4 instances][D_IMOD_STRIDE]
     double *sLinW = sD + d_d_doubles(NU, N);  // ILIN: [3 nl][64], this wavefront's group of SolveParams::ilin (never together with IMOD); IKNOT: [N slots][3 nl][64]
-    double *sRefW = sD + d_d_doubles(NU, N);  // ITRAJ: [N + 2][64], this wavefront's group of SolveParams::iref_lr (never together with IMOD or ILIN)
-    static_assert(!ITRAJ || sizeof(double) * (D_OPS_DOUBLES + D_START_DOUBLES + VL * 64 + d_d_doubles(NU, N) + d_itraj_wave_doubles(true, N)) < 65536,
+    // ITRAJ: [N + 2][64], this wavefront's group of SolveParams::iref_lr (never together with IMOD), behind the wavefront's linear rows where the form has both
+    double *sRefW = sLinW + d_ilin_wave_doubles(ILIN, IKNOT ? N : 0);
+    static_assert(!ITRAJ || sizeof(double) * (D_OPS_DOUBLES + D_START_DOUBLES + VL * 64 + d_d_doubles(NU, N) + d_ilin_wave_doubles(ILIN, IKNOT ? N : 0) + d_itraj_wave_doubles(true, N)) < 65536,
                   "per-instance trajectories: the last row's reads stay below the 16-bit ds offset field, whatever constant part of the address the compiler folds in");
     // (a slot's rows lie LIN_SLOT doubles behind the last slot's: 0 where the rows are constant over the horizon -- one code path)
     constexpr int LIN_SLOT = IKNOT ? 3 * ILIN * 64 : 0;
-    static_assert(!IKNOT || sizeof(double) * (D_OPS_DOUBLES + D_START_DOUBLES + VL * 64 + d_d_doubles(NU, N) + d_ilin_wave_doubles(ILIN, N)) < 65536,
+    static_assert(!IKNOT || sizeof(double) * (D_OPS_DOUBLES + D_START_DOUBLES + VL * 64 + d_d_doubles(NU, N) + d_ilin_wave_doubles(ILIN, N) + d_itraj_wave_doubles(ITRAJ, N)) < 65536,
                   "rows per knot: the last slot's reads stay below the 16-bit ds offset field, whatever constant part of the address the compiler folds in");
 
     // ---- workgroup-shared: the two sweep operators, transposed to [k][r] (conflict-free row reads), and the tables
@@ -1368,7 +1371,7 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
             // (... and a step's accumulator start, lr + cb on state lanes and cb on input lanes, is ONE fused multiply-add on a lane constant
             // 1 / 0 -- the same bits as the sum and the select of the shared form: the product is exact, the rows are finite)
             double xsel;
-            if constexpr (ITRAJ) xsel = is_x ? 1.0 : 0.0;
+            if constexpr (ITRAJ && !FAM) xsel = is_x ? 1.0 : 0.0;
             if constexpr (ITRAJ) {
                 lr_head1 = lds_read_async<NS * 512>(aR);  // (slot S: offset (S + 1) * 512)
                 lr_head2 = lds_read_async<(NS - 1) * 512>(aR);
@@ -1390,7 +1393,7 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
                 if constexpr (FAM) lrT = is_x ? pnref_lin + LX[NS - 1] : lrT;
                 const double lr2 = lr_of(std::integral_constant<int, NS - 2>{});
                 double lrmc2;
-                if constexpr (ITRAJ) lrmc2 = fma(lr2, xsel, cb);
+                if constexpr (ITRAJ && !FAM) lrmc2 = fma(lr2, xsel, cb);  // (with the families: their own select -- LX is theirs)
                 else lrmc2 = is_x ? lr2 + cb : cb;
                 const double v1 = vget(std::integral_constant<int, NS - 1>{}), v2 = vget(std::integral_constant<int, NS - 2>{});
                 double t;
@@ -1477,14 +1480,18 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
                 double v2n = 0.0;
                 if constexpr (s >= 2) v2n = vreq(std::integral_constant<int, s3>{});
                 double lrn;  // (ITRAJ: the next block's linref, slot s3; block 1's tail feeds nothing -- it keeps slot 0's)
+                // (... with the families block 1 keeps the very value block 2 used, slot 0's read of block 3: the sums with LX[0] and cb are
+                // then formed once for both, as the goal form forms them on its lane constant)
+                constexpr int LR_LAST = FAM ? 3 : 2;  // the last block that reads ahead
                 if constexpr (ITRAJ) {  // (nested: a condition that depends on the step would capture these in every form's lambda)
-                    if constexpr (s >= 2) lrn = lds_read_async<(s3 + 1) * 512>(aR);
+                    if constexpr (s >= LR_LAST) lrn = lds_read_async<(s3 + 1) * 512>(aR);
                 }
                 double lr2;
-                if constexpr (ITRAJ) lr2 = lrcur;
+                if constexpr (ITRAJ && FAM) lr2 = lrcur + LX[s2];  // (the slot's row + the families' term: lr_of's sum on the read of a block ago)
+                else if constexpr (ITRAJ) lr2 = lrcur;
                 else lr2 = lr_of(std::integral_constant<int, s2>{});
                 double lrmc2;
-                if constexpr (ITRAJ) lrmc2 = fma(lr2, xsel, cb);
+                if constexpr (ITRAJ && !FAM) lrmc2 = fma(lr2, xsel, cb);  // (with the families: their own select -- LX is theirs)
                 else lrmc2 = is_x ? lr2 + cb : cb;
 #if TINY_LEAN_PARK
                 if constexpr (SH_B && s >= VLR) {
@@ -1543,7 +1550,7 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
                 acc = an;
                 v2cur = v2n;
                 if constexpr (ITRAJ) {
-                    if constexpr (s >= 2) lrcur = lrn;
+                    if constexpr (s >= LR_LAST) lrcur = lrn;
                 }
             });
 #if TINY_LEAN_SHARE

@@ -417,7 +417,11 @@ class TinyMPC:
         the arrays may lack the count axis. The row counts belong to the batch, the values to the instance; b = +inf switches one row
         off for one instance. The first call names the whole batch unless the solver holds shared rows of the same counts (the other
         instances then keep those); set_linear_constraints() returns every instance to shared rows. Enables the linear family of every
-        non-empty side, as set_linear_constraints does, and keeps the ADMM state: re-send the rows between two mpc_step() ticks."""
+        non-empty side, as set_linear_constraints does, and keeps the ADMM state: re-send the rows between two mpc_step() ticks.
+        Runs on layout A -- or, after prepare(), on layout D's per-instance linear-row form (nx+nu <= 16, N <= 22, bounds constant over
+        the horizon, cones that share no row), with references that are constant over the horizon or per-instance trajectories / tracks
+        (set_x_ref_batch, the track verbs: the form then reads every wavefront's own reference rows); a trajectory shared by the batch
+        through set_x_ref() / set_u_ref() keeps the mode on layout A."""
         self._check_setup()
         sides = []
         for A, b, cols, name in ((Alin_x, blin_x, self.nx, "x"), (Alin_u, blin_u, self.nu, "u")):
@@ -469,9 +473,11 @@ class TinyMPC:
         whole batch, later calls may replace a sub-range; set_linear_constraints() returns every instance to shared rows, a whole-batch
         set_linear_constraints_batch() to rows constant over the horizon. Enables the linear family of every non-empty side and keeps the
         ADMM state: re-send the shifted rows between two mpc_step() ticks. Batched solvers only. Runs on layout A -- or, after prepare()
-        (before or after this call), on the per-knot variant of layout D's per-instance linear-row form: nx+nu <= 16, references and
-        bounds constant over the horizon, cones that share no row, and a horizon and row count whose rows of all knots fit a wavefront's
-        share of the LDS (one row per side up to N = 22, two up to N = 12, three up to N = 8); launch_info()["layout"] and jit_info()
+        (before or after this call), on the per-knot variant of layout D's per-instance linear-row form: nx+nu <= 16, bounds constant
+        over the horizon, references constant over the horizon or per-instance trajectories / tracks (a trajectory shared by the batch
+        through set_x_ref() keeps layout A), cones that share no row, and a horizon and row count whose rows of all knots fit a wavefront's
+        share of the LDS (one row per side up to N = 22, two up to N = 12, three up to N = 8; beside per-instance trajectories or tracks,
+        whose N+2 reference rows share that space: N = 17, 10, 7 for the quadrotor); launch_info()["layout"] and jit_info()
         (" per-knot-linear", with "refused(...)" in front after a refused plan) say which."""
         self._check_setup()
         sides = []
@@ -822,7 +828,11 @@ class TinyMPC:
         (set_cone_slopes_batch) are the other half of that mode and run on the same form, whose cone slope is always the instance's;
         cones that share rows stay on layout A. Per-instance reference trajectories and tracks (set_x_ref_batch / set_u_ref_batch with
         a trajectory per instance, set_x_ref_track_batch / set_u_ref_track_batch; before or after this call) run on layout D's
-        per-instance trajectory form under the same conditions on shape and bounds, with the shared model and no constraint families."""
+        per-instance trajectory form under the same conditions on shape and bounds, with the shared model and no constraint families.
+        Both together -- per-instance rows, rows per knot or cone slopes on per-instance trajectories or tracks -- run on the linear-row
+        form that reads every wavefront's own reference rows (jit_info(): "... per-instance-linear per-instance-trajectories"), where rows
+        and reference rows fit a wavefront's LDS share together; a trajectory shared by the batch through set_x_ref() / set_u_ref() is not
+        one of these and keeps the mode on layout A -- send it through set_x_ref_batch() to stay on layout D."""
         self._check_setup()
         self._push_settings()
         _lib.check(self._L.tinympc_prepare(self._h))
