@@ -231,7 +231,10 @@ int tinympc_set_x0_batch_device(tinympc_solver *s, const double *d_x0s, int firs
  * trajectory form: where the handle runs layout D with nx+nu <= 16, bounds are constant over the horizon (shared or per instance), the
  * model and rho are the shared ones, and the horizon's N+2 reference rows fit a wavefront's share of LDS beside its other state (the
  * plan's arithmetic decides; for the quadrotor, nu = 4, that is a horizon of about 60 -- N = 50 is compiled in, other shapes are
- * specialised at run time). Whatever misses a condition stays on layout A; tinympc_get_layout and tinympc_get_jit_info
+ * specialised at run time). With bounds that vary over the horizon -- per instance (tinympc_set_bound_constraints_batch with cols = N)
+ * or shared -- the form also holds the wavefront's 2 (N+2) clamp rows (" per-knot-bounds" beside " per-instance-trajectories"; box
+ * path only; quadrotor: N <= 22, N = 20 compiled in; " per-knot-bounds(no plan)" and layout A beyond). Whatever misses a condition
+ * stays on layout A; tinympc_get_layout and tinympc_get_jit_info
  * (" per-instance-trajectories", or "refused(...)" with the reason) say which ran. Inside the per-instance families mode
  * (tinympc_set_linear_constraints_batch, _knots_batch, tinympc_set_cone_slopes_batch) trajectories sent through THESE verbs keep a
  * prepared handle on layout D as well (see there); a trajectory shared by the batch that arrives through tinympc_set_x_ref /
@@ -258,7 +261,7 @@ int tinympc_set_u_ref_batch_device(tinympc_solver *s, const double *d_Urefs, int
  * replace a sub-range with the same T, a whole-batch call may change T; replacing a track does not touch the steps. A half in track
  * mode IS a half with per-instance trajectories: it turns per-instance references on for that half, runs on layout A (even with
  * T = 1: never layout D's goal form) -- or, after tinympc_prepare and under tinympc_set_x_ref_batch's conditions, on layout D's
- * per-instance trajectory form, or, inside the per-instance families mode, on that mode's form for trajectories
+ * per-instance trajectory form (with bounds per knot: on its per-knot bounds form, see there), or, inside the per-instance families mode, on that mode's form for trajectories
  * (tinympc_set_linear_constraints_batch; tinympc_mpc_step_batch with auto-advance included: the rows are rebuilt per tick as on layout A,
  * and the kernel stages the rebuilt rows) --,
  * " reference-track" is appended to tinympc_get_jit_info, and every refusal of per-instance
@@ -302,7 +305,13 @@ int tinympc_get_ref_step_batch(tinympc_solver *s, int *steps_out, int first, int
  * per-instance mode on; instances outside the range keep the handle's shared bounds of that moment. A later
  * tinympc_set_bound_constraints returns every instance to shared bounds. reset_workspace, update_settings, the reference verbs, the
  * solve verbs and mpc_step_batch keep them. Boxes (with references constant over the horizon) run on layout D where the handle runs
- * layout D, everything else on layout A; with the cone / linear families, adaptive rho or nx+nu > 64 a solve returns
+ * layout D. Bounds per knot run on layout A -- or, on a handle that called tinympc_prepare and runs layout D with nx+nu <= 16, on layout
+ * D's per-knot bounds form: box path, the shared model and rho, every reference half constant over the horizon (shared or per instance)
+ * or a per-instance trajectory / track, and a horizon whose 2 (N+2) clamp rows (3 (N+2) rows beside trajectories) fit a wavefront's
+ * LDS share (quadrotor: N <= 33, N <= 22 beside trajectories; tinympc_get_jit_info says " per-knot-bounds", or " per-knot-bounds(no
+ * plan)" where the horizon does not fit). What stays on layout A with bounds per knot: no tinympc_prepare, a trajectory shared by the
+ * batch through tinympc_set_x_ref / _set_u_ref, per-instance models or rho, per-instance linear rows or cone slopes, wider systems,
+ * longer horizons. With the cone / linear families, adaptive rho or nx+nu > 64 a solve returns
  * TINYMPC_ERR_UNSUPPORTED (never a solve with the shared bounds). Invalid arguments return TINYMPC_ERR_INVALID_INPUT and leave the mode
  * as it was. Single-instance handles: the same as tinympc_set_bound_constraints. The input has been copied when the call returns. */
 int tinympc_set_bound_constraints_batch(tinympc_solver *s, const double *x_min, const double *x_max,
@@ -622,8 +631,10 @@ int tinympc_get_jit_info(tinympc_solver *s, char *buf, int len);
  * cone / linear families, no adaptive rho, a horizon whose reference rows fit a wavefront's LDS share; and a batch with BOTH
  * per-instance linear rows (or rows per knot, or cone slopes) and per-instance trajectories or tracks on the linear-row form that reads
  * every wavefront's own reference rows, where rows and references fit the wavefront's LDS share together (a trajectory shared by the
- * batch through tinympc_set_x_ref / _set_u_ref is not one of these: layout A); otherwise layout A as without
- * this call. No reference
+ * batch through tinympc_set_x_ref / _set_u_ref is not one of these: layout A); and a batch with box bounds per knot and per instance
+ * (tinympc_set_bound_constraints_batch with cols = N, in either order), or with shared per-knot bounds beside per-instance trajectories
+ * or tracks, on layout D's per-knot bounds form under the same conditions, where the clamp rows fit the wavefront's LDS share too;
+ * otherwise layout A as without this call. No reference
  * counterpart (the reference has one code path). */
 int tinympc_prepare(tinympc_solver *s);
 

@@ -510,7 +510,7 @@ bool solve_e_supported(int nx, int nu, int N, bool const_tables, bool families, 
 hipError_t launch_solve_e(const SolveParams &p, const FamilyStructure &fs, hipStream_t stream);
 void solve_e_describe(int nx, int nu, int N, bool const_tables, bool families, const FamilyStructure &fs, char *buf, size_t len);
 void solve_jit_describe(int W, int nx, int nu, int N, bool const_tables, bool families, bool adaptive, char *buf, size_t len, bool goal = false,
-                        bool models = false, int ilin = 0, bool icone = false, int knots = 0, bool traj = false);
+                        bool models = false, int ilin = 0, bool icone = false, int knots = 0, bool traj = false, bool kbnd = false);
 // Layout F (tinympc_solve_f.hip, run-time specialised only): the latency kernel with compile-time shape and structure
 bool solve_f_plan(int nx, int nu, int N, bool const_tables, bool families, const FamilyStructure &fs, int *chunk_len, int *chunks, int *wpg, size_t *lds_bytes);
 bool solve_f_supported(int nx, int nu, int N, bool const_tables, bool families, const FamilyStructure &fs);  // plans AND compiles
@@ -667,16 +667,20 @@ hipError_t launch_solve_m(const SolveParams &p, hipStream_t stream);
 // who want this form send it through the batch verb. The plan holds both per-wavefront terms: the quadrotor at N=20 with one row takes
 // 304 (d) + 192 (rows) + 1,408 (linref rows) of a wavefront's 4,992 doubles (one wavefront per SIMD: the families' registers); with rows
 // per knot it needs 304 + 3,840 + 1,408 and has no plan -- one row per knot fits up to N=17, two up to N=10, three up to N=7.
+// kbnd (with goal; with or without traj): the per-knot bounds form (-DTINY_JIT_IKBND=1: the goal form reading every instance's own clamp rows of
+// every knot, SolveParams::ibnd = layout A's store, lo [groups][N + 2][64] | hi behind them, staged per wavefront; 16 lanes, box path).
 bool solve_jit_supported(int W, int nx, int nu, int N, bool const_tables, bool families = false, bool adaptive = false, bool goal = false,
-                         bool models = false, int ilin = 0, bool icone = false, int knots = 0, bool traj = false);
+                         bool models = false, int ilin = 0, bool icone = false, int knots = 0, bool traj = false, bool kbnd = false);
+// (the plan alone, nothing compiled: does the shape fit a wavefront's LDS share and the registers at all?)
+bool solve_jit_planned(int W, int nx, int nu, int N, bool const_tables, bool families, bool adaptive, bool models, int ilin, int knots, bool traj, bool kbnd);
 hipError_t launch_solve_jit(const SolveParams &p, int W, hipStream_t stream, bool models = false, int ilin = 0, bool icone = false, int knots = 0,
-                            bool traj = false);
+                            bool traj = false, bool kbnd = false);
 bool solve_jit_refill_supported(int W, int nx, int nu, int N, bool const_tables);   // (compiles the slot-refill variant on first use)
 int solve_jit_resident_wavefronts(int W, int nx, int nu, int N, bool const_tables);  // wavefronts of the shape's plan the device holds at once
 int solve_jit_workgroups(int W, int nx, int nu, int N, bool const_tables, int groups, bool families = false, bool adaptive = false, bool goal = false,
-                         bool models = false, int ilin = 0, bool icone = false, int knots = 0, bool traj = false);
+                         bool models = false, int ilin = 0, bool icone = false, int knots = 0, bool traj = false, bool kbnd = false);
 size_t solve_jit_lds_bytes(int W, int nx, int nu, int N, bool const_tables, bool families = false, bool adaptive = false, bool goal = false,
-                           bool models = false, int ilin = 0, bool icone = false, int knots = 0, bool traj = false);  // per workgroup, from the plan  // 8 wavefronts per workgroup, 4 on the long-horizon plan
+                           bool models = false, int ilin = 0, bool icone = false, int knots = 0, bool traj = false, bool kbnd = false);  // per workgroup, from the plan  // 8 wavefronts per workgroup, 4 on the long-horizon plan
 #endif  // !__HIPCC_RTC__
 
 // Doubles of working state per group in layout A (G and V with N+2 rows, D with 64 dummy slots).

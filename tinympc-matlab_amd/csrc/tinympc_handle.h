@@ -66,6 +66,14 @@ struct InstState {
     // called tinympc_prepare, bounds constant over the horizon): -1 not asked yet, 0 no (the horizon's rows do not fit a wavefront's LDS
     // share, or the specialiser refused: the mode stays on layout A), 1 yes
     int d_traj = -1;
+    // layout D's per-knot bounds form (IKBND, with ITRAJ where a reference half is a per-instance trajectory or track: 16 lanes, compiled in or
+    // run-time specialised; bounds that vary over the horizon on a handle that called tinympc_prepare): -1 not asked yet, 0 no (the
+    // specialiser refused), 1 yes, 2 no plan (the horizon's clamp rows do not fit a wavefront's LDS share: the mode stays on layout A and
+    // nothing was refused). The answer is the one for d_kbnd_traj, the ITRAJ variant it was asked for.
+    int d_kbnd = -1;
+    bool d_kbnd_traj = false;
+    // ... the form reads layout A's clamp rows (bnd): from its first launch on they are built in every mode, from the shared bounds too
+    bool bnd_always = false;
     // every instance's value, column-major [batch] blocks of nx x N (Xi, xmin, xmax) / nu x (N-1) (Ui, umin, umax)
     double *Xi = nullptr, *Ui = nullptr, *xmin = nullptr, *xmax = nullptr, *umin = nullptr, *umax = nullptr;
     double *lr = nullptr, *pn = nullptr;     // linref rows (inst_lr_doubles), pNref [instance][W]
@@ -402,6 +410,7 @@ struct LaunchPlan {
     bool inst_bounds = false;                // ... per-instance bounds (layout A's InstBounds variant)
     bool inst_models = false;                // ... per-instance models (layout A's InstModels variant; inst_refs and inst_bounds are set with it)
     bool inst_lin = false;                   // ... per-instance linear rows (layout A's InstFamilies variant, or layout D's ILIN form: D_JIT; inst_refs and inst_bounds are set with it)
+    bool inst_kbnd = false;                  // ... bounds per knot on layout D's IKBND form (D_JIT; inst_refs is set with it; inst_traj beside it: IKBND with ITRAJ)
     bool inst_traj = false;                  // ... per-instance trajectories / tracks on layout D's ITRAJ form (D_JIT; inst_refs is set with it; beside inst_lin: the families' form on them)
     bool jit = false;                        // a run-time specialisation (tinympc_jit.hip) rather than a compiled-in kernel
     bool host_exchange = false;              // the kernel serves the pinned-host paths (x0 in, solution / completion stamp out)

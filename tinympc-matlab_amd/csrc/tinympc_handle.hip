@@ -358,7 +358,8 @@ int refresh_inst_tables(tinympc_solver *s) {
     p.x_min = in.bounds ? in.xmin : s->dxmin; p.x_max = in.bounds ? in.xmax : s->dxmax;
     p.u_min = in.bounds ? in.umin : s->dumin; p.u_max = in.bounds ? in.umax : s->dumax;
     p.lr = const_cast<double *>(in.lr_rows()); p.pn = in.pn; p.lrg = in.lrg; p.bndg = in.bndg;
-    p.bnd = (in.bounds || in.models || in.fam()) ? in.bnd : nullptr;  // (the models' and the linear rows' kernels always read per-instance clamp rows: shared bounds are copied)
+    // (the models' and the linear rows' kernels, and layout D's per-knot bounds form, always read per-instance clamp rows: shared bounds are copied)
+    p.bnd = (in.bounds || in.models || in.fam() || in.bnd_always) ? in.bnd : nullptr;
     HIP_TRY(launch_build_inst_tables(p, s->stream));
     in.dirty_lo = in.dirty_hi = 0;
     return TINYMPC_OK;

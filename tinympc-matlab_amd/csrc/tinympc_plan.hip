@@ -174,6 +174,22 @@ bool traj_wants_d(const tinympc_solver *s) {
            !s->st.adaptive_rho;
 }
 
+// Box bounds that vary over the horizon on layout D: opt-in like the trajectory form (tinympc_prepare), where the handle runs layout D, 16
+// lanes per instance, box path, the shared model and rho, and the bounds are per instance and per knot (tinympc_set_bound_constraints_batch
+// with a column per knot) or shared per-knot bounds beside per-instance trajectories / tracks. Every reference half is constant over the
+// horizon (shared or per instance) or a per-instance trajectory / track (kbnd_traj: the form then has ITRAJ beside IKBND) -- a SHARED
+// trajectory, tinympc_set_x_ref / _set_u_ref, keeps the mode on layout A. Whether the kernel exists -- the horizon's clamp rows fit a
+// wavefront's LDS share -- is inst.d_kbnd for the variant inst.d_kbnd_traj (resolve_plan).
+bool kbnd_traj(const tinympc_solver *s) { return (s->inst.x && !s->inst.x_const) || (s->inst.u && !s->inst.u_const); }
+bool kbnd_wants_d(const tinympc_solver *s) {
+    const InstState &in = s->inst;
+    const bool shared_const = s->xmin_const && s->xmax_const && s->umin_const && s->umax_const;
+    const bool per_knot = in.bounds ? !in.bounds_const : !shared_const && kbnd_traj(s);
+    return per_knot && (in.x || s->xref_const) && (in.u || s->uref_const) && !in.models && !in.fam() && s->specialise_asked && s->layout_d && !s->layout_m && s->W == 16 &&
+           !s->families_active() && !s->st.adaptive_rho;
+}
+bool kbnd_on_d(const tinympc_solver *s) { return kbnd_wants_d(s) && s->inst.d_kbnd == 1 && s->inst.d_kbnd_traj == kbnd_traj(s); }
+
 // Per-instance linear rows (tinympc_set_linear_constraints_batch): layout A's InstFamilies variant, or layout D's ILIN form (below). What
 // neither can carry is refused at the launch (lin_refusal), never solved with shared rows.
 bool lin_runs(const tinympc_solver *s) {
@@ -217,6 +233,10 @@ namespace host {
 //   per-instance models                D's model form (only after tinympc_prepare: 16 lanes, references and bounds constant over the horizon,
 //                                      a horizon its per-wavefront operator plan holds)  >  A (the same refusals)
 //                                      (the mode of tinympc_set_model_batch AND tinympc_set_rho_batch: one form, rho always read per instance)
+//   bounds per knot, per instance      D's IKBND form (only after tinympc_prepare: 16 lanes, box path, shared model and rho; bounds per instance and
+//                                      knot, or shared per-knot bounds beside per-instance trajectories / tracks; every reference half constant
+//                                      or a per-instance trajectory / track -- then IKBND with ITRAJ; a horizon whose clamp rows its
+//                                      per-wavefront plan holds: quadrotor N <= 33, N <= 22 beside trajectories)  >  A's InstBounds variant
 //   per-instance linear rows           D's ILIN form (only after tinympc_prepare: 16 lanes, bounds constant over the horizon, every reference half
 //                                      constant over the horizon or a per-instance trajectory / track -- then ILIN with ITRAJ, the wavefront's
 //                                      own linref rows behind its linear rows; a SHARED trajectory stays on layout A --, cones
@@ -245,8 +265,12 @@ LaunchPlan current_plan(const tinympc_solver *s) {
         // trajectories and tracks: layout A's InstRefs / InstBounds variants, or -- under the same opt-in -- layout D's trajectory form (the
         // goal form with every wavefront's own linref rows in its LDS region: KernelId::D_JIT)
         pl.inst_traj = !goal && traj_wants_d(s) && s->inst.d_traj == 1;
+        // bounds per knot: layout A's InstBounds variant (or its shared tables), or -- under the same opt-in -- layout D's per-knot bounds form
+        // (the goal form with every wavefront's own clamp rows in its LDS region, and its linref rows beside trajectories: KernelId::D_JIT)
+        pl.inst_kbnd = !goal && kbnd_on_d(s);
+        if (pl.inst_kbnd) pl.inst_traj = kbnd_traj(s);
         pl.kernel = (goal && !s->d_jit && s->W == 16 && solve_d_supported(s->nx, s->nu, s->N, true)) ? KernelId::D_COMPILED
-                    : ((goal && s->inst.d_goal == 1) || d_models || pl.inst_traj) ? KernelId::D_JIT : KernelId::A;
+                    : ((goal && s->inst.d_goal == 1) || d_models || pl.inst_traj || pl.inst_kbnd) ? KernelId::D_JIT : KernelId::A;
         pl.inst_refs = true;
         pl.inst_models = s->inst.models;
         pl.inst_bounds = s->inst.bounds || pl.inst_models;  // (the models' variant always runs on per-instance clamp rows)
@@ -271,9 +295,9 @@ LaunchPlan current_plan(const tinympc_solver *s) {
             pl.jit = true;
             const int ilin = pl.inst_lin ? s->ifam_nl() : 0;  // (the ILIN form: the families' kernel whichever sides are enabled)
             pl.workgroups = solve_jit_workgroups(s->W, s->nx, s->nu, s->N, ct, s->groups, fam || ilin, adaptive, pl.inst_refs, pl.inst_models, ilin, ilin && s->inst.cones,
-                                                 ilin ? lin_d_knots(s) : 0, pl.inst_traj);
+                                                 ilin ? lin_d_knots(s) : 0, pl.inst_traj, pl.inst_kbnd);
             pl.lds_bytes = solve_jit_lds_bytes(s->W, s->nx, s->nu, s->N, ct, fam || ilin, adaptive, pl.inst_refs, pl.inst_models, ilin, ilin && s->inst.cones, ilin ? lin_d_knots(s) : 0,
-                                               pl.inst_traj);
+                                               pl.inst_traj, pl.inst_kbnd);
             break;
         }
         case KernelId::D_COMPILED:
@@ -336,6 +360,23 @@ int resolve_plan(tinympc_solver *s) {
         // a refusal, leaves trajectories and tracks on layout A)
         if (s->inst.d_traj < 0 && traj_wants_d(s))
             s->inst.d_traj = solve_jit_supported(s->W, s->nx, s->nu, s->N, true, false, false, true, false, 0, false, 0, true) ? 1 : 0;
+        // ... and the per-knot bounds form's, for the mode's ITRAJ variant (compiled in for the quadrotor N=20 with trajectories, specialised now
+        // otherwise). A horizon whose rows fit no plan is no refusal (2); the other variant is another specialisation: asked again.
+        if (kbnd_wants_d(s)) {
+            InstState &in = s->inst;
+            const bool tr = kbnd_traj(s);
+            if (in.d_kbnd >= 0 && in.d_kbnd_traj != tr) in.d_kbnd = -1;
+            if (in.d_kbnd < 0) {
+                in.d_kbnd_traj = tr;
+                in.d_kbnd = !solve_jit_planned(s->W, s->nx, s->nu, s->N, true, false, false, false, 0, 0, tr, true) ? 2
+                            : solve_jit_supported(s->W, s->nx, s->nu, s->N, true, false, false, true, false, 0, false, 0, tr, true) ? 1 : 0;
+            }
+            if (in.d_kbnd == 1 && !in.bnd_always) {  // (the form reads layout A's clamp rows whether the bounds are per instance or shared)
+                if ((rc = alloc_inst_rows(s, true))) return rc;
+                in.bnd_always = true;
+                in.mark(0, s->batch);
+            }
+        }
         // ... and the linear-row form's, for the mode's row count (compiled in for the quadrotor N=20 with one row, specialised now
         // otherwise; a refusal leaves the mode on layout A). Another count is another specialisation: asked again -- and so is the other
         // of rows constant over the horizon and rows per knot (compiled in for the same quadrotor with one row).
@@ -567,7 +608,8 @@ int launch(tinympc_solver *s, bool timed) {
         // (layout A and layout D's trajectory form: the rows of every knot; the goal form: knot 0's)
         p.iref_lr = (pl.kernel == KernelId::A || pl.inst_traj) ? s->inst.lr_rows() : s->inst.lrg;
         p.iref_pn = s->inst.pn;
-        if (pl.kernel != KernelId::A) p.ibnd = s->inst.bndg;  // (the goal form: always per lane)
+        if (pl.inst_kbnd) p.ibnd = s->inst.bnd;  // (layout D's per-knot bounds form: layout A's clamp rows, every knot's)
+        else if (pl.kernel != KernelId::A) p.ibnd = s->inst.bndg;  // (the goal form: always per lane)
         else if (pl.inst_bounds) p.ibnd = s->inst.bnd;
     }
     p.rho_min = s->st.adaptive_rho_min; p.rho_max = s->st.adaptive_rho_max; p.rho_clip = s->st.adaptive_rho_enable_clipping;
@@ -592,7 +634,7 @@ int launch(tinympc_solver *s, bool timed) {
             break;
         case KernelId::D_JIT:  // (box path, families with everything in registers, or adaptive rho per lane)
             HIP_TRY(launch_solve_jit(p, s->W, s->stream, pl.inst_models, pl.inst_lin ? s->ifam_nl() : 0, pl.inst_lin && s->inst.cones, pl.inst_lin ? lin_d_knots(s) : 0,
-                                     pl.inst_traj));
+                                     pl.inst_traj, pl.inst_kbnd));
             break;
         case KernelId::D_COMPILED:
             if (lean_applies(s, pl) && !p.x0_mirror && !p.u0_host && !p.refill_next)
@@ -692,7 +734,15 @@ static int jit_info_text(tinympc_solver *s, char *buf, int len) {
         const std::string w = std::string(s->inst.refs() ? " per-instance-refs" : "") + (s->inst.bounds ? " per-instance-bounds" : "") +
                               (pl.inst_models ? " per-instance-models" : "");
         const char *words = w.c_str();
-        if (pl.kernel == KernelId::D_JIT && pl.inst_traj && !pl.inst_lin) {  // layout D's trajectory form (box path)
+        if (!pl.inst_lin && !pl.inst_models && (pl.inst_kbnd || (pl.kernel == KernelId::A && kbnd_wants_d(s) && s->inst.d_kbnd == 0 && s->inst.d_kbnd_traj == kbnd_traj(s)))) {
+            // layout D's per-knot bounds form -- or asked for and refused (a plan, but no kernel): layout A, and why
+            if ((rc = bind_device(s))) return rc;
+            const bool tr = kbnd_traj(s);
+            solve_jit_describe(s->W, s->nx, s->nu, s->N, true, false, false, buf, (size_t)len, true, false, 0, false, 0, tr, true);
+            strncat(buf, words, (size_t)len - strlen(buf) - 1);
+            if (tr) strncat(buf, " per-instance-trajectories", (size_t)len - strlen(buf) - 1);
+            strncat(buf, " per-knot-bounds", (size_t)len - strlen(buf) - 1);
+        } else if (pl.kernel == KernelId::D_JIT && pl.inst_traj && !pl.inst_lin) {  // layout D's trajectory form (box path)
             if ((rc = bind_device(s))) return rc;
             solve_jit_describe(s->W, s->nx, s->nu, s->N, true, false, false, buf, (size_t)len, true, false, 0, false, 0, true);
             strncat(buf, words, (size_t)len - strlen(buf) - 1);
@@ -724,6 +774,9 @@ static int jit_info_text(tinympc_solver *s, char *buf, int len) {
         } else {
             snprintf(buf, (size_t)len, "compiled-in layout=%c%s%s%s", pl.layout, words, pl.kernel == KernelId::D_COMPILED ? " goal" : "",
                      lean_words(s, pl));
+            // (the per-knot bounds form was asked for and the horizon's clamp rows fit no plan: layout A, nothing was refused)
+            if (pl.kernel == KernelId::A && kbnd_wants_d(s) && s->inst.d_kbnd == 2 && s->inst.d_kbnd_traj == kbnd_traj(s))
+                strncat(buf, " per-knot-bounds(no plan)", (size_t)len - strlen(buf) - 1);
         }
         return TINYMPC_OK;
     }

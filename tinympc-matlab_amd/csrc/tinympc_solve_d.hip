@@ -277,14 +277,17 @@ constexpr int D_IMOD_WAVE_DOUBLES = 4 * D_IMOD_STRIDE;
 __host__ __device__ constexpr int d_ilin_wave_doubles(int ilin, int knots) { return 3 * ilin * 64 * (knots > 0 ? knots : 1); }
 // (itraj: the per-instance trajectory form -- the wavefront's own linref rows, table_rows(N) = N + 2 vectors of 64 doubles, SolveParams::iref_lr's block)
 __host__ __device__ constexpr int d_itraj_wave_doubles(bool itraj, int N) { return itraj ? (N + 2) * 64 : 0; }
+// (ikbnd: the per-knot bounds form -- the wavefront's own clamp rows, lo and hi, 2 (N + 2) vectors of 64 doubles, SolveParams::ibnd's two blocks)
+__host__ __device__ constexpr int d_ikbnd_wave_doubles(bool ikbnd, int N) { return ikbnd ? 2 * (N + 2) * 64 : 0; }
 __host__ __device__ constexpr int d_vl(int nu, int N, bool ct, int wpg, int cu_waves = 8, bool fam = false, bool adapt = false, bool imod = false, int ilin = 0,
-                                       int knots = 0, bool itraj = false) {
+                                       int knots = 0, bool itraj = false, bool ikbnd = false) {
     const int ns = N - 1;
     const int wg_doubles = D_LDS_PER_CU / 8 * wpg / cu_waves - (imod ? 0 : D_OPS_DOUBLES + D_START_DOUBLES) - (ct ? 0 : d_tab_doubles(N)) - (fam && !ilin ? D_FAM_DOUBLES : 0) - (adapt ? D_ADAPT_DOUBLES : 0);
 #if TINY_TRIM_DSTORE
     const int wave_doubles = wg_doubles / wpg - d_d_doubles(nu, N) - D_DUMP_DOUBLES(nu) - (imod ? D_IMOD_WAVE_DOUBLES : 0);
 #else
-    const int wave_doubles = wg_doubles / wpg - d_d_doubles(nu, N) - (imod ? D_IMOD_WAVE_DOUBLES : 0) - d_ilin_wave_doubles(ilin, knots) - d_itraj_wave_doubles(itraj, N);
+    const int wave_doubles = wg_doubles / wpg - d_d_doubles(nu, N) - (imod ? D_IMOD_WAVE_DOUBLES : 0) - d_ilin_wave_doubles(ilin, knots) - d_itraj_wave_doubles(itraj, N) -
+                             d_ikbnd_wave_doubles(ikbnd, N);
 #endif
     if (wave_doubles < 0) return -1;
     const int vlmax = wave_doubles / 64;
@@ -292,12 +295,13 @@ __host__ __device__ constexpr int d_vl(int nu, int N, bool ct, int wpg, int cu_w
     return want <= vlmax ? want : -1;
 }
 __host__ __device__ constexpr size_t d_lds_bytes(int nu, int N, bool ct, int wpg, int vl, bool fam = false, bool adapt = false, bool imod = false, int ilin = 0,
-                                                 int knots = 0, bool itraj = false) {
+                                                 int knots = 0, bool itraj = false, bool ikbnd = false) {
     return sizeof(double) * ((size_t)(imod ? 0 : D_OPS_DOUBLES + D_START_DOUBLES) + (ct ? 0 : d_tab_doubles(N)) + (fam && !ilin ? D_FAM_DOUBLES : 0) + (adapt ? D_ADAPT_DOUBLES : 0) +
 #if TINY_TRIM_DSTORE
                              (size_t)wpg * (vl * 64 + D_DUMP_DOUBLES(nu) + d_d_doubles(nu, N) + (imod ? D_IMOD_WAVE_DOUBLES : 0)));
 #else
-                             (size_t)wpg * (vl * 64 + d_d_doubles(nu, N) + (imod ? D_IMOD_WAVE_DOUBLES : 0) + d_ilin_wave_doubles(ilin, knots) + d_itraj_wave_doubles(itraj, N)));
+                             (size_t)wpg * (vl * 64 + d_d_doubles(nu, N) + (imod ? D_IMOD_WAVE_DOUBLES : 0) + d_ilin_wave_doubles(ilin, knots) + d_itraj_wave_doubles(itraj, N) +
+                                            d_ikbnd_wave_doubles(ikbnd, N)));
 #endif
 }
 
@@ -397,7 +401,7 @@ __device__ __forceinline__ bool wave_may_converge_d32(unsigned long long bad, un
 // arithmetic of an instance is that of the plain kernel (bit-identical results: tests/test_hip_parity.py); what changes is that
 // a wavefront's time is the sum of what its rows worked, not four times its slowest instance.
 template <int NX, int NU, int N, bool CT, int WPG, int VL, bool FAM = false, bool ADAPT = false, bool TWO_PER_SIMD = true, bool HOSTX = false,
-          bool REFILL = false, bool IGOAL = false, bool IMOD = false, int ILIN = 0, bool ICONE = false, bool IKNOT = false, bool ITRAJ = false>
+          bool REFILL = false, bool IGOAL = false, bool IMOD = false, int ILIN = 0, bool ICONE = false, bool IKNOT = false, bool ITRAJ = false, bool IKBND = false>
 #else
 // IGOAL: the per-instance goal form (every instance's references and bounds constant over the horizon; k_admm_solve_d_gbnd) -- the
 // four table constants lr_c, pNref, lo_c and hi_c come per lane from SolveParams::iref_lr / iref_pn / ibnd ([instance][16], ibnd's hi
@@ -422,8 +426,15 @@ template <int NX, int NU, int N, bool CT, int WPG, int VL, bool FAM = false, boo
 // stay the goal form's (constant over the horizon, per lane). FOLD needs references constant over the horizon: off.
 // ITRAJ with ILIN (ICONE and IKNOT as they are): the per-instance families on per-instance trajectories -- both blocks are staged, the
 // trajectory rows behind the linear rows, and every linref of the backward sweep is the row's read plus the families' LX of its slot.
+// IKBND (with IGOAL, box path; with or without ITRAJ): box bounds per knot AND per instance (tinympc_set_bound_constraints_batch with one
+// column per knot after tinympc_prepare, or shared per-knot bounds beside per-instance trajectories) -- SolveParams::ibnd is layout A's
+// store, lo [group][N + 2][64] | hi [group][N + 2][64] in this kernel's lane order (k_build_inst_tables: row k + 1 = knot k), and the
+// wavefront stages its group's two blocks, verbatim, into an LDS region of its own (behind its linref rows where the form has both). The
+// forward sweep reads the clamp of slot q there, the rows the shared !CT form reads in the workgroup's table, one step ahead like d; knot
+// 0's clamp is row 1. References, pNref and (without ITRAJ) lr_c stay the goal form's. FOLD is off, as in the shared !CT form: the
+// arithmetic of an instance is that form's, bit for bit.
 template <int NX, int NU, int N, bool CT, int WPG, int VL, bool FAM = false, bool ADAPT = false, bool TWO_PER_SIMD = true, bool HOSTX = false,
-          bool REFILL = false, bool IGOAL = false, bool IMOD = false, int ILIN = 0, bool ICONE = false, bool IKNOT = false, bool ITRAJ = false>
+          bool REFILL = false, bool IGOAL = false, bool IMOD = false, int ILIN = 0, bool ICONE = false, bool IKNOT = false, bool ITRAJ = false, bool IKBND = false>
 #endif
 __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double *smem) {
     static_assert(!(FAM && ADAPT), "adaptive rho and the constraint families exclude each other (as in the C ABI)");
@@ -433,6 +444,8 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
     static_assert(!IKNOT || ILIN > 0, "rows per knot: a form of the per-instance rows");
     static_assert(!ITRAJ || (IGOAL && CT && FAM == (ILIN > 0) && !ADAPT && !IMOD && !REFILL && !HOSTX && !TINY_LEAN),
                   "per-instance trajectories: the goal form of the box path, or of the per-instance families (bounds constant over the horizon), plain sweeps");
+    static_assert(!IKBND || (IGOAL && CT && !FAM && ILIN == 0 && !ADAPT && !IMOD && !REFILL && !HOSTX && !TINY_LEAN),
+                  "per-knot bounds per instance: the goal form of the box path (references constant over the horizon or per-instance trajectories), plain sweeps");
     static_assert(ILIN == 0 || (ILIN > 0 && ILIN <= MAX_LIN_ROWS && FAM && IGOAL && CT && !ADAPT && !IMOD && !REFILL && !HOSTX && !TINY_LEAN),
                   "per-instance linear rows: the families' variant in the goal form (references and bounds constant over the horizon), plain sweeps");
 #if TINY_REFILL
@@ -451,7 +464,7 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
     // into a sweep). FOLD (references constant over the horizon as well): the backward step's input-row operand r_s = -rho * t + lr_c
     // is not formed; the operator's input columns carry -rho and the accumulator starts carry Mb[:, nx:] * lr_c instead (Step::bwd_fold).
     constexpr bool K0 = !FAM && !ADAPT && !REFILL;
-    constexpr bool FOLD = !FAM && !ADAPT && CT && !ITRAJ;
+    constexpr bool FOLD = !FAM && !ADAPT && CT && !ITRAJ && !IKBND;
 
 #ifdef TINY_CLOCK_STAMP
     const unsigned long long ck_entry = __builtin_amdgcn_s_memrealtime();
@@ -483,15 +496,21 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
     double *sD = sV + VL * 64 + D_DUMP_DOUBLES(NU);  // (rows -1 and -2 of d: written by the dump lanes of the lean backward sweeps, never read)
 #else
     double *sV = sAd + (ADAPT ? D_ADAPT_DOUBLES : 0) + (size_t)wv * (VL * 64 + d_d_doubles(NU, N) + (IMOD ? D_IMOD_WAVE_DOUBLES : 0) + d_ilin_wave_doubles(ILIN, IKNOT ? N : 0) +
-                                                                       d_itraj_wave_doubles(ITRAJ, N));
+                                                                       d_itraj_wave_doubles(ITRAJ, N) + d_ikbnd_wave_doubles(IKBND, N));
     double *sD = sV + VL * 64;
 #endif
     double *sOpsW = sD + d_d_doubles(NU, N);  // IMOD: [4 instances][D_IMOD_STRIDE]
     double *sLinW = sD + d_d_doubles(NU, N);  // ILIN: [3 nl][64], this wavefront's group of SolveParams::ilin (never together with IMOD); IKNOT: [N slots][3 nl][64]
     // ITRAJ: [N + 2][64], this wavefront's group of SolveParams::iref_lr (never together with IMOD), behind the wavefront's linear rows where the form has both
     double *sRefW = sLinW + d_ilin_wave_doubles(ILIN, IKNOT ? N : 0);
-    static_assert(!ITRAJ || sizeof(double) * (D_OPS_DOUBLES + D_START_DOUBLES + VL * 64 + d_d_doubles(NU, N) + d_ilin_wave_doubles(ILIN, IKNOT ? N : 0) + d_itraj_wave_doubles(true, N)) < 65536,
+    static_assert(!ITRAJ || sizeof(double) * (D_OPS_DOUBLES + D_START_DOUBLES + VL * 64 + d_d_doubles(NU, N) + d_ilin_wave_doubles(ILIN, IKNOT ? N : 0) + d_itraj_wave_doubles(true, N) +
+                                              d_ikbnd_wave_doubles(IKBND, N)) < 65536,
                   "per-instance trajectories: the last row's reads stay below the 16-bit ds offset field, whatever constant part of the address the compiler folds in");
+    // IKBND: lo [N + 2][64] | hi [N + 2][64], this wavefront's group of SolveParams::ibnd's two blocks, behind the wavefront's linref rows where the form has both
+    double *sBndW = sRefW + d_itraj_wave_doubles(ITRAJ, N);
+    constexpr int BHI = (N + 2) * 64;  // (hi lies one block behind lo)
+    static_assert(!IKBND || sizeof(double) * (D_OPS_DOUBLES + D_START_DOUBLES + VL * 64 + d_d_doubles(NU, N) + d_itraj_wave_doubles(ITRAJ, N) + d_ikbnd_wave_doubles(true, N)) < 65536,
+                  "per-knot bounds: the last row's reads stay below the 16-bit ds offset field, whatever constant part of the address the compiler folds in");
     // (a slot's rows lie LIN_SLOT doubles behind the last slot's: 0 where the rows are constant over the horizon -- one code path)
     constexpr int LIN_SLOT = IKNOT ? 3 * ILIN * 64 : 0;
     static_assert(!IKNOT || sizeof(double) * (D_OPS_DOUBLES + D_START_DOUBLES + VL * 64 + d_d_doubles(NU, N) + d_ilin_wave_doubles(ILIN, N) + d_itraj_wave_doubles(ITRAJ, N)) < 65536,
@@ -535,6 +554,17 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
         if (grp_ok) {
             const double *const rows_g = p.iref_lr + (size_t)grp * d_itraj_wave_doubles(true, N);
             for (int i = lane; i < d_itraj_wave_doubles(true, N); i += 64) sRefW[i] = rows_g[i];
+        }
+    }
+    if constexpr (IKBND) {
+        // ... per wavefront: its group's clamp rows, lo and hi, verbatim (padding rows, lanes beyond the batch or the system's rows, and a
+        // disabled bound family: -inf / +inf)
+        if (grp_ok) {
+            const double *const lo_g = p.ibnd + (size_t)grp * BHI, *const hi_g = lo_g + (size_t)p.groups * BHI;
+            for (int i = lane; i < BHI; i += 64) {
+                sBndW[i] = lo_g[i];
+                sBndW[BHI + i] = hi_g[i];
+            }
         }
     }
     if constexpr (IKNOT) {
@@ -731,8 +761,9 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
     // IMOD: the instance's own rho (tinympc_set_rho_batch; the handle's where the verb never named it) -- a lane variable, constant over the solve
     if constexpr (IMOD) rho = inst_ok ? p.rho_inst[inst] : rho0;
     double nrho = -rho;
-    const double lo_c = IGOAL ? (inst_ok ? p.ibnd[inst * W + r] : 0.0) : p.tables[W + r];
-    const double hi_c = IGOAL ? (inst_ok ? p.ibnd[(size_t)p.groups * 64 + inst * W + r] : 0.0) : p.tables[(size_t)TOFF + W + r];
+    // (IKBND: ibnd is the store of every knot's rows, not [instance][16] -- the form reads its clamps from sBndW and has no lo_c / hi_c)
+    const double lo_c = IKBND ? 0.0 : IGOAL ? (inst_ok ? p.ibnd[inst * W + r] : 0.0) : p.tables[W + r];
+    const double hi_c = IKBND ? 0.0 : IGOAL ? (inst_ok ? p.ibnd[(size_t)p.groups * 64 + inst * W + r] : 0.0) : p.tables[(size_t)TOFF + W + r];
     // (ITRAJ: iref_lr is the store of every knot's rows, not [instance][16] -- the form reads its linref from sRefW and has no lr_c)
     const double lr_c = ITRAJ ? 0.0 : IGOAL ? (inst_ok ? p.iref_lr[inst * W + r] : 0.0) : p.tables[(size_t)2 * TOFF + W + r];
     double rhom = is_x ? nrho : 0.0;
@@ -751,6 +782,7 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
     const double *const sMf = (IMOD ? sOpsW + j * D_IMOD_STRIDE : sOps) + r, *const sMb = sMf + 256;
     const unsigned aV = lds_addr(sVl), aD = lds_addr(sDr), aT = lds_addr(sTl);
     const unsigned aR = ITRAJ ? lds_addr(sRefW + koff * 64 + lane) : 0u;  // (ITRAJ) row of slot s: offset (s + 1) * 512 -- the knot the shared table's sTl reads
+    const unsigned aB = IKBND ? lds_addr(sBndW + koff * 64 + lane) : 0u;  // (IKBND) lo of slot s: offset (s + 1) * 512, hi BHI * 8 behind it
 #if TINY_LDS_START
     const unsigned aC = lds_addr(sStart + r);
 #endif
@@ -1058,7 +1090,14 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
         }
         // ---------------- knot 0, state lanes: x_0 is given (tiny_set_x0), no mat-vec
         {
-            const double lo0 = CT ? lo_c : sT[W + r], hi0 = CT ? hi_c : sT[TOFF + W + r];
+            double lo0, hi0;  // (IKBND: knot 0's row of the wavefront's own block, row 1 -- on every lane, like the shared table's)
+            if constexpr (IKBND) {
+                lo0 = sBndW[64 + lane];
+                hi0 = sBndW[BHI + 64 + lane];
+            } else {
+                lo0 = CT ? lo_c : sT[W + r];
+                hi0 = CT ? hi_c : sT[TOFF + W + r];
+            }
             const double s = x0v + G0;
             const double snew = fmin(hi0, fmax(lo0, s));
 #if TINY_LEAN_HOIST
@@ -1079,7 +1118,7 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
                 // (the test on 32-bit halves: the 64-bit form keeps two 64-bit constants in vector registers across the run)
                 may = __builtin_amdgcn_readfirstlane((int)wave_may_converge_d32(__ballot(bad), __ballot(active))) != 0;
 #else
-                may = __builtin_amdgcn_readfirstlane((int)((ILIN || ITRAJ) ? wave_may_converge_d32(__ballot(bad), __ballot(active)) : wave_may_converge_d(__ballot(bad), __ballot(active)))) != 0;
+                may = __builtin_amdgcn_readfirstlane((int)((ILIN || ITRAJ || IKBND) ? wave_may_converge_d32(__ballot(bad), __ballot(active)) : wave_may_converge_d(__ballot(bad), __ballot(active)))) != 0;
 #endif
             }
 #if TINY_REFILL
@@ -1126,7 +1165,10 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
 #endif
         // (!CT: bounds that vary over the horizon come from the workgroup's LDS copy of the tables, one step ahead like d)
         double locur = lo_c, hicur = hi_c;
-        if constexpr (!CT) {
+        if constexpr (IKBND) {  // (... or from the wavefront's own clamp rows, the same way)
+            locur = lds_read_async<512>(aB);
+            hicur = lds_read_async<(BHI + 64) * 8>(aB);
+        } else if constexpr (!CT) {
             locur = lds_read_async<W * 8>(aT);
             hicur = lds_read_async<(TOFF + W) * 8>(aT);
         }
@@ -1150,7 +1192,12 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
 #else
             if constexpr (q + 1 < VL) vn = lds_read_async<(q + 1) * 512>(aV);
 #endif
-            if constexpr (!CT && q + 1 < NS) {
+            if constexpr (IKBND) {  // (nested: a condition that depends on the step would capture aB in every form's lambda)
+                if constexpr (q + 1 < NS) {
+                    lon = lds_read_async<(q + 2) * 512>(aB);
+                    hin = lds_read_async<(BHI + (q + 2) * 64) * 8>(aB);
+                }
+            } else if constexpr (!CT && q + 1 < NS) {
                 lon = lds_read_async<(q + 2) * W * 8>(aT);
                 hin = lds_read_async<(TOFF + (q + 2) * W) * 8>(aT);
             }
@@ -1245,7 +1292,7 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
 #if TINY_LDS_START
             acur = an;
 #endif
-            if constexpr (!CT) {
+            if constexpr (!CT || IKBND) {
                 locur = lon;
                 hicur = hin;
             }
@@ -1269,7 +1316,7 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
 #elif TINY_LEAN_PARK
                         may = __builtin_amdgcn_readfirstlane((int)wave_may_converge_d32(__ballot(bad), __ballot(active))) != 0;
 #else
-                        may = __builtin_amdgcn_readfirstlane((int)((ILIN || ITRAJ) ? wave_may_converge_d32(__ballot(bad), __ballot(active)) : wave_may_converge_d(__ballot(bad), __ballot(active)))) != 0;
+                        may = __builtin_amdgcn_readfirstlane((int)((ILIN || ITRAJ || IKBND) ? wave_may_converge_d32(__ballot(bad), __ballot(active)) : wave_may_converge_d(__ballot(bad), __ballot(active)))) != 0;
 #endif
                     }
                 }
@@ -1855,6 +1902,9 @@ __global__ void __launch_bounds__(64 * WPG) __attribute__((amdgpu_waves_per_eu(2
 #if TINY_JIT_ILIN && TINY_REFILL
 #error "per-instance linear rows: no slot-refill variant"
 #endif
+#if defined(TINY_JIT_IKBND) && TINY_JIT_IKBND && TINY_REFILL
+#error "per-knot bounds per instance: no slot-refill variant"
+#endif
 #if defined(TINY_JIT_ITRAJ) && TINY_JIT_ITRAJ && TINY_REFILL
 #error "per-instance trajectories: no slot-refill variant"
 #endif
@@ -1886,9 +1936,13 @@ TINY_KERNEL_NAME(const tinympc::SolveParams p) {
 #define TINY_JIT_ITRAJ 0
 #endif
     constexpr bool ITJ = TINY_JIT_ITRAJ != 0;  // per-instance trajectories (with -DTINY_JIT_IGOAL=1): the wavefront's own linref rows
-    constexpr int VLJ = tinympc::d_vl(TINY_JIT_NU, TINY_JIT_N, CTJ, WPGJ, 4 * TINY_JIT_WPS, FAMJ, ADJ, IMJ, ILJ, KNJ, ITJ);
+#ifndef TINY_JIT_IKBND
+#define TINY_JIT_IKBND 0
+#endif
+    constexpr bool IBJ = TINY_JIT_IKBND != 0;  // per-knot bounds per instance (with -DTINY_JIT_IGOAL=1): the wavefront's own clamp rows
+    constexpr int VLJ = tinympc::d_vl(TINY_JIT_NU, TINY_JIT_N, CTJ, WPGJ, 4 * TINY_JIT_WPS, FAMJ, ADJ, IMJ, ILJ, KNJ, ITJ, IBJ);
     static_assert(VLJ >= 0, "shape does not fit the layout-D plan");
-    __shared__ __attribute__((aligned(16))) double smem_jit[tinympc::d_lds_bytes(TINY_JIT_NU, TINY_JIT_N, CTJ, WPGJ, VLJ, FAMJ, ADJ, IMJ, ILJ, KNJ, ITJ) / sizeof(double)];
+    __shared__ __attribute__((aligned(16))) double smem_jit[tinympc::d_lds_bytes(TINY_JIT_NU, TINY_JIT_N, CTJ, WPGJ, VLJ, FAMJ, ADJ, IMJ, ILJ, KNJ, ITJ, IBJ) / sizeof(double)];
 #if TINY_REFILL
 #ifndef TINY_JIT_REFILL
 #define TINY_JIT_REFILL 0
@@ -1899,7 +1953,7 @@ TINY_KERNEL_NAME(const tinympc::SolveParams p) {
 #define TINY_JIT_IGOAL 0
 #endif
     tinympc::k_admm_solve_d_body<TINY_JIT_NX, TINY_JIT_NU, TINY_JIT_N, CTJ, WPGJ, VLJ, FAMJ, ADJ, TINY_JIT_WPS == 2, false, false,
-                                 TINY_JIT_IGOAL != 0 || IMJ, IMJ, ILJ, TINY_JIT_ICONE != 0, TINY_JIT_IKNOT != 0, ITJ>(p, smem_jit);
+                                 TINY_JIT_IGOAL != 0 || IMJ, IMJ, ILJ, TINY_JIT_ICONE != 0, TINY_JIT_IKNOT != 0, ITJ, IBJ>(p, smem_jit);
 #endif
 }
 namespace tinympc {

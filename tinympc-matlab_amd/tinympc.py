@@ -832,7 +832,10 @@ class TinyMPC:
         Both together -- per-instance rows, rows per knot or cone slopes on per-instance trajectories or tracks -- run on the linear-row
         form that reads every wavefront's own reference rows (jit_info(): "... per-instance-linear per-instance-trajectories"), where rows
         and reference rows fit a wavefront's LDS share together; a trajectory shared by the batch through set_x_ref() / set_u_ref() is not
-        one of these and keeps the mode on layout A -- send it through set_x_ref_batch() to stay on layout D."""
+        one of these and keeps the mode on layout A -- send it through set_x_ref_batch() to stay on layout D. Box bounds per knot and
+        per instance (set_bound_constraints_batch with (nx, N, count) / (nu, N-1, count) arrays), with or without per-instance
+        trajectories or tracks, run on layout D's per-knot bounds form where the horizon's clamp rows fit a wavefront's LDS share
+        (jit_info(): "... per-knot-bounds"; box path, the shared model and rho)."""
         self._check_setup()
         self._push_settings()
         _lib.check(self._L.tinympc_prepare(self._h))
