@@ -226,7 +226,9 @@ int tinympc_set_x0_batch_device(tinympc_solver *s, const double *d_x0s, int firs
  * for a half (x or u) turns per-instance mode on for that half; instances outside the range keep the handle's shared
  * reference of that moment. A later tinympc_set_x_ref / tinympc_set_u_ref returns that half to shared mode for every
  * instance. reset_workspace, update_settings, set_bound_constraints, the solve verbs and mpc_step_batch keep them.
- * Goals run on layout D where the handle runs layout D (compiled in or run-time specialised). Trajectories (either half, cols = N /
+ * Goals run on layout D where the handle runs layout D (compiled in or run-time specialised) -- and, 16-lane shapes with a batch
+ * beyond one resident set and tolerances that can be met, with slot refill (tinympc_get_jit_info: " goal slot-refill"; bit-identical
+ * results; TINYMPC_REFILL as for the shared reference). Trajectories (either half, cols = N /
  * N-1) run on layout A -- or, on a handle that called tinympc_prepare (before or after these verbs), on layout D's per-instance
  * trajectory form: where the handle runs layout D with nx+nu <= 16, bounds are constant over the horizon (shared or per instance), the
  * model and rho are the shared ones, and the horizon's N+2 reference rows fit a wavefront's share of LDS beside its other state (the
@@ -305,7 +307,7 @@ int tinympc_get_ref_step_batch(tinympc_solver *s, int *steps_out, int first, int
  * per-instance mode on; instances outside the range keep the handle's shared bounds of that moment. A later
  * tinympc_set_bound_constraints returns every instance to shared bounds. reset_workspace, update_settings, the reference verbs, the
  * solve verbs and mpc_step_batch keep them. Boxes (with references constant over the horizon) run on layout D where the handle runs
- * layout D. Bounds per knot run on layout A -- or, on a handle that called tinympc_prepare and runs layout D with nx+nu <= 16, on layout
+ * layout D, with slot refill where a shared box would have it (see tinympc_get_jit_info). Bounds per knot run on layout A -- or, on a handle that called tinympc_prepare and runs layout D with nx+nu <= 16, on layout
  * D's per-knot bounds form: box path, the shared model and rho, every reference half constant over the horizon (shared or per instance)
  * or a per-instance trajectory / track, and a horizon whose 2 (N+2) clamp rows (3 (N+2) rows beside trajectories) fit a wavefront's
  * LDS share (quadrotor: N <= 33, N <= 22 beside trajectories; tinympc_get_jit_info says " per-knot-bounds", or " per-knot-bounds(no
@@ -614,7 +616,11 @@ int tinympc_get_layout(tinympc_solver *s);
  * (converged, or max_iter) is written back and given the next instance of the batch while the rest of its wavefront keeps
  * iterating -- a wavefront then costs the sum of what its rows worked instead of four times its slowest instance. Results are
  * bit-identical to the plain kernel's. Taken whenever the tolerances can be met (with forced iteration counts there is nothing to
- * balance); TINYMPC_REFILL=0 switches it off, =1 takes it for any batch beyond one resident set. */
+ * balance); TINYMPC_REFILL=0 switches it off, =1 takes it for any batch beyond one resident set. The box path of the 16-lane
+ * shapes: handles whose instances share one reference and one box, and handles with one goal and / or one box per instance
+ * (tinympc_set_x_ref_batch / _u_ref_batch / _set_bound_constraints_batch with one column per instance: layout D's goal form,
+ * " goal slot-refill" -- a row that takes an instance takes its goal and box with it). Not with per-instance trajectories, tracks,
+ * bounds per knot, models, rho, linear rows or cone slopes, the families, adaptive rho or the zero-copy tick. */
 int tinympc_get_jit_info(tinympc_solver *s, char *buf, int len);
 
 /* Decide (and, where needed, specialise -- seconds the first time) the solve kernel for the handle's CURRENT configuration:

@@ -400,6 +400,8 @@ __device__ __forceinline__ bool wave_may_converge_d32(unsigned long long bad, un
 // loaded with the next instance of the batch, cold or warm, while the other three rows of the wavefront keep iterating. The
 // arithmetic of an instance is that of the plain kernel (bit-identical results: tests/test_hip_parity.py); what changes is that
 // a wavefront's time is the sum of what its rows worked, not four times its slowest instance.
+// REFILL with IGOAL (the per-instance goal form of the box path, k_admm_solve_d_refill_gbnd): lr_c, pNref, lo_c and hi_c belong to the
+// row's CURRENT instance -- loaded per lane at kernel start, reloaded with the folded accumulator start where a row takes an instance.
 template <int NX, int NU, int N, bool CT, int WPG, int VL, bool FAM = false, bool ADAPT = false, bool TWO_PER_SIMD = true, bool HOSTX = false,
           bool REFILL = false, bool IGOAL = false, bool IMOD = false, int ILIN = 0, bool ICONE = false, bool IKNOT = false, bool ITRAJ = false, bool IKBND = false>
 #else
@@ -762,10 +764,17 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
     if constexpr (IMOD) rho = inst_ok ? p.rho_inst[inst] : rho0;
     double nrho = -rho;
     // (IKBND: ibnd is the store of every knot's rows, not [instance][16] -- the form reads its clamps from sBndW and has no lo_c / hi_c)
+#if TINY_REFILL
+    // (REFILL with IGOAL: the four lane constants belong to the row's CURRENT instance -- reloaded where the row takes its next one)
+    double lo_c = IKBND ? 0.0 : IGOAL ? (inst_ok ? p.ibnd[inst * W + r] : 0.0) : p.tables[W + r];
+    double hi_c = IKBND ? 0.0 : IGOAL ? (inst_ok ? p.ibnd[(size_t)p.groups * 64 + inst * W + r] : 0.0) : p.tables[(size_t)TOFF + W + r];
+    double lr_c = ITRAJ ? 0.0 : IGOAL ? (inst_ok ? p.iref_lr[inst * W + r] : 0.0) : p.tables[(size_t)2 * TOFF + W + r];
+#else
     const double lo_c = IKBND ? 0.0 : IGOAL ? (inst_ok ? p.ibnd[inst * W + r] : 0.0) : p.tables[W + r];
     const double hi_c = IKBND ? 0.0 : IGOAL ? (inst_ok ? p.ibnd[(size_t)p.groups * 64 + inst * W + r] : 0.0) : p.tables[(size_t)TOFF + W + r];
     // (ITRAJ: iref_lr is the store of every knot's rows, not [instance][16] -- the form reads its linref from sRefW and has no lr_c)
     const double lr_c = ITRAJ ? 0.0 : IGOAL ? (inst_ok ? p.iref_lr[inst * W + r] : 0.0) : p.tables[(size_t)2 * TOFF + W + r];
+#endif
     double rhom = is_x ? nrho : 0.0;
 #if TINY_REFILL
     double x0v = (inst_ok && is_x) ? p.x0[inst * NX + r] : 0.0;
@@ -1020,6 +1029,23 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
                     const size_t grp_n = (size_t)(nxt >> 2);
                     const int lane_n = (nxt & 3) * 16 + r_o;
                     if (take && x_o) x0v = p.x0[(size_t)nxt * NX + r_o];
+                    if constexpr (IGOAL) {
+                        // The goal form: the taking rows' lane constants are their new instance's ([instance][16]; ibnd's hi half at
+                        // groups * 64), and so is the folded accumulator start -- the kernel start's expression on the same operands.
+                        // Its chain exchanges values across the 16-lane row: executed by every lane, then selected on `take` (whole rows).
+                        static_assert(FOLD && !ITRAJ && !IKBND && !IMOD && ILIN == 0, "slot refill: the goal form of the box path only");
+                        if (take) {
+                            const size_t io = (size_t)nxt * W + r_o;
+                            lr_c = p.iref_lr[io];
+                            pnref = p.iref_pn[io];
+                            lo_c = p.ibnd[io];
+                            hi_c = p.ibnd[(size_t)p.groups * 64 + io];
+                        }
+                        double mb[16];
+                        static_for<0, 16>([&](auto K) { mb[K.value] = (K.value >= NX && K.value < NXU) ? p.ops[(size_t)W * KT + (size_t)r_o * KT + K.value] : 0.0; });
+                        const double lrmc_n = Step::acc_inputs(x_o ? lr_c + cb : cb, lr_c, mb);
+                        lrmc_f = take ? lrmc_n : lrmc_f;
+                    }
                     if (cold) {
                         static_for<0, NS>([&](auto S) { G[S.value] = take ? 0.0 : G[S.value]; });
                         static_for<0, NVR>([&](auto S) { Vr[S.value] = take ? 0.0 : Vr[S.value]; });
@@ -1862,6 +1888,15 @@ __global__ void __launch_bounds__(64 * WPG) __attribute__((amdgpu_waves_per_eu(2
     k_admm_solve_d_body<NX, NU, N, CT, WPG, VL, false, false, true, HOSTX>(p, smem);
 #endif
 }
+#if TINY_REFILL
+// Slot refill for the per-instance goal form (k_admm_solve_d_gbnd's launches): a row that takes the next instance of the batch takes
+// that instance's lr_c / pNref / lo_c / hi_c and folded accumulator start with it.
+template <int NX, int NU, int N, int WPG, int VL>
+__global__ void __launch_bounds__(64 * WPG) __attribute__((amdgpu_waves_per_eu(2, 2))) k_admm_solve_d_refill_gbnd(const SolveParams p) {
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    k_admm_solve_d_body<NX, NU, N, true, WPG, VL, false, false, true, false, true, true>(p, smem);
+}
+#endif
 #if !TINY_REFILL
 // The per-instance goal form (one goal per instance from tinympc_set_x_ref_batch and / or one box per instance from
 // tinympc_set_bound_constraints_batch; shared references and bounds that are constant over the horizon fill the rest): the plain
@@ -1947,7 +1982,15 @@ TINY_KERNEL_NAME(const tinympc::SolveParams p) {
 #ifndef TINY_JIT_REFILL
 #define TINY_JIT_REFILL 0
 #endif
+#if defined(TINY_JIT_IGOAL) && TINY_JIT_IGOAL
+#if !TINY_JIT_REFILL || !TINY_JIT_CT || TINY_JIT_FAM || TINY_JIT_ADAPT
+#error "slot refill for the goal form: the box path with constant tables"
+#endif
+    // (the goal form: a row's four lane constants and its folded accumulator start follow the instance it takes)
+    tinympc::k_admm_solve_d_body<TINY_JIT_NX, TINY_JIT_NU, TINY_JIT_N, true, WPGJ, VLJ, false, false, TINY_JIT_WPS == 2, false, true, true>(p, smem_jit);
+#else
     tinympc::k_admm_solve_d_body<TINY_JIT_NX, TINY_JIT_NU, TINY_JIT_N, CTJ, WPGJ, VLJ, FAMJ, ADJ, TINY_JIT_WPS == 2, false, TINY_JIT_REFILL != 0>(p, smem_jit);
+#endif
 #else
 #ifndef TINY_JIT_IGOAL
 #define TINY_JIT_IGOAL 0
@@ -1996,12 +2039,24 @@ static hipError_t launch_d_one(const SolveParams &p, hipStream_t stream) {
         return hipErrorInvalidValue;
     } else {
         constexpr size_t lds = d_lds_bytes(NU, N, CT, WPG, VL);
-        static size_t lds_set_r[16] = {0};
+        static size_t lds_set_r[16] = {0}, lds_set_rgoal[16] = {0};
         const int wgs = (p.groups + WPG - 1) / WPG;
+        const int resident = solve_d_resident_workgroups(WPG);
+        if (p.iref_pn) {  // per-instance goals (constant tables only; the guards of the plain goal launch)
+            if constexpr (!CT) {
+                return hipErrorInvalidValue;
+            } else {
+                if (p.x0_mirror || p.u0_host || !p.iref_lr || !p.ibnd) return hipErrorInvalidValue;
+                auto fn = &k_admm_solve_d_refill_gbnd<NX, NU, N, WPG, VL>;
+                hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void *>(fn), lds, lds_set_rgoal);
+                if (e != hipSuccess) return e;
+                hipLaunchKernelGGL(fn, dim3(wgs < resident ? wgs : resident), dim3(64 * WPG), lds, stream, p);
+            }
+            return hipGetLastError();
+        }
         auto fn = &k_admm_solve_d_refill<NX, NU, N, CT, WPG, VL>;
         hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void *>(fn), lds, lds_set_r);
         if (e != hipSuccess) return e;
-        const int resident = solve_d_resident_workgroups(WPG);
         hipLaunchKernelGGL(fn, dim3(wgs < resident ? wgs : resident), dim3(64 * WPG), lds, stream, p);
         return hipGetLastError();
     }

@@ -317,7 +317,9 @@ class TinyMPC:
     def set_x_ref_batch(self, x_refs, first: int = 0):
         """Per-instance state references for instances first, first+1, ...: a numpy array of shape (nx, count) (one goal per
         instance, held over the horizon) or (nx, N, count) (a trajectory per instance), or a CUDA torch tensor with the same memory
-        layout, (count, nx) or (count, N, nx) contiguous. set_x_ref() returns every instance to the shared reference."""
+        layout, (count, nx) or (count, N, nx) contiguous. set_x_ref() returns every instance to the shared reference. Goals run on
+        layout D's goal form where the handle runs layout D; a converging batch beyond one resident set (16-lane shapes) runs it
+        with slot refill, bit-identical to the plain goal kernel (jit_info(): 'goal slot-refill'; TINYMPC_REFILL=0 switches it off)."""
         self._check_setup()
         self._set_batch("references", (x_refs,), (self.nx,), (self.N,), self._L.tinympc_set_x_ref_batch,
                         self._L.tinympc_set_x_ref_batch_device, first, self.nx)
@@ -403,7 +405,9 @@ class TinyMPC:
         """Per-instance box bounds for instances first, first+1, ...: numpy arrays of shape (nx, count) / (nu, count) (one box per
         instance, held over the horizon) or (nx, N, count) / (nu, N-1, count) (bounds per knot), or CUDA torch tensors with the same
         memory layout, (count, nx) / (count, nu) or (count, N, nx) / (count, N-1, nu) contiguous float64. All four in the same form.
-        Enables both bound families, as set_bound_constraints does; set_bound_constraints() returns every instance to shared bounds."""
+        Enables both bound families, as set_bound_constraints does; set_bound_constraints() returns every instance to shared bounds.
+        One box per instance (beside references constant over the horizon) runs on layout D's goal form, with slot refill where a
+        shared box would have it (see set_x_ref_batch)."""
         self._check_setup()
         self._set_batch("bounds", (x_min, x_max, u_min, u_max), (self.nx, self.nx, self.nu, self.nu), (self.N, self.N, self.N - 1, self.N - 1),
                         self._L.tinympc_set_bound_constraints_batch, self._L.tinympc_set_bound_constraints_batch_device, first)
@@ -849,7 +853,8 @@ class TinyMPC:
 
     def jit_info(self) -> str:
         """Origin of the kernel of the current configuration: 'compiled-in ...', 'compiled ...', 'disk-cache ...' or
-        'refused(<reason>)' (tinympc_get_jit_info)."""
+        'refused(<reason>)' (tinympc_get_jit_info). ' slot-refill' where the launch runs layout D's slot-refill variant: the shared
+        box path, or the goal form (one goal and / or one box per instance)."""
         self._check_setup()
         self._push_settings()
         buf = C.create_string_buffer(1024)
