@@ -228,7 +228,8 @@ int tinympc_set_x0_batch_device(tinympc_solver *s, const double *d_x0s, int firs
  * instance. reset_workspace, update_settings, set_bound_constraints, the solve verbs and mpc_step_batch keep them.
  * Goals run on layout D where the handle runs layout D (compiled in or run-time specialised) -- and, 16-lane shapes with a batch
  * beyond one resident set and tolerances that can be met, with slot refill (tinympc_get_jit_info: " goal slot-refill"; bit-identical
- * results; TINYMPC_REFILL as for the shared reference). Trajectories (either half, cols = N /
+ * results; TINYMPC_REFILL as for the shared reference; the trajectory form of layout D, below, refills in the same way beyond ITS
+ * resident set: " per-instance-trajectories slot-refill"). Trajectories (either half, cols = N /
  * N-1) run on layout A -- or, on a handle that called tinympc_prepare (before or after these verbs), on layout D's per-instance
  * trajectory form: where the handle runs layout D with nx+nu <= 16, bounds are constant over the horizon (shared or per instance), the
  * model and rho are the shared ones, and the horizon's N+2 reference rows fit a wavefront's share of LDS beside its other state (the
@@ -265,7 +266,8 @@ int tinympc_set_u_ref_batch_device(tinympc_solver *s, const double *d_Urefs, int
  * T = 1: never layout D's goal form) -- or, after tinympc_prepare and under tinympc_set_x_ref_batch's conditions, on layout D's
  * per-instance trajectory form (with bounds per knot: on its per-knot bounds form, see there), or, inside the per-instance families mode, on that mode's form for trajectories
  * (tinympc_set_linear_constraints_batch; tinympc_mpc_step_batch with auto-advance included: the rows are rebuilt per tick as on layout A,
- * and the kernel stages the rebuilt rows) --,
+ * and the kernel stages the rebuilt rows; the trajectory and per-knot bounds forms run a tick beyond one resident set with slot refill,
+ * see tinympc_get_jit_info) --,
  * " reference-track" is appended to tinympc_get_jit_info, and every refusal of per-instance
  * references applies unchanged (the cone / linear families, adaptive rho, nx+nu > 64: a solve returns TINYMPC_ERR_UNSUPPORTED;
  * tinympc_session_begin likewise). tinympc_set_x_ref / _u_ref returns the half to shared references; a whole-batch
@@ -311,7 +313,8 @@ int tinympc_get_ref_step_batch(tinympc_solver *s, int *steps_out, int first, int
  * D's per-knot bounds form: box path, the shared model and rho, every reference half constant over the horizon (shared or per instance)
  * or a per-instance trajectory / track, and a horizon whose 2 (N+2) clamp rows (3 (N+2) rows beside trajectories) fit a wavefront's
  * LDS share (quadrotor: N <= 33, N <= 22 beside trajectories; tinympc_get_jit_info says " per-knot-bounds", or " per-knot-bounds(no
- * plan)" where the horizon does not fit). What stays on layout A with bounds per knot: no tinympc_prepare, a trajectory shared by the
+ * plan)" where the horizon does not fit; beyond one resident set of that form and with tolerances that can be met it runs with slot
+ * refill, " per-knot-bounds slot-refill", bit-identical). What stays on layout A with bounds per knot: no tinympc_prepare, a trajectory shared by the
  * batch through tinympc_set_x_ref / _set_u_ref, per-instance models or rho, per-instance linear rows or cone slopes, wider systems,
  * longer horizons. With the cone / linear families, adaptive rho or nx+nu > 64 a solve returns
  * TINYMPC_ERR_UNSUPPORTED (never a solve with the shared bounds). Invalid arguments return TINYMPC_ERR_INVALID_INPUT and leave the mode
@@ -619,8 +622,11 @@ int tinympc_get_layout(tinympc_solver *s);
  * balance); TINYMPC_REFILL=0 switches it off, =1 takes it for any batch beyond one resident set. The box path of the 16-lane
  * shapes: handles whose instances share one reference and one box, and handles with one goal and / or one box per instance
  * (tinympc_set_x_ref_batch / _u_ref_batch / _set_bound_constraints_batch with one column per instance: layout D's goal form,
- * " goal slot-refill" -- a row that takes an instance takes its goal and box with it). Not with per-instance trajectories, tracks,
- * bounds per knot, models, rho, linear rows or cone slopes, the families, adaptive rho or the zero-copy tick. */
+ * " goal slot-refill" -- a row that takes an instance takes its goal and box with it), and, after tinympc_prepare, handles on layout
+ * D's per-instance trajectory form (trajectories, tracks) and / or per-knot bounds form (" per-instance-trajectories slot-refill",
+ * " per-knot-bounds slot-refill" -- the row also restages its column of its wavefront's reference / clamp rows; a resident set is that
+ * form's own: 4,096 instances where it runs one wavefront per SIMD, e.g. the quadrotor's trajectories at N = 50). Not with
+ * per-instance models, rho, linear rows or cone slopes, the families, adaptive rho or the zero-copy tick. */
 int tinympc_get_jit_info(tinympc_solver *s, char *buf, int len);
 
 /* Decide (and, where needed, specialise -- seconds the first time) the solve kernel for the handle's CURRENT configuration:
@@ -640,7 +646,8 @@ int tinympc_get_jit_info(tinympc_solver *s, char *buf, int len);
  * batch through tinympc_set_x_ref / _set_u_ref is not one of these: layout A); and a batch with box bounds per knot and per instance
  * (tinympc_set_bound_constraints_batch with cols = N, in either order), or with shared per-knot bounds beside per-instance trajectories
  * or tracks, on layout D's per-knot bounds form under the same conditions, where the clamp rows fit the wavefront's LDS share too;
- * otherwise layout A as without this call. No reference
+ * otherwise layout A as without this call. Where the trajectory or per-knot bounds form is already the handle's and its batch lies
+ * beyond one resident set, the form's slot-refill variant is built here as well. No reference
  * counterpart (the reference has one code path). */
 int tinympc_prepare(tinympc_solver *s);
 

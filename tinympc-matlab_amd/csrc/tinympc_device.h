@@ -675,8 +675,10 @@ bool solve_jit_supported(int W, int nx, int nu, int N, bool const_tables, bool f
 bool solve_jit_planned(int W, int nx, int nu, int N, bool const_tables, bool families, bool adaptive, bool models, int ilin, int knots, bool traj, bool kbnd);
 hipError_t launch_solve_jit(const SolveParams &p, int W, hipStream_t stream, bool models = false, int ilin = 0, bool icone = false, int knots = 0,
                             bool traj = false, bool kbnd = false);
-bool solve_jit_refill_supported(int W, int nx, int nu, int N, bool const_tables, bool goal = false);   // (compiles the slot-refill variant on first use; goal: the per-instance goal form's)
-int solve_jit_resident_wavefronts(int W, int nx, int nu, int N, bool const_tables, bool goal = false);  // wavefronts of the shape's plan (goal: the goal form's own) the device holds at once
+// (compiles the slot-refill variant on first use; goal: the per-instance goal form's; traj / kbnd: its trajectory / per-knot bounds form's)
+bool solve_jit_refill_supported(int W, int nx, int nu, int N, bool const_tables, bool goal = false, bool traj = false, bool kbnd = false);
+// wavefronts of the shape's plan (goal, traj, kbnd: that form's OWN plan -- the trajectory forms of long horizons run one wavefront per SIMD) the device holds at once
+int solve_jit_resident_wavefronts(int W, int nx, int nu, int N, bool const_tables, bool goal = false, bool traj = false, bool kbnd = false);
 int solve_jit_workgroups(int W, int nx, int nu, int N, bool const_tables, int groups, bool families = false, bool adaptive = false, bool goal = false,
                          bool models = false, int ilin = 0, bool icone = false, int knots = 0, bool traj = false, bool kbnd = false);
 size_t solve_jit_lds_bytes(int W, int nx, int nu, int N, bool const_tables, bool families = false, bool adaptive = false, bool goal = false,

@@ -402,22 +402,29 @@ int resolve_plan(tinympc_solver *s) {
 // with. TINYMPC_REFILL=0 switches it off, =1 takes it for any batch beyond one resident set whatever the tolerances. Shared tables, or
 // the per-instance goal form (on by default as well: 65,536 quadrotors with a goal and a box each, 10.91 against 13.45 ms,
 // profiles/refill_goal_ab.txt).
+// The trajectory and per-knot bounds forms of the goal form (per-instance trajectories, tracks, bound schedules after tinympc_prepare)
+// have a variant too, on by default as well: 65,536 quadrotors N=50 with a trajectory each, 7.45 against 19.71 ms, below the plain form
+// in every round (profiles/refill_traj_ab.txt). Their resident set is their OWN plan's -- 4,096 instances where the form runs one
+// wavefront per SIMD.
 static bool refill_applies(const tinympc_solver *s, const LaunchPlan &pl) {
     const bool jit = pl.kernel == KernelId::D_JIT;
     if ((pl.kernel != KernelId::D_COMPILED && !jit) || s->W != 16 || pl.adaptive || pl.families || s->zero_copy_tick || s->st.max_iter <= 0 ||
         s->st.check_termination <= 0)
         return false;
     if (pl.inst_models) return false;  // (the model form has no slot-refill variant)
-    // A per-instance handle: exactly when the launch runs layout D's goal form (a row that takes an instance takes its four lane constants
-    // with it); the forms whose rows live in per-wavefront LDS regions -- trajectories, bounds per knot, linear rows -- have no variant.
+    // A per-instance handle: when the launch runs layout D's goal form (a row that takes an instance takes its four lane constants with
+    // it), or that form on per-instance trajectories / tracks and / or bounds per knot (the row also restages its column of its
+    // wavefront's linref / clamp rows); the per-instance families' form -- linear rows, with or without trajectories -- has no variant.
     const bool goal = pl.inst_refs;
-    if (goal && (pl.inst_traj || pl.inst_kbnd || pl.inst_lin)) return false;
+    if (goal && pl.inst_lin) return false;
+    const bool traj = goal && pl.inst_traj, kbnd = goal && pl.inst_kbnd;
+    if ((traj || kbnd) && !jit) return false;  // (those forms are specialisations)
     const char *env = getenv("TINYMPC_REFILL");
     const int mode = env ? atoi(env) : -1;
     if (mode == 0) return false;
     const bool ct = s->tables_const() || goal;  // (the plan's constness: the goal form always has constant tables)
     long resident;  // wavefronts = groups of four instances
-    if (jit) resident = solve_jit_resident_wavefronts(s->W, s->nx, s->nu, s->N, ct, goal);  // (the goal form's own plan)
+    if (jit) resident = solve_jit_resident_wavefronts(s->W, s->nx, s->nu, s->N, ct, goal, traj, kbnd);  // (the form's own plan: one wavefront per SIMD for the long trajectory forms)
     else {
         const int wpg = solve_d_wavefronts_per_workgroup(s->nu, s->N, ct);
         resident = (long)solve_d_resident_workgroups(wpg) * wpg;
@@ -427,7 +434,7 @@ static bool refill_applies(const tinympc_solver *s, const LaunchPlan &pl) {
     const bool reachable = s->st.abs_pri_tol > 0.0 && s->st.abs_dua_tol > 0.0;
     if ((long)s->groups <= resident) return false;
     if (!reachable && mode != 1) return false;
-    return !jit || solve_jit_refill_supported(s->W, s->nx, s->nu, s->N, ct, goal);  // (run-time specialised shapes: built on first use)
+    return !jit || solve_jit_refill_supported(s->W, s->nx, s->nu, s->N, ct, goal, traj, kbnd);  // (run-time specialised shapes: built on first use)
 }
 
 // Lean sweeps (tinympc_lean_d.hip, TINY_LEAN): layout D's compiled-in 16-lane kernels (box path; shared tables or the per-instance
@@ -748,11 +755,13 @@ static int jit_info_text(tinympc_solver *s, char *buf, int len) {
             strncat(buf, words, (size_t)len - strlen(buf) - 1);
             if (tr) strncat(buf, " per-instance-trajectories", (size_t)len - strlen(buf) - 1);
             strncat(buf, " per-knot-bounds", (size_t)len - strlen(buf) - 1);
+            if (pl.kernel == KernelId::D_JIT && refill_applies(s, pl)) strncat(buf, " slot-refill", (size_t)len - strlen(buf) - 1);
         } else if (pl.kernel == KernelId::D_JIT && pl.inst_traj && !pl.inst_lin) {  // layout D's trajectory form (box path)
             if ((rc = bind_device(s))) return rc;
             solve_jit_describe(s->W, s->nx, s->nu, s->N, true, false, false, buf, (size_t)len, true, false, 0, false, 0, true);
             strncat(buf, words, (size_t)len - strlen(buf) - 1);
             strncat(buf, " per-instance-trajectories", (size_t)len - strlen(buf) - 1);
+            if (refill_applies(s, pl)) strncat(buf, " slot-refill", (size_t)len - strlen(buf) - 1);
         } else if (pl.kernel == KernelId::A && !pl.inst_lin && !pl.inst_models && traj_wants_d(s) && s->inst.d_traj == 0) {  // asked for and refused: layout A, and why
             if ((rc = bind_device(s))) return rc;
             solve_jit_describe(s->W, s->nx, s->nu, s->N, true, false, false, buf, (size_t)len, true, false, 0, false, 0, true);
@@ -765,7 +774,7 @@ static int jit_info_text(tinympc_solver *s, char *buf, int len) {
                                pl.inst_traj);
             strncat(buf, words, (size_t)len - strlen(buf) - 1);
             if (!pl.inst_traj) strncat(buf, " goal", (size_t)len - strlen(buf) - 1);  // (the families' form on trajectories, inst_lin with inst_traj: named behind the mode's words)
-            if (refill_applies(s, pl)) strncat(buf, " slot-refill", (size_t)len - strlen(buf) - 1);  // (the goal form of the box path only: see refill_applies)
+            if (refill_applies(s, pl)) strncat(buf, " slot-refill", (size_t)len - strlen(buf) - 1);  // (the goal form of the box path, not the families': see refill_applies)
         } else if (pl.inst_lin && lin_wants_d(s) && s->inst.d_lin == 0 && lin_d_answer_current(s)) {  // asked for and refused: layout A, and why
             if ((rc = bind_device(s))) return rc;
             solve_jit_describe(s->W, s->nx, s->nu, s->N, true, true, false, buf, (size_t)len, true, false, s->ifam_nl(), s->inst.cones, lin_d_knots(s), lin_d_traj(s));

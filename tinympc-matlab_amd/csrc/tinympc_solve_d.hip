@@ -402,6 +402,10 @@ __device__ __forceinline__ bool wave_may_converge_d32(unsigned long long bad, un
 // a wavefront's time is the sum of what its rows worked, not four times its slowest instance.
 // REFILL with IGOAL (the per-instance goal form of the box path, k_admm_solve_d_refill_gbnd): lr_c, pNref, lo_c and hi_c belong to the
 // row's CURRENT instance -- loaded per lane at kernel start, reloaded with the folded accumulator start where a row takes an instance.
+// REFILL with ITRAJ and / or IKBND (forms of the goal form, box path; run-time specialised, k_builtin_d_quadrotor50_traj_refill compiled
+// in): the wavefront stages its FIRST group's linref / clamp rows at kernel start as the plain form does; a row that takes an instance
+// reloads the lane constants its form has (pNref, lo_c, hi_c with ITRAJ; pNref and, without ITRAJ, lr_c with IKBND) and restages its own
+// 16-lane column of those rows from the new instance's column of ITS group's block. FOLD is off in both forms: nothing is recomputed.
 template <int NX, int NU, int N, bool CT, int WPG, int VL, bool FAM = false, bool ADAPT = false, bool TWO_PER_SIMD = true, bool HOSTX = false,
           bool REFILL = false, bool IGOAL = false, bool IMOD = false, int ILIN = 0, bool ICONE = false, bool IKNOT = false, bool ITRAJ = false, bool IKBND = false>
 #else
@@ -444,10 +448,10 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
                   "per-instance models: the goal form of the box path (its rows are always built per instance), plain sweeps");
     static_assert(!ICONE || ILIN > 0, "per-instance cone slopes: with the per-instance rows' form (one absent row where there are none)");
     static_assert(!IKNOT || ILIN > 0, "rows per knot: a form of the per-instance rows");
-    static_assert(!ITRAJ || (IGOAL && CT && FAM == (ILIN > 0) && !ADAPT && !IMOD && !REFILL && !HOSTX && !TINY_LEAN),
-                  "per-instance trajectories: the goal form of the box path, or of the per-instance families (bounds constant over the horizon), plain sweeps");
-    static_assert(!IKBND || (IGOAL && CT && !FAM && ILIN == 0 && !ADAPT && !IMOD && !REFILL && !HOSTX && !TINY_LEAN),
-                  "per-knot bounds per instance: the goal form of the box path (references constant over the horizon or per-instance trajectories), plain sweeps");
+    static_assert(!ITRAJ || (IGOAL && CT && FAM == (ILIN > 0) && !ADAPT && !IMOD && (!REFILL || ILIN == 0) && !HOSTX && !TINY_LEAN),
+                  "per-instance trajectories: the goal form of the box path (plain sweeps or slot refill), or of the per-instance families (bounds constant over the horizon; plain sweeps)");
+    static_assert(!IKBND || (IGOAL && CT && !FAM && ILIN == 0 && !ADAPT && !IMOD && !HOSTX && !TINY_LEAN),
+                  "per-knot bounds per instance: the goal form of the box path (references constant over the horizon or per-instance trajectories), plain sweeps or slot refill");
     static_assert(ILIN == 0 || (ILIN > 0 && ILIN <= MAX_LIN_ROWS && FAM && IGOAL && CT && !ADAPT && !IMOD && !REFILL && !HOSTX && !TINY_LEAN),
                   "per-instance linear rows: the families' variant in the goal form (references and bounds constant over the horizon), plain sweeps");
 #if TINY_REFILL
@@ -1033,18 +1037,46 @@ __device__ __forceinline__ void k_admm_solve_d_body(const SolveParams &p, double
                         // The goal form: the taking rows' lane constants are their new instance's ([instance][16]; ibnd's hi half at
                         // groups * 64), and so is the folded accumulator start -- the kernel start's expression on the same operands.
                         // Its chain exchanges values across the 16-lane row: executed by every lane, then selected on `take` (whole rows).
-                        static_assert(FOLD && !ITRAJ && !IKBND && !IMOD && ILIN == 0, "slot refill: the goal form of the box path only");
+                        // (ITRAJ / IKBND: the constants the form loads per instance at kernel start -- it has no lr_c with trajectories, no
+                        // lo_c / hi_c with bounds per knot -- and no folded start: FOLD is off, every backward block forms its own from the row it reads)
+                        static_assert(!IMOD && ILIN == 0 && FOLD == (!ITRAJ && !IKBND), "slot refill: the goal form of the box path, its trajectory and per-knot bounds forms");
                         if (take) {
                             const size_t io = (size_t)nxt * W + r_o;
-                            lr_c = p.iref_lr[io];
+                            if constexpr (!ITRAJ) lr_c = p.iref_lr[io];
                             pnref = p.iref_pn[io];
-                            lo_c = p.ibnd[io];
-                            hi_c = p.ibnd[(size_t)p.groups * 64 + io];
+                            if constexpr (!IKBND) {
+                                lo_c = p.ibnd[io];
+                                hi_c = p.ibnd[(size_t)p.groups * 64 + io];
+                            }
                         }
-                        double mb[16];
-                        static_for<0, 16>([&](auto K) { mb[K.value] = (K.value >= NX && K.value < NXU) ? p.ops[(size_t)W * KT + (size_t)r_o * KT + K.value] : 0.0; });
-                        const double lrmc_n = Step::acc_inputs(x_o ? lr_c + cb : cb, lr_c, mb);
-                        lrmc_f = take ? lrmc_n : lrmc_f;
+                        if constexpr (FOLD) {
+                            double mb[16];
+                            static_for<0, 16>([&](auto K) { mb[K.value] = (K.value >= NX && K.value < NXU) ? p.ops[(size_t)W * KT + (size_t)r_o * KT + K.value] : 0.0; });
+                            const double lrmc_n = Step::acc_inputs(x_o ? lr_c + cb : cb, lr_c, mb);
+                            lrmc_f = take ? lrmc_n : lrmc_f;
+                        }
+                        if constexpr (ITRAJ || IKBND) {
+                            // The rows the wavefront staged at kernel start are its FIRST group's. A taking row restages its own 16-lane column of
+                            // them -- (lane & 48) + r, every row, padding rows and lanes beyond the system's rows included -- from its new
+                            // instance's column, (nxt & 3) * 16 + r of group nxt >> 2's block; the other three rows' columns are not touched (their
+                            // instances generally belong to other groups). The region is this wavefront's own: no barrier. The take path stands at
+                            // the iteration boundary -- every read the backward sweep issued a block ahead was consumed behind its block's wait --,
+                            // and the sweeps' reads of these rows (volatile, issued a block ahead) are kept behind the stores by the wait below.
+                            auto restage = [&](double *dst, const double *src) {
+                                double *const d = dst + lane_o;
+                                const double *const g = src + grp_n * (size_t)BHI + lane_n;
+#pragma unroll 4
+                                for (int k = 0; k < N + 2; ++k) d[k * 64] = g[k * 64];
+                            };
+                            if (take) {
+                                if constexpr (ITRAJ) restage(sRefW, p.iref_lr);
+                                if constexpr (IKBND) {
+                                    restage(sBndW, p.ibnd);
+                                    restage(sBndW + BHI, p.ibnd + (size_t)p.groups * BHI);  // (hi: one array of blocks behind lo, as the kernel start reads it)
+                                }
+                            }
+                            lds_wait();  // (lgkmcnt(0) and a compiler barrier: the stores have retired before the next sweep's first read is issued)
+                        }
                     }
                     if (cold) {
                         static_for<0, NS>([&](auto S) { G[S.value] = take ? 0.0 : G[S.value]; });
@@ -1937,11 +1969,8 @@ __global__ void __launch_bounds__(64 * WPG) __attribute__((amdgpu_waves_per_eu(2
 #if TINY_JIT_ILIN && TINY_REFILL
 #error "per-instance linear rows: no slot-refill variant"
 #endif
-#if defined(TINY_JIT_IKBND) && TINY_JIT_IKBND && TINY_REFILL
-#error "per-knot bounds per instance: no slot-refill variant"
-#endif
-#if defined(TINY_JIT_ITRAJ) && TINY_JIT_ITRAJ && TINY_REFILL
-#error "per-instance trajectories: no slot-refill variant"
+#if TINY_REFILL && ((defined(TINY_JIT_IKBND) && TINY_JIT_IKBND) || (defined(TINY_JIT_ITRAJ) && TINY_JIT_ITRAJ)) && !(defined(TINY_JIT_IGOAL) && TINY_JIT_IGOAL)
+#error "slot refill for per-instance trajectories / bounds per knot: forms of the goal form (-DTINY_JIT_IGOAL=1)"
 #endif
 extern "C" __global__ void __launch_bounds__(64 * TINY_JIT_WPG) __attribute__((amdgpu_waves_per_eu(TINY_JIT_WPS, TINY_JIT_WPS)))
 TINY_KERNEL_NAME(const tinympc::SolveParams p) {
@@ -1986,8 +2015,9 @@ TINY_KERNEL_NAME(const tinympc::SolveParams p) {
 #if !TINY_JIT_REFILL || !TINY_JIT_CT || TINY_JIT_FAM || TINY_JIT_ADAPT
 #error "slot refill for the goal form: the box path with constant tables"
 #endif
-    // (the goal form: a row's four lane constants and its folded accumulator start follow the instance it takes)
-    tinympc::k_admm_solve_d_body<TINY_JIT_NX, TINY_JIT_NU, TINY_JIT_N, true, WPGJ, VLJ, false, false, TINY_JIT_WPS == 2, false, true, true>(p, smem_jit);
+    // (the goal form: a row's four lane constants and its folded accumulator start follow the instance it takes; its trajectory and
+    // per-knot bounds forms: the lane constants they have, and the row's column of the wavefront's linref / clamp rows)
+    tinympc::k_admm_solve_d_body<TINY_JIT_NX, TINY_JIT_NU, TINY_JIT_N, true, WPGJ, VLJ, false, false, TINY_JIT_WPS == 2, false, true, true, false, 0, false, false, ITJ, IBJ>(p, smem_jit);
 #else
     tinympc::k_admm_solve_d_body<TINY_JIT_NX, TINY_JIT_NU, TINY_JIT_N, CTJ, WPGJ, VLJ, FAMJ, ADJ, TINY_JIT_WPS == 2, false, TINY_JIT_REFILL != 0>(p, smem_jit);
 #endif

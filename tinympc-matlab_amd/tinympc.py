@@ -319,7 +319,9 @@ class TinyMPC:
         instance, held over the horizon) or (nx, N, count) (a trajectory per instance), or a CUDA torch tensor with the same memory
         layout, (count, nx) or (count, N, nx) contiguous. set_x_ref() returns every instance to the shared reference. Goals run on
         layout D's goal form where the handle runs layout D; a converging batch beyond one resident set (16-lane shapes) runs it
-        with slot refill, bit-identical to the plain goal kernel (jit_info(): 'goal slot-refill'; TINYMPC_REFILL=0 switches it off)."""
+        with slot refill, bit-identical to the plain goal kernel (jit_info(): 'goal slot-refill'; TINYMPC_REFILL=0 switches it off).
+        Trajectories run on layout D's trajectory form after prepare(), and beyond that form's resident set (4,096 quadrotors at
+        N=50) with slot refill as well ('per-instance-trajectories slot-refill')."""
         self._check_setup()
         self._set_batch("references", (x_refs,), (self.nx,), (self.N,), self._L.tinympc_set_x_ref_batch,
                         self._L.tinympc_set_x_ref_batch_device, first, self.nx)
@@ -336,7 +338,8 @@ class TinyMPC:
         per instance, independent of N; (nx, T) on a single-instance solver -- or a CUDA torch tensor with the same memory layout,
         (count, T, nx) contiguous float64. Kept on the device: instance b at step k tracks columns min(k+i, T-1), i = 0..N-1, of its
         track, so a closed-loop tick uploads nothing but x0 (set_ref_step_batch, advance_ref_step, set_ref_auto_advance). The first
-        call must name the whole batch; set_x_ref() / a whole-batch set_x_ref_batch() leave the mode."""
+        call must name the whole batch; set_x_ref() / a whole-batch set_x_ref_batch() leave the mode. After prepare() a tick runs on
+        layout D's trajectory form, with slot refill for a converging batch beyond one resident set (see set_x_ref_batch)."""
         self._check_setup()
         self._set_track(x_tracks, self.nx, self._L.tinympc_set_x_ref_track_batch, self._L.tinympc_set_x_ref_track_batch_device, first)
 
@@ -407,7 +410,8 @@ class TinyMPC:
         memory layout, (count, nx) / (count, nu) or (count, N, nx) / (count, N-1, nu) contiguous float64. All four in the same form.
         Enables both bound families, as set_bound_constraints does; set_bound_constraints() returns every instance to shared bounds.
         One box per instance (beside references constant over the horizon) runs on layout D's goal form, with slot refill where a
-        shared box would have it (see set_x_ref_batch)."""
+        shared box would have it (see set_x_ref_batch); bounds per knot run on layout D's per-knot bounds form after prepare(), with
+        slot refill beyond that form's resident set ('per-knot-bounds slot-refill')."""
         self._check_setup()
         self._set_batch("bounds", (x_min, x_max, u_min, u_max), (self.nx, self.nx, self.nu, self.nu), (self.N, self.N, self.N - 1, self.N - 1),
                         self._L.tinympc_set_bound_constraints_batch, self._L.tinympc_set_bound_constraints_batch_device, first)
@@ -839,7 +843,9 @@ class TinyMPC:
         one of these and keeps the mode on layout A -- send it through set_x_ref_batch() to stay on layout D. Box bounds per knot and
         per instance (set_bound_constraints_batch with (nx, N, count) / (nu, N-1, count) arrays), with or without per-instance
         trajectories or tracks, run on layout D's per-knot bounds form where the horizon's clamp rows fit a wavefront's LDS share
-        (jit_info(): "... per-knot-bounds"; box path, the shared model and rho)."""
+        (jit_info(): "... per-knot-bounds"; box path, the shared model and rho). The trajectory and per-knot bounds forms run a
+        converging batch beyond one resident set with slot refill (jit_info(): "... slot-refill"); where such a form is already the
+        handle's, this call builds that variant too."""
         self._check_setup()
         self._push_settings()
         _lib.check(self._L.tinympc_prepare(self._h))
@@ -854,7 +860,8 @@ class TinyMPC:
     def jit_info(self) -> str:
         """Origin of the kernel of the current configuration: 'compiled-in ...', 'compiled ...', 'disk-cache ...' or
         'refused(<reason>)' (tinympc_get_jit_info). ' slot-refill' where the launch runs layout D's slot-refill variant: the shared
-        box path, or the goal form (one goal and / or one box per instance)."""
+        box path, the goal form (one goal and / or one box per instance), or after prepare() the trajectory and per-knot bounds forms
+        (a trajectory, track or bound schedule per instance)."""
         self._check_setup()
         self._push_settings()
         buf = C.create_string_buffer(1024)
