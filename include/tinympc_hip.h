@@ -595,6 +595,53 @@ int tinympc_collect_kernel_ms(tinympc_solver *s, float *kernel_ms, int capacity,
  * buffer the next launch reads, and tinympc_get_solution / tinympc_get_stats after a solve are host copies.) */
 int tinympc_mpc_step_batch(tinympc_solver *s, const double *x0s, double *u0_out);
 
+/* Closed-loop rollout on the device (batched handles outside a session; no reference counterpart). A closed-loop study is `ticks`
+ * times: solve, apply the first control to a plant, measure. With the plant on the host every tick is one upload of x0, one download
+ * of the first controls and one stream synchronisation around the solve; here the plant runs behind the solve on the handle's
+ * stream (k_plant_step, csrc/tinympc_rollout.hip) and the state never leaves the device.
+ *
+ * tinympc_rollout_batch starts from the x0 the handle holds (tinympc_set_x0_batch / _device) and queues, for t = 0 .. ticks-1,
+ * exactly what a tinympc_mpc_step_batch tick launches (the warm-started solve, x0 read from device memory) and then, for every
+ * instance b,
+ *     x_log[b][:, t] = x0[b],  u_log[b][:, t] = u,  iter_log[b][t],  status_log[b][t]     (u: the first control of that solve)
+ *     x0[b] <- A_p x0[b] + B_p u + f_p + disturbance[b][:, t]                              (and x_log[b][:, ticks] after the last tick)
+ * and the reference tracks' auto-advance where it is on (tinympc_set_ref_auto_advance). No host copy and no synchronisation
+ * between ticks, no graph capture; one synchronisation at the end, then the requested logs are copied out of device buffers the
+ * handle keeps (grown on demand, freed with the handle). Afterwards x0 holds the final state, and the ADMM state, the tracks' steps
+ * and every getter are as after the same ticks issued one by one (tinympc_solve + tinympc_plant_step_batch, bit for bit).
+ *   plant    A_p, B_p, f_p: the override of tinympc_set_plant_batch; else the instance's own model while per-instance models are on
+ *            (tinympc_set_model_batch); else the handle's shared A, B, fdyn.
+ *   order    per row one chain of fused multiply-adds, started from f_p (zero where there is none), over A_p's columns ascending,
+ *            continued over B_p's columns ascending; then + disturbance. Fixed: results are reproducible bit for bit.
+ *   layout   instance-major, the layout of the reference tracks: x_log nx x (ticks+1) x batch (instance b's block at
+ *            b nx (ticks+1)), u_log nu x ticks x batch, iter_log and status_log ticks x batch (instance b's row at b ticks),
+ *            disturbance nx x ticks x batch (NULL: none). A rollout's x_log can be handed as it is to
+ *            tinympc_set_x_ref_track_batch / _device of another handle (T = ticks+1).
+ *   logs     any member, or logs itself, may be NULL: that log is not written.
+ *   gpu_ms   (may be NULL) one event pair around the whole queue, in milliseconds.
+ * tinympc_rollout_batch_device writes the logs to, and reads the disturbance from, caller-owned device memory on the handle's GPU
+ * (d_logs is a host struct of device pointers). It returns once the work is QUEUED: the caller orders its reads behind the handle's
+ * stream (tinympc_get_stream, or tinympc_synchronize) and keeps the buffers alive until then.
+ * tinympc_plant_step_batch queues the plant step once, without logs -- the same kernel and arithmetic: x0 <- plant(x0, first controls
+ * of the last solve) + disturbance (host memory, nx x batch, or NULL). For callers that want to look at every tick.
+ * Refusals (nothing is queued or changed): TINYMPC_ERR_INVALID_INPUT for ticks < 1, for max_iter < 1 (a tick that writes no control
+ * cannot be rolled out) and for anything but the handle's GPU's memory handed to the _device form; TINYMPC_ERR_UNSUPPORTED for
+ * single-instance handles that answer through pinned host memory and inside a session; and whatever a launch of the current
+ * configuration refuses, with the launch's own code and message, before tick 0. */
+typedef struct { double *x_log, *u_log; int *iter_log, *status_log; } tinympc_rollout_logs;   /* any member may be NULL */
+int tinympc_rollout_batch(tinympc_solver *s, int ticks, const double *disturbance, const tinympc_rollout_logs *logs, float *gpu_ms);
+int tinympc_rollout_batch_device(tinympc_solver *s, int ticks, const double *d_disturbance, const tinympc_rollout_logs *d_logs);
+int tinympc_plant_step_batch(tinympc_solver *s, const double *disturbance);
+
+/* A plant that differs from the controller's model (model-mismatch and robustness studies): A is nx x nx x count, B nx x nu x count,
+ * f nx x count or NULL (no affine term), for instances first .. first+count-1; column-major blocks, one per instance. The first call
+ * must name the whole batch, later calls may replace sub-ranges. Everything is validated before anything is written (finite values;
+ * the _device form on the device, one flag read back). The controller is never touched: cache, operators, table rows and kernel
+ * plan stay as they are. tinympc_clear_plant_batch returns to the model's own plant. Batched handles only. */
+int tinympc_set_plant_batch(tinympc_solver *s, const double *A, const double *B, const double *f, int first, int count);
+int tinympc_set_plant_batch_device(tinympc_solver *s, const double *d_A, const double *d_B, const double *d_f, int first, int count);
+int tinympc_clear_plant_batch(tinympc_solver *s);
+
 /* Launch geometry of the solve kernel, for reports: lanes per instance, instances per wavefront,
  * workgroups in the grid, dynamic LDS bytes per workgroup, and whether the per-knot bound/reference
  * tables are LDS-resident. Any pointer may be NULL. */

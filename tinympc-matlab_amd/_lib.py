@@ -41,6 +41,11 @@ class CodegenData(C.Structure):
                 + [(n, c_double_p) for n in ("Q", "R", "Adyn", "Bdyn", "x_min", "x_max", "u_min", "u_max")])
 
 
+class RolloutLogs(C.Structure):
+    """tinympc_rollout_logs (include/tinympc_hip.h): host or device addresses, any of them 0 (that log is not written)."""
+    _fields_ = [("x_log", C.c_void_p), ("u_log", C.c_void_p), ("iter_log", C.c_void_p), ("status_log", C.c_void_p)]
+
+
 # name -> (restype, argtypes); mirrors include/tinympc_hip.h one to one
 SIGNATURES = {
     "tinympc_last_error": (C.c_char_p, []),
@@ -130,6 +135,12 @@ SIGNATURES = {
     "tinympc_prepare": (C.c_int, [Handle]),
     "tinympc_get_jit_info": (C.c_int, [Handle, C.c_char_p, C.c_int]),
     "tinympc_get_stream": (C.c_void_p, [Handle]),
+    "tinympc_rollout_batch": (C.c_int, [Handle, C.c_int, c_double_p, C.POINTER(RolloutLogs), C.POINTER(C.c_float)]),
+    "tinympc_rollout_batch_device": (C.c_int, [Handle, C.c_int, C.c_void_p, C.POINTER(RolloutLogs)]),
+    "tinympc_plant_step_batch": (C.c_int, [Handle, c_double_p]),
+    "tinympc_set_plant_batch": (C.c_int, [Handle, c_double_p, c_double_p, c_double_p, C.c_int, C.c_int]),
+    "tinympc_set_plant_batch_device": (C.c_int, [Handle, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+    "tinympc_clear_plant_batch": (C.c_int, [Handle]),
 }
 
 # include/tinympc_hip_bench.h: measurement helpers / diagnostics, not part of the drop-in boundary

@@ -3,6 +3,7 @@
 // tinympc_plan.hip; the resident session: tinympc_session.hip. Host-side bookkeeping only -- every number the solver produces is
 // computed by the kernels; there is no CPU fallback anywhere.
 #include "tinympc_handle.h"
+#include "tinympc_rollout.h"
 
 #include <atomic>
 #include <chrono>
@@ -2043,8 +2044,191 @@ int tinympc_get_solution_device_ptrs(tinympc_solver *s, const double **d_x, cons
 }
 
 
+// ---- closed-loop rollout on the device (k_plant_step, tinympc_rollout.hip)
+namespace {
 
+// A buffer of the rollout's host form: grown to `need` elements where it is smaller, otherwise left alone (never shrunk).
+extern "C++" template <typename T>
+int grow_rollout_buffer(tinympc_solver *s, T **p, size_t *cap, size_t need) {
+    if (need <= *cap && *p) return TINYMPC_OK;
+    dfree(s, *p);
+    *p = nullptr;
+    *cap = 0;
+    int rc = dalloc(s, p, need);
+    if (rc) return rc;
+    *cap = need;
+    return TINYMPC_OK;
+}
 
+// The plant of a step: the override, else the instance's own model while per-instance models are on, else the shared model.
+void fill_plant_operands(const tinympc_solver *s, PlantStepParams *p) {
+    const size_t nx = s->nx, nu = s->nu;
+    if (s->plant) {
+        p->A = s->pA; p->B = s->pB; p->f = s->pf;
+        p->A_stride = nx * nx; p->B_stride = nx * nu; p->f_stride = nx;
+    } else if (s->inst.models) {
+        p->A = s->inst.mA; p->B = s->inst.mB; p->f = s->inst.mf;
+        p->A_stride = nx * nx; p->B_stride = nx * nu; p->f_stride = nx;
+    } else {
+        p->A = s->dA; p->B = s->dB; p->f = s->dfdyn;
+        p->A_stride = p->B_stride = p->f_stride = 0;
+    }
+    p->nx = s->nx; p->nu = s->nu; p->batch = s->batch;
+    p->u_stride = s->U();
+    p->x0 = s->dx0; p->sol_u = s->dsolu; p->istats = s->distats;
+}
+
+// What both forms of the rollout refuse, before anything is queued or changed; on success the device is bound and the plan resolved.
+int rollout_refusals(tinympc_solver *s, const char *verb, int ticks) {
+    int rc = check_handle(s);
+    if (rc) return rc;
+    if (ticks < 1) return fail(TINYMPC_ERR_INVALID_INPUT, "%s: ticks must be >= 1 (got %d)", verb, ticks);
+    if (s->session_active || s->host_path()) return fail(TINYMPC_ERR_UNSUPPORTED, "%s: batched handles outside a session only", verb);
+    if (s->st.max_iter < 1)
+        return fail(TINYMPC_ERR_INVALID_INPUT, "%s: max_iter must be >= 1 (a tick of %d iterations writes no control to roll out)", verb, s->st.max_iter);
+    if ((rc = bind_device(s))) return rc;
+    if ((rc = resolve_plan(s))) return rc;  // (a run-time specialisation happens here, outside the queue)
+    return check_launch(s, current_plan(s));  // (the launch's own refusal, with its message)
+}
+
+// ticks x (what a tinympc_mpc_step_batch tick launches, x0 read from dx0; k_plant_step; the tracks' auto-advance) on the handle's
+// stream: no copy, no synchronisation, no graph.
+int queue_rollout(tinympc_solver *s, int ticks, const double *d_w, const tinympc_rollout_logs &d_logs) {
+    int rc;
+    PlantStepParams p{};
+    p.ticks = ticks;
+    p.w = d_w;
+    p.x_log = d_logs.x_log; p.u_log = d_logs.u_log; p.iter_log = d_logs.iter_log; p.status_log = d_logs.status_log;
+    for (int t = 0; t < ticks; ++t) {
+        if ((rc = refresh_derived(s))) return rc;
+        if ((rc = refresh_inst_tables(s))) return rc;
+        if ((rc = launch(s, false))) return rc;
+        fill_plant_operands(s, &p);
+        p.t = t;
+        HIP_TRY(launch_plant_step(p, s->W, s->KT, s->stream));
+        if (s->inst.auto_advance && (rc = advance_ref_steps_after_tick(s))) return rc;
+    }
+    return TINYMPC_OK;
+}
+
+// tinympc_set_plant_batch (+ _device)
+int set_plant_batch(tinympc_solver *s, const double *A, const double *B, const double *f, bool on_device, int first, int count) {
+    const char *verb = on_device ? "set_plant_batch_device" : "set_plant_batch";
+    int rc = check_handle(s);
+    if (rc) return rc;
+    if (!A || !B) return fail(TINYMPC_ERR_INVALID_INPUT, "%s requires A and B", verb);
+    if (first < 0 || count < 1 || first + count > s->batch)
+        return fail(TINYMPC_ERR_INVALID_INPUT, "%s: instance range [%d, %d) is empty or outside batch of %d", verb, first, first + count, s->batch);
+    if (s->session_active || s->host_path()) return fail(TINYMPC_ERR_UNSUPPORTED, "%s: batched handles outside a session only", verb);
+    if (!s->plant && (first != 0 || count != s->batch))
+        return fail(TINYMPC_ERR_INVALID_INPUT, "%s: the first call must name the whole batch (got [%d, %d) of %d)", verb, first, first + count, s->batch);
+    const size_t nx = s->nx, nu = s->nu, n = (size_t)count, batch = (size_t)s->batch;
+    if (on_device) {
+        if (!on_handles_device(s, A) || !on_handles_device(s, B) || (f && !on_handles_device(s, f)))
+            return fail(TINYMPC_ERR_INVALID_INPUT, "%s: the plant is not device memory of the handle's GPU %d", verb, s->device);
+        if ((rc = bind_device(s))) return rc;
+        InstState &in = s->inst;
+        if (!in.mflag && (rc = dalloc(s, &in.mflag, (size_t)1))) return rc;
+        int bad = 0;
+        HIP_TRY(hipMemsetAsync(in.mflag, 0, sizeof(int), s->stream));
+        HIP_TRY(launch_check_finite(A, nx * nx * n, in.mflag, s->stream));
+        HIP_TRY(launch_check_finite(B, nx * nu * n, in.mflag, s->stream));
+        if (f) HIP_TRY(launch_check_finite(f, nx * n, in.mflag, s->stream));
+        if ((rc = download(s, &bad, in.mflag, sizeof(int)))) return rc;
+        if (bad) return fail(TINYMPC_ERR_INVALID_INPUT, "%s: every entry of the plant must be finite", verb);
+    } else {
+        const double *arr[3] = {A, B, f};
+        const size_t len[3] = {nx * nx * n, nx * nu * n, nx * n};
+        const char *name[3] = {"A", "B", "f"};
+        for (int a = 0; a < 3; ++a)
+            for (size_t i = 0; arr[a] && i < len[a]; ++i)
+                if (!std::isfinite(arr[a][i])) return fail(TINYMPC_ERR_INVALID_INPUT, "%s: %s[%zu] = %g. Expected a finite number.", verb, name[a], i, arr[a][i]);
+        if ((rc = bind_device(s))) return rc;
+    }
+    if (!s->pA && ((rc = dalloc(s, &s->pA, nx * nx * batch)) || (rc = dalloc(s, &s->pB, nx * nu * batch)) || (rc = dalloc(s, &s->pf, nx * batch)))) return rc;
+    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    HIP_TRY(hipMemcpyAsync(s->pA + (size_t)first * nx * nx, A, sizeof(double) * nx * nx * n, kind, s->stream));
+    HIP_TRY(hipMemcpyAsync(s->pB + (size_t)first * nx * nu, B, sizeof(double) * nx * nu * n, kind, s->stream));
+    if (f) HIP_TRY(hipMemcpyAsync(s->pf + (size_t)first * nx, f, sizeof(double) * nx * n, kind, s->stream));
+    else HIP_TRY(hipMemsetAsync(s->pf + (size_t)first * nx, 0, sizeof(double) * nx * n, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));  // (the caller keeps ownership of its buffers: copied when the call returns)
+    s->plant = true;
+    return TINYMPC_OK;
+}
+
+}  // namespace
+
+int tinympc_rollout_batch(tinympc_solver *s, int ticks, const double *disturbance, const tinympc_rollout_logs *logs, float *gpu_ms) {
+    int rc = rollout_refusals(s, "rollout_batch", ticks);
+    if (rc) return rc;
+    const size_t nx = s->nx, nu = s->nu, batch = s->batch, T = (size_t)ticks;
+    const tinympc_rollout_logs want = logs ? *logs : tinympc_rollout_logs{nullptr, nullptr, nullptr, nullptr};
+    tinympc_rollout_logs d{nullptr, nullptr, nullptr, nullptr};
+    if (want.x_log) { if ((rc = grow_rollout_buffer(s, &s->rl_x, &s->rl_x_cap, nx * (T + 1) * batch))) return rc; d.x_log = s->rl_x; }
+    if (want.u_log) { if ((rc = grow_rollout_buffer(s, &s->rl_u, &s->rl_u_cap, nu * T * batch))) return rc; d.u_log = s->rl_u; }
+    if (want.iter_log) { if ((rc = grow_rollout_buffer(s, &s->rl_it, &s->rl_it_cap, T * batch))) return rc; d.iter_log = s->rl_it; }
+    if (want.status_log) { if ((rc = grow_rollout_buffer(s, &s->rl_st, &s->rl_st_cap, T * batch))) return rc; d.status_log = s->rl_st; }
+    if (disturbance) {
+        if ((rc = grow_rollout_buffer(s, &s->rl_w, &s->rl_w_cap, nx * T * batch))) return rc;
+        if ((rc = upload(s, s->rl_w, disturbance, nx * T * batch))) return rc;
+    }
+    if (gpu_ms) HIP_TRY(hipEventRecord(s->ev0, s->stream));
+    if ((rc = queue_rollout(s, ticks, disturbance ? s->rl_w : nullptr, d))) return rc;
+    if (gpu_ms) HIP_TRY(hipEventRecord(s->ev1, s->stream));
+    // the one synchronisation of the rollout, then the requested logs
+    if (d.x_log) HIP_TRY(hipMemcpyAsync(want.x_log, d.x_log, sizeof(double) * nx * (T + 1) * batch, hipMemcpyDeviceToHost, s->stream));
+    if (d.u_log) HIP_TRY(hipMemcpyAsync(want.u_log, d.u_log, sizeof(double) * nu * T * batch, hipMemcpyDeviceToHost, s->stream));
+    if (d.iter_log) HIP_TRY(hipMemcpyAsync(want.iter_log, d.iter_log, sizeof(int) * T * batch, hipMemcpyDeviceToHost, s->stream));
+    if (d.status_log) HIP_TRY(hipMemcpyAsync(want.status_log, d.status_log, sizeof(int) * T * batch, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    if (gpu_ms) HIP_TRY(hipEventElapsedTime(gpu_ms, s->ev0, s->ev1));
+    return TINYMPC_OK;
+}
+
+int tinympc_rollout_batch_device(tinympc_solver *s, int ticks, const double *d_disturbance, const tinympc_rollout_logs *d_logs) {
+    int rc = check_handle(s);
+    if (rc) return rc;
+    const tinympc_rollout_logs d = d_logs ? *d_logs : tinympc_rollout_logs{nullptr, nullptr, nullptr, nullptr};
+    const void *ptrs[5] = {d_disturbance, d.x_log, d.u_log, d.iter_log, d.status_log};
+    for (const void *q : ptrs)
+        if (q && !on_handles_device(s, q))
+            return fail(TINYMPC_ERR_INVALID_INPUT, "rollout_batch_device: the disturbance and the logs must be device memory of the handle's GPU %d", s->device);
+    if ((rc = rollout_refusals(s, "rollout_batch_device", ticks))) return rc;
+    return queue_rollout(s, ticks, d_disturbance, d);
+}
+
+int tinympc_plant_step_batch(tinympc_solver *s, const double *disturbance) {
+    int rc = check_handle(s);
+    if (rc) return rc;
+    if (s->session_active || s->host_path()) return fail(TINYMPC_ERR_UNSUPPORTED, "plant_step_batch: batched handles outside a session only");
+    if ((rc = bind_device(s))) return rc;
+    if ((rc = materialize_zero_solution(s))) return rc;  // (no solve since a reset: the first controls are zeros)
+    const size_t n = (size_t)s->nx * s->batch;
+    if (disturbance) {
+        if ((rc = grow_rollout_buffer(s, &s->rl_w, &s->rl_w_cap, n))) return rc;
+        if ((rc = upload(s, s->rl_w, disturbance, n))) return rc;
+    }
+    PlantStepParams p{};
+    fill_plant_operands(s, &p);
+    p.t = 0; p.ticks = 1;
+    p.w = disturbance ? s->rl_w : nullptr;
+    HIP_TRY(launch_plant_step(p, s->W, s->KT, s->stream));
+    return TINYMPC_OK;
+}
+
+int tinympc_set_plant_batch(tinympc_solver *s, const double *A, const double *B, const double *f, int first, int count) {
+    return set_plant_batch(s, A, B, f, false, first, count);
+}
+int tinympc_set_plant_batch_device(tinympc_solver *s, const double *d_A, const double *d_B, const double *d_f, int first, int count) {
+    return set_plant_batch(s, d_A, d_B, d_f, true, first, count);
+}
+
+int tinympc_clear_plant_batch(tinympc_solver *s) {
+    int rc = check_handle(s);
+    if (rc) return rc;
+    s->plant = false;  // (the stores stay for the next override)
+    return TINYMPC_OK;
+}
 
 #ifdef TINY_CLOCK_STAMP
 // Diagnostic build only (not part of the ABI): the stamp records of the last layout-D launch, 8 values per wavefront (see the

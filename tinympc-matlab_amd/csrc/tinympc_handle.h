@@ -312,6 +312,16 @@ struct tinympc_solver {
         return (inst.x ? inst.x_const : xref_const) && (inst.u ? inst.u_const : uref_const) &&
                (inst.bounds ? inst.bounds_const : xmin_const && xmax_const && umin_const && umax_const);
     }
+    // Closed-loop rollout on the device (tinympc_rollout_batch / _device, tinympc_plant_step_batch; k_plant_step, tinympc_rollout.hip).
+    // The plant override (tinympc_set_plant_batch): every instance's A_p | B_p | f_p, [batch] blocks, on from the first call (which names
+    // the whole batch) until tinympc_clear_plant_batch; the stores stay for the next override. Nothing of the controller reads them.
+    bool plant = false;
+    double *pA = nullptr, *pB = nullptr, *pf = nullptr;
+    // ... and the device buffers the host form logs into and stages its disturbance in: grown on demand (capacities in elements), never
+    // shrunk, freed with the handle
+    double *rl_x = nullptr, *rl_u = nullptr, *rl_w = nullptr;
+    int *rl_it = nullptr, *rl_st = nullptr;
+    size_t rl_x_cap = 0, rl_u_cap = 0, rl_w_cap = 0, rl_it_cap = 0, rl_st_cap = 0;
     size_t lds_bytes_a = 0;       // layout-A LDS plan (layout B, where it runs, replaces lds_bytes; the families and adaptive rho always use layout A)
     bool tables_in_lds_a = false;
 
@@ -420,6 +430,7 @@ struct LaunchPlan {
 };
 LaunchPlan current_plan(const tinympc_solver *s);  // from what has been decided so far (compiles nothing)
 int resolve_plan(tinympc_solver *s);               // decide (and, where needed, specialise) the variants of the current configuration
+int check_launch(const tinympc_solver *s, const LaunchPlan &pl);  // what launch() refuses for plan `pl`, with its message; queues and changes nothing
 int launch(tinympc_solver *s, bool timed);
 
 // ---- tinympc_session.hip

@@ -505,11 +505,9 @@ static const char *lean_words(const tinympc_solver *s, const LaunchPlan &pl) {
                                   : " lean";
 }
 
-int launch(tinympc_solver *s, bool timed) {
-    int rc;
-    s->flag_pending = false;
-    if ((rc = resolve_plan(s))) return rc;
-    const LaunchPlan pl = current_plan(s);
+// Everything launch() refuses, for plan `pl` of the current configuration: host-side tests only. launch() runs it before it queues or
+// rebuilds anything; tinympc_rollout_batch runs it before tick 0, so that a refused rollout has queued nothing.
+int check_launch(const tinympc_solver *s, const LaunchPlan &pl) {
     const bool fam = pl.families, adaptive = pl.adaptive;
     if (s->inst.fam() && !pl.inst_lin) {  // never a solve with shared rows or slopes in their place
         const char *why = s->layout_m ? "for systems with nx+nu > 64"
@@ -543,12 +541,6 @@ int launch(tinympc_solver *s, bool timed) {
         return fail(TINYMPC_ERR_UNSUPPORTED, "%s are not supported %s; %s", subj.c_str(),
                     s->layout_m ? "for systems with nx+nu > 64" : fam ? "with cone / linear constraint families" : "with adaptive rho", way.c_str());
     }
-    // k_build_adapt reads the device copy of the references before the solve kernel starts: bring the device copies and the tables up
-    // to date the ordinary way (every other kernel of a single-instance handle stages references left in pinned host memory itself)
-    if (s->refs_on_host && (adaptive || pl.inst_models)) {  // (... and so are the per-instance rows of the models' variant)
-        if ((rc = flush_host_refs(s))) return rc;
-    }
-    if ((rc = refresh_derived(s))) return rc;
     if (adaptive && fam)
         return fail(TINYMPC_ERR_UNSUPPORTED, "adaptive_rho together with cone / linear constraint families is not supported");
     if (s->layout_m && adaptive)
@@ -557,6 +549,22 @@ int launch(tinympc_solver *s, bool timed) {
         return fail(TINYMPC_ERR_UNSUPPORTED, "more than %d linear rows per side, %d cones or %d rounds of overlapping cones run on the run-time "
                     "specialised kernels only (nx+nu <= 16, TINYMPC_JIT not 0): this configuration has none (%s)", MAX_LIN_ROWS, MAX_CONES, MAX_ROUNDS,
                     s->W != 16 ? "nx+nu > 16" : "the specialiser refused it, see tinympc_get_jit_info");
+    return TINYMPC_OK;
+}
+
+int launch(tinympc_solver *s, bool timed) {
+    int rc;
+    s->flag_pending = false;
+    if ((rc = resolve_plan(s))) return rc;
+    const LaunchPlan pl = current_plan(s);
+    const bool fam = pl.families, adaptive = pl.adaptive;
+    if ((rc = check_launch(s, pl))) return rc;
+    // k_build_adapt reads the device copy of the references before the solve kernel starts: bring the device copies and the tables up
+    // to date the ordinary way (every other kernel of a single-instance handle stages references left in pinned host memory itself)
+    if (s->refs_on_host && (adaptive || pl.inst_models)) {  // (... and so are the per-instance rows of the models' variant)
+        if ((rc = flush_host_refs(s))) return rc;
+    }
+    if ((rc = refresh_derived(s))) return rc;
     if (adaptive) {  // tiny tables from the current cache, sensitivities and Xref; rebuilt per launch (a few microseconds)
         AdaptTableParams a{};
         a.nx = s->nx; a.nu = s->nu; a.N = s->N; a.W = s->W; a.KT = s->KT;

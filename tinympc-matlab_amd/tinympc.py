@@ -648,6 +648,126 @@ class TinyMPC:
         _lib.check(self._L.tinympc_get_cache_batch(self._h, _p(K), _p(P), _p(Qi), _p(Am), it.ctypes.data_as(_lib.c_int_p), int(first), int(count)))
         return dict(Kinf=K, Pinf=P, Quu_inv=Qi, AmBKt=Am, riccati_iters=it)
 
+    # ------------------------------------------------------------------ closed-loop rollout on the device
+    _ROLLOUT_LOGS = ("x", "u", "iter", "status")
+
+    def rollout(self, ticks: int, disturbance=None, log=("x", "u", "iter", "status"), out=None) -> dict:
+        """`ticks` closed-loop ticks on the device, from the x0 the solver holds: solve, log, x0 <- plant(x0, first control) +
+        disturbance, the tracks' auto-advance -- no copy and no synchronisation between ticks (include/tinympc_hip.h,
+        tinympc_rollout_batch). Returns a dict of the logs named in `log`: "x" (nx, ticks+1, batch), "u" (nu, ticks, batch), "iter" and
+        "status" (ticks, batch) int32, and "gpu_ms", the device time of the whole queue. disturbance: (nx, ticks, batch) or None.
+        The device form -- a CUDA torch tensor (batch, ticks, nx) for the disturbance, and / or `out`, a dict of contiguous CUDA tensors
+        "x" (batch, ticks+1, nx), "u" (batch, ticks, nu) float64, "iter" / "status" (batch, ticks) int32 (the same memory) -- logs
+        into the tensors. With `out` the call returns once the work is queued: order reads behind the solver's stream
+        (synchronize()). Without it the tensors are allocated here and the call waits."""
+        self._check_setup()
+        E = _lib.ERR_INVALID_INPUT
+        ticks = int(ticks)
+        if ticks < 1:
+            raise TinyMPCError(E, "rollout: ticks must be >= 1 (got %d)" % ticks)
+        log = tuple(log) if out is None else tuple(out)
+        if any(k not in self._ROLLOUT_LOGS for k in log):
+            raise TinyMPCError(E, "rollout: logs are named %s, got %s" % (self._ROLLOUT_LOGS, log))
+        nx, nu, B = self.nx, self.nu, self.batch
+        w_dev = hasattr(disturbance, "data_ptr") and getattr(disturbance, "is_cuda", False)
+        if w_dev or out is not None:
+            import torch
+            shapes = {"x": (B, ticks + 1, nx), "u": (B, ticks, nu), "iter": (B, ticks), "status": (B, ticks)}
+            dtypes = {"x": torch.float64, "u": torch.float64, "iter": torch.int32, "status": torch.int32}
+            if disturbance is not None and not w_dev:
+                raise TinyMPCError(E, "rollout: with out= the disturbance must be a CUDA tensor (or None)")
+            if w_dev and (disturbance.dtype != torch.float64 or not disturbance.is_contiguous() or tuple(disturbance.shape) != (B, ticks, nx)):
+                raise TinyMPCError(E, "rollout: the disturbance on the device must be a contiguous float64 tensor of shape (%d, %d, %d), got %s %s"
+                                   % (B, ticks, nx, disturbance.dtype, tuple(disturbance.shape)))
+            own = out is None
+            if own:
+                out = {k: torch.empty(shapes[k], dtype=dtypes[k], device=disturbance.device) for k in log}
+            for k, t in out.items():
+                if not (hasattr(t, "data_ptr") and getattr(t, "is_cuda", False)) or t.dtype != dtypes[k] or not t.is_contiguous() or tuple(t.shape) != shapes[k]:
+                    raise TinyMPCError(E, "rollout: out[%r] must be a contiguous CUDA %s tensor of shape %s" % (k, dtypes[k], shapes[k]))
+            logs = _lib.RolloutLogs(*[out[k].data_ptr() if k in out else None for k in self._ROLLOUT_LOGS])
+            for t in list(out.values()) + ([disturbance] if w_dev else []):
+                torch.cuda.current_stream(t.device).synchronize()  # (the set_x0_batch contract)
+            _lib.check(self._L.tinympc_rollout_batch_device(self._h, ticks, C.c_void_p(disturbance.data_ptr()) if w_dev else None, C.byref(logs)))
+            if own:
+                self.synchronize()
+            return out
+        w = None
+        if disturbance is not None:
+            w = np.asarray(disturbance, dtype=np.float64)
+            if w.shape != (nx, ticks, B):
+                raise TinyMPCError(E, "rollout: the disturbance must be %d x %d x %d (nx x ticks x batch), got %s" % (nx, ticks, B, w.shape))
+            w = _f(w)
+        res = {}
+        if "x" in log:
+            res["x"] = np.zeros((nx, ticks + 1, B), order="F")
+        if "u" in log:
+            res["u"] = np.zeros((nu, ticks, B), order="F")
+        for k in ("iter", "status"):
+            if k in log:
+                res[k] = np.zeros((ticks, B), dtype=np.int32, order="F")
+        logs = _lib.RolloutLogs(*[res[k].ctypes.data if k in res else None for k in self._ROLLOUT_LOGS])
+        ms = C.c_float(0.0)
+        _lib.check(self._L.tinympc_rollout_batch(self._h, ticks, _p(w) if w is not None else None, C.byref(logs), C.byref(ms)))
+        res["gpu_ms"] = float(ms.value)
+        return res
+
+    def plant_step(self, disturbance=None):
+        """x0 <- plant(x0, first controls of the last solve) + disturbance, on the device (tinympc_plant_step_batch): the rollout's
+        plant step on its own. disturbance: (nx, batch) or None."""
+        self._check_setup()
+        w = None
+        if disturbance is not None:
+            w = np.asarray(disturbance, dtype=np.float64)
+            if w.shape != (self.nx, self.batch):
+                raise TinyMPCError(_lib.ERR_INVALID_INPUT, "plant_step: the disturbance must be %d x %d (nx x batch), got %s" % (self.nx, self.batch, w.shape))
+            w = _f(w)
+        _lib.check(self._L.tinympc_plant_step_batch(self._h, _p(w) if w is not None else None))
+
+    def set_plant_batch(self, A, B, f=None, first: int = 0):
+        """A plant that differs from the controller's model, for instances first, first+1, ...: numpy arrays A (nx, nx, count),
+        B (nx, nu, count) and, optionally, f (nx, count) -- or contiguous float64 CUDA tensors with the same memory layout, (count, nx, nx)
+        holding A_b', (count, nu, nx) holding B_b', (count, nx). The first call names the whole batch. rollout() and plant_step() then
+        advance the state with it; the controller is untouched. clear_plant_batch() returns to the model's own plant."""
+        self._check_setup()
+        nx, nu = self.nx, self.nu
+        arrays = [A, B] + ([f] if f is not None else [])
+        shapes = [(nx, nx), (nx, nu)] + ([(nx,)] if f is not None else [])
+        if any(a is None for a in arrays):
+            raise TinyMPCError(_lib.ERR_INVALID_INPUT, "plant: A and B are required")
+        on_device = [hasattr(a, "data_ptr") and getattr(a, "is_cuda", False) for a in arrays]
+        if any(on_device):
+            import torch
+            if not all(on_device):
+                raise TinyMPCError(_lib.ERR_INVALID_INPUT, "plant: all must be CUDA tensors, or none")
+            for a, sh in zip(arrays, shapes):
+                if a.dtype != torch.float64 or not a.is_contiguous() or a.dim() != len(sh) + 1 or tuple(a.shape[1:]) != tuple(reversed(sh)):
+                    raise TinyMPCError(_lib.ERR_INVALID_INPUT, "plant on the device must be contiguous float64 tensors of shape (count, %s), got %s %s"
+                                       % (", ".join(str(d) for d in reversed(sh)), a.dtype, tuple(a.shape)))
+            counts = {int(a.shape[0]) for a in arrays}
+            ptrs = [C.c_void_p(a.data_ptr()) for a in arrays] + ([None] if f is None else [])
+            fn = "tinympc_set_plant_batch_device"
+        else:
+            arrays = [np.asarray(a, dtype=np.float64) for a in arrays]
+            for a, sh in zip(arrays, shapes):
+                if a.ndim != len(sh) + 1 or tuple(a.shape[:-1]) != sh:
+                    raise TinyMPCError(_lib.ERR_INVALID_INPUT, "plant must be %s x count, got %s" % (" x ".join(str(d) for d in sh), a.shape))
+            counts = {int(a.shape[-1]) for a in arrays}
+            arrays = [_f(a) for a in arrays]
+            ptrs = [_p(a) for a in arrays] + ([None] if f is None else [])
+            fn = "tinympc_set_plant_batch"
+        if len(counts) != 1:
+            raise TinyMPCError(_lib.ERR_INVALID_INPUT, "plant: all must have the same count")
+        (count,) = counts
+        if on_device[0]:
+            torch.cuda.current_stream(arrays[0].device).synchronize()  # (the set_x0_batch contract)
+        _lib.check(getattr(self._L, fn)(self._h, *ptrs, int(first), count))
+
+    def clear_plant_batch(self):
+        """rollout() and plant_step() advance every instance with the controller's own model again."""
+        self._check_setup()
+        _lib.check(self._L.tinympc_clear_plant_batch(self._h))
+
     def _set_batch(self, what, arrays, rows, full, f_host, f_device, first, *extra):
         """The per-instance verbs: numpy arrays of shape (rows, count) / (rows, cols, count), or contiguous float64 CUDA tensors with the
         same memory layout, (count, rows) / (count, cols, rows) -- one column held over the horizon, or cols = full. All arrays in the

@@ -1,0 +1,154 @@
+"""Closed-loop rollout at bench size: what a tick costs with the plant on the host and with the plant on the device.
+
+`--batch` quadrotors at N = 50, tolerances 1e-3, max_iter 100, seeded x0 (tools/bench_legs.py's tick workload), a warm-started closed
+loop of `--ticks` ticks with the model's own plant. The legs, wall time per tick:
+  a   the library of the PARENT commit at --parent-lib: mpc_step per tick (x0 up, first controls down, one synchronisation), the plant
+      x <- A x + B u in numpy between ticks -- the host loop a closed-loop study is written as today
+  b   this tree's library, the ticks issued one by one with the state staying on the device: solve (launch + synchronisation) and
+      plant_step per tick, no copy in either direction
+  c   this tree's library, ONE rollout call for all ticks, all four logs requested: the copy-out into pageable host memory at the end
+      (220 MB at 8,192 instances and 200 ticks, most of it the states) is inside the measured time; beside it the device time of the
+      queue (gpu_ms, one event pair)
+  c0  the same call with no logs (log=()): the queue and its one synchronisation alone
+Every measurement is a fresh process -- the two libraries alternate, `--rounds` times each -- so the legs share one call's noise. Before
+the counted ticks every leg runs WARMUP ticks the same way (first launch, table builds, staging buffers; leg c also one rollout of the
+full length, so that its log buffers exist), then starts again from the seeded x0 with a cold ADMM state. The legs' plants differ in
+rounding (numpy's dot product against the kernel's chain), so their trajectories agree to rounding, not bit for bit: the mean
+iterations per tick are printed beside the times. The bar: leg c below leg a in every round at 4,096 and 8,192 instances (the exit
+status says so); at 256, where the zero-copy tick is already lean, the line says which way it went.
+    python tools/rollout_sweep.py --parent-lib /path/to/parent/libtinympc_hip.so [--batches 256,4096,8192] [--ticks 200] [--rounds 4]"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+WARMUP = 3
+
+
+def run_leg(pkg, leg, batch, ticks):
+    """-> (wall us per tick over the counted ticks, mean iterations per tick, kernel line)"""
+    P = pkg.problems
+    prob = P.quadrotor(50)
+    s = pkg.TinyMPC()
+    s.setup(prob.A, prob.B, prob.Q, prob.R, prob.N, batch=batch, rho=prob.rho, max_iter=100, abs_pri_tol=1e-3, abs_dua_tol=1e-3)
+    s.set_bound_constraints(prob.x_min, prob.x_max, prob.u_min, prob.u_max)
+    x0 = np.asfortranarray(P.quadrotor_batch_x0(batch))
+
+    def loop(n):
+        """n ticks from the state the handle holds (leg a: from x) -> (seconds, iterations per tick)"""
+        nonlocal x
+        its = []
+        t0 = time.perf_counter()
+        if leg in ("c", "c0"):
+            log = s.rollout(n, log=("x", "u", "iter", "status") if leg == "c" else ())
+            gpu_us.append(1e3 * log["gpu_ms"] / n)
+            return time.perf_counter() - t0, log["iter"].mean(axis=1) if leg == "c" else []
+        for _ in range(n):
+            if leg == "a":
+                u = s.mpc_step(x)
+                x = np.asfortranarray(prob.A @ x + prob.B @ u)
+            else:
+                s.solve()
+                s.plant_step()
+        dt = time.perf_counter() - t0
+        return dt, its
+
+    def restart():
+        nonlocal x
+        s.reset_workspace()
+        x = x0.copy(order="F")
+        s.set_x0_batch(x0)
+
+    x = x0.copy(order="F")
+    gpu_us = []
+    s.set_x0_batch(x0)
+    if leg in ("c", "c0"):
+        loop(ticks)
+        restart()
+    loop(WARMUP)
+    restart()
+    dt, its = loop(ticks)
+    iters = float(np.mean(its)) if len(its) else float("nan")
+    info = "%s %s" % (s.launch_info()["layout"], s.jit_info())
+    s.reset()
+    return 1e6 * dt / ticks, iters, info, (gpu_us[-1] if gpu_us else None)
+
+
+def child(pkg, a):
+    has = hasattr(pkg.load_library(), "tinympc_rollout_batch")
+    out = dict(library="this" if has else "parent", tick_us={}, iters={}, kernel={}, gpu_us={})
+    for leg in (("b", "c", "c0") if has else ("a",)):
+        us, iters, info, gpu = run_leg(pkg, leg, a.batch, a.ticks)
+        out["tick_us"][leg], out["iters"][leg], out["kernel"][leg], out["gpu_us"][leg] = us, iters, info, gpu
+    print("ROLLOUT-CHILD " + json.dumps(out), flush=True)
+
+
+def sweep(a):
+    """The parent: starts the children (it never opens the GPU itself) and prints the table."""
+    if not a.parent_lib or not os.path.exists(a.parent_lib):
+        raise SystemExit("needs --parent-lib: libtinympc_hip.so built from the parent commit")
+    ok = True
+    for batch in [int(b) for b in a.batches.split(",")]:
+        rows = {"this": [], "parent": []}
+        for rnd in range(a.rounds):
+            for lib in ("this", "parent") if rnd % 2 == 0 else ("parent", "this"):
+                env = dict(os.environ)
+                env.pop("TINYMPC_HIP_LIBRARY", None)
+                if lib == "parent":
+                    env["TINYMPC_HIP_LIBRARY"] = os.path.abspath(a.parent_lib)
+                cmd = [sys.executable, os.path.abspath(__file__), "--child", "--batch", str(batch), "--ticks", str(a.ticks)]
+                r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)
+                line = [l for l in r.stdout.splitlines() if l.startswith("ROLLOUT-CHILD ")]
+                if r.returncode != 0 or not line:
+                    raise SystemExit("batch %d round %d (%s) failed with %d:\n%s\n%s" % (batch, rnd, lib, r.returncode, r.stdout[-2000:], r.stderr[-2000:]))
+                rec = json.loads(line[0][len("ROLLOUT-CHILD "):])
+                assert rec["library"] == lib, rec
+                rows[lib].append(rec)
+                print("# batch %d round %d %-6s %s" % (batch, rnd, lib, json.dumps(rec["tick_us"])), flush=True)
+        print("closed-loop rollout, %d quadrotors N=50, tolerances 1e-3, max_iter 100, %d warm-started ticks, wall us per tick (%d rounds, a fresh "
+              "process each, the two libraries alternating)" % (batch, a.ticks, a.rounds))
+        print("%-58s | %-36s | %-9s | %-19s | %s" % ("leg", "rounds", "median", "spread", "iterations / tick"))
+        med = {}
+        for leg, lib, name in (("a", "parent", "a  mpc_step + the plant in numpy (parent)"), ("b", "this", "b  solve + plant_step per tick, state on the device"),
+                               ("c", "this", "c  one rollout call, all logs copied out"), ("c0", "this", "c0 one rollout call, no logs")):
+            v = [r["tick_us"][leg] for r in rows[lib]]
+            med[leg] = float(np.median(v))
+            it = rows[lib][0]["iters"][leg]
+            print("%-58s | %-36s | %9.1f | %8.1f - %8.1f | %s" % (name, " ".join("%.1f" % x for x in v), med[leg], min(v), max(v),
+                                                                 "%.2f" % it if it == it else "not read"))
+        print("kernel: %s" % rows["this"][0]["kernel"]["c"])
+        print("device time of the queue per tick (gpu_ms / ticks, median of the rounds): c %.1f us, c0 %.1f us"
+              % (float(np.median([r["gpu_us"]["c"] for r in rows["this"]])), float(np.median([r["gpu_us"]["c0"] for r in rows["this"]]))))
+        below = all(rc["tick_us"]["c"] < ra["tick_us"]["a"] for rc, ra in zip(rows["this"], rows["parent"]))
+        print("batch %d: c against a %.2fx, c0 against a %.2fx, c0 against b %.2fx; c below a in every round: %s\n"
+              % (batch, med["a"] / med["c"], med["a"] / med["c0"], med["b"] / med["c0"], "yes" if below else "NO"))
+        if batch >= 4096 and not below:
+            ok = False
+    if not ok:
+        raise SystemExit(1)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batches", default="256,4096,8192")
+    ap.add_argument("--batch", type=int, default=8192, help=argparse.SUPPRESS)
+    ap.add_argument("--ticks", type=int, default=200)
+    ap.add_argument("--rounds", type=int, default=4)
+    ap.add_argument("--parent-lib", default="")
+    ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
+    a = ap.parse_args()
+    if not a.child:
+        return sweep(a)
+    import __graft_entry__ as ge
+    child(ge.load_package(), a)
+
+
+if __name__ == "__main__":
+    main()
