@@ -642,6 +642,42 @@ int tinympc_set_plant_batch(tinympc_solver *s, const double *A, const double *B,
 int tinympc_set_plant_batch_device(tinympc_solver *s, const double *d_A, const double *d_B, const double *d_f, int first, int count);
 int tinympc_clear_plant_batch(tinympc_solver *s);
 
+/* Rollout metrics: what a closed-loop study wants of a rollout is a few numbers per instance, not every state of every tick. While
+ * the metrics are on, every plant step the handle queues (tinympc_rollout_batch / _device of any length, in any number of calls, and
+ * tinympc_plant_step_batch) runs the scored variant of k_plant_step, which moves one row of 8 doubles per instance on, in device
+ * memory the handle owns ([batch][8], allocated by the first call, freed with the handle). A scored rollout without logs moves
+ * 64 bytes per instance to the host instead of the logs. With x = x0[b] before the step, u the first control of the solve that
+ * just ran, xr / ur the reference that solve tracked at knot 0, lo / hi its bounds at knot 0, e = x - xr, d = u - ur, and t the
+ * steps since the reset:
+ *   [0] steps accumulated
+ *   [1] cost: the running sum of qx_i (e_i e_i) over the state rows ascending, then ru_j (d_j d_j) over the input rows ascending
+ *   [2] max over steps and rows of max(0, lo_i - x_i, x_i - hi_i)      (0 while en_state_bound is off)
+ *   [3] the same for u against the input bounds                          (0 while en_input_bound is off)
+ *   [4] sum of the iteration counts      [5] most iterations of one step      [6] steps whose status is not TINYMPC_STATUS_SOLVED
+ *   [7] settle step: t + 1 of the last step with max_i |e_i| > settle_tol; 0 if there was none, or if settle_tol <= 0
+ * Counts are stored as doubles and are exact.
+ *   order    slot 1 is ONE chain per step: it starts from the stored cost and adds one term per row, state rows ascending, then input
+ *            rows ascending; every product is rounded once (e e, then times the weight) and nothing is contracted into the add.
+ *            Fixed: the rows are reproducible bit for bit, a rollout of T ticks equals two of T/2, and a sequential float64
+ *            restatement reproduces them exactly.
+ *   xr, ur   what the solve used: a half in track mode, column min(step[b], T - 1) of the instance's track, read before the
+ *            auto-advance; else the instance's own reference (tinympc_set_x_ref_batch / _u_ref_batch), column 0; else the shared one,
+ *            column 0. lo, hi: the instance's bounds where tinympc_set_bound_constraints_batch is on, else the shared ones, column 0.
+ * tinympc_set_rollout_metrics turns the metrics on (or replaces the weights: qx nx values, ru nu values, shared by the batch) and
+ * zeroes every row; tinympc_reset_rollout_metrics zeroes the rows, queued on the handle's stream; tinympc_clear_rollout_metrics turns
+ * them off: steps run the plain kernel again. tinympc_get_rollout_metrics copies the rows out (8 x batch, row b at 8 b) and
+ * synchronises; the _device_ptr form hands out the rows themselves: order reads behind the handle's stream. x0, the logs, the ADMM
+ * state and every getter are bit for bit what they are without the metrics.
+ * Refusals (nothing is queued or changed): TINYMPC_ERR_UNSUPPORTED for single-instance handles that answer through pinned host memory
+ * and inside a session; TINYMPC_ERR_INVALID_INPUT for a NULL qx or ru, a weight that is negative or not finite, a settle_tol that is
+ * not finite, and for get / reset / device_ptr while the metrics are off. */
+typedef struct { const double *qx, *ru; double settle_tol; } tinympc_rollout_score;  /* qx: nx weights, ru: nu weights, shared by the batch */
+int tinympc_set_rollout_metrics(tinympc_solver *s, const tinympc_rollout_score *score);  /* on (or re-weighted), and reset */
+int tinympc_reset_rollout_metrics(tinympc_solver *s);                                   /* zero every row, queued on the stream */
+int tinympc_clear_rollout_metrics(tinympc_solver *s);                                   /* off: steps run the plain kernel again */
+int tinympc_get_rollout_metrics(tinympc_solver *s, double *out);                        /* 8 x batch, synchronises */
+int tinympc_get_rollout_metrics_device_ptr(tinympc_solver *s, const double **d_rows);    /* ordered behind the handle's stream */
+
 /* Launch geometry of the solve kernel, for reports: lanes per instance, instances per wavefront,
  * workgroups in the grid, dynamic LDS bytes per workgroup, and whether the per-knot bound/reference
  * tables are LDS-resident. Any pointer may be NULL. */

@@ -46,6 +46,11 @@ class RolloutLogs(C.Structure):
     _fields_ = [("x_log", C.c_void_p), ("u_log", C.c_void_p), ("iter_log", C.c_void_p), ("status_log", C.c_void_p)]
 
 
+class RolloutScore(C.Structure):
+    """tinympc_rollout_score (include/tinympc_hip.h): the weights of the rollout metrics' cost, nx | nu values, and the settle tolerance."""
+    _fields_ = [("qx", c_double_p), ("ru", c_double_p), ("settle_tol", C.c_double)]
+
+
 # name -> (restype, argtypes); mirrors include/tinympc_hip.h one to one
 SIGNATURES = {
     "tinympc_last_error": (C.c_char_p, []),
@@ -141,6 +146,11 @@ SIGNATURES = {
     "tinympc_set_plant_batch": (C.c_int, [Handle, c_double_p, c_double_p, c_double_p, C.c_int, C.c_int]),
     "tinympc_set_plant_batch_device": (C.c_int, [Handle, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
     "tinympc_clear_plant_batch": (C.c_int, [Handle]),
+    "tinympc_set_rollout_metrics": (C.c_int, [Handle, C.POINTER(RolloutScore)]),
+    "tinympc_reset_rollout_metrics": (C.c_int, [Handle]),
+    "tinympc_clear_rollout_metrics": (C.c_int, [Handle]),
+    "tinympc_get_rollout_metrics": (C.c_int, [Handle, c_double_p]),
+    "tinympc_get_rollout_metrics_device_ptr": (C.c_int, [Handle, C.POINTER(c_double_p)]),
 }
 
 # include/tinympc_hip_bench.h: measurement helpers / diagnostics, not part of the drop-in boundary

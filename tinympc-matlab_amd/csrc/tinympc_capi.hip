@@ -2078,6 +2078,39 @@ void fill_plant_operands(const tinympc_solver *s, PlantStepParams *p) {
     p->x0 = s->dx0; p->sol_u = s->dsolu; p->istats = s->distats;
 }
 
+// What the scored step measures against: the reference and the bounds the solve itself used at knot 0. A half in track mode: the
+// instance's column min(steps[b], T - 1) of its track (the kernel reads the step: the step of THIS tick, the auto-advance comes behind
+// it); else the instance's own reference, column 0; else the shared one. Bounds: the instance's where that mode is on, else the shared
+// ones; NULL while the family is disabled (the slot stays 0).
+void fill_metrics_operands(const tinympc_solver *s, PlantMetricsParams *q) {
+    const InstState &in = s->inst;
+    const size_t nx = s->nx, nu = s->nu, X = s->X(), U = s->U();
+    *q = PlantMetricsParams{};
+    q->rows = s->rm_rows; q->qx = s->rm_w; q->ru = s->rm_w + nx; q->settle_tol = s->rm_tol;
+    q->steps = in.steps;
+    if (in.x && in.x_track && in.Xt && in.steps) { q->xr = in.Xt; q->xr_stride = nx * (size_t)in.Tx; q->xr_T = in.Tx; }
+    else if (in.x && in.Xi) { q->xr = in.Xi; q->xr_stride = X; }
+    else { q->xr = s->dXref; q->xr_stride = 0; }
+    if (in.u && in.u_track && in.Ut && in.steps) { q->ur = in.Ut; q->ur_stride = nu * (size_t)in.Tu; q->ur_T = in.Tu; }
+    else if (in.u && in.Ui) { q->ur = in.Ui; q->ur_stride = U; }
+    else { q->ur = s->dUref; q->ur_stride = 0; }
+    const bool ib = in.bounds && in.xmin && in.xmax && in.umin && in.umax;
+    if (s->st.en_state_bound) { q->xlo = ib ? in.xmin : s->dxmin; q->xhi = ib ? in.xmax : s->dxmax; q->xb_stride = ib ? X : 0; }
+    if (s->st.en_input_bound) { q->ulo = ib ? in.umin : s->dumin; q->uhi = ib ? in.umax : s->dumax; q->ub_stride = ib ? U : 0; }
+}
+
+// One plant step on the handle's stream: the scored variant while the metrics are on, the plain kernel otherwise.
+int queue_plant_step(tinympc_solver *s, const PlantStepParams &p) {
+    if (s->metrics) {
+        PlantMetricsParams q;
+        fill_metrics_operands(s, &q);
+        HIP_TRY(launch_plant_step_scored(p, q, s->W, s->KT, s->stream));
+    } else {
+        HIP_TRY(launch_plant_step(p, s->W, s->KT, s->stream));
+    }
+    return TINYMPC_OK;
+}
+
 // What both forms of the rollout refuse, before anything is queued or changed; on success the device is bound and the plan resolved.
 int rollout_refusals(tinympc_solver *s, const char *verb, int ticks) {
     int rc = check_handle(s);
@@ -2105,7 +2138,7 @@ int queue_rollout(tinympc_solver *s, int ticks, const double *d_w, const tinympc
         if ((rc = launch(s, false))) return rc;
         fill_plant_operands(s, &p);
         p.t = t;
-        HIP_TRY(launch_plant_step(p, s->W, s->KT, s->stream));
+        if ((rc = queue_plant_step(s, p))) return rc;
         if (s->inst.auto_advance && (rc = advance_ref_steps_after_tick(s))) return rc;
     }
     return TINYMPC_OK;
@@ -2212,8 +2245,7 @@ int tinympc_plant_step_batch(tinympc_solver *s, const double *disturbance) {
     fill_plant_operands(s, &p);
     p.t = 0; p.ticks = 1;
     p.w = disturbance ? s->rl_w : nullptr;
-    HIP_TRY(launch_plant_step(p, s->W, s->KT, s->stream));
-    return TINYMPC_OK;
+    return queue_plant_step(s, p);
 }
 
 int tinympc_set_plant_batch(tinympc_solver *s, const double *A, const double *B, const double *f, int first, int count) {
@@ -2227,6 +2259,76 @@ int tinympc_clear_plant_batch(tinympc_solver *s) {
     int rc = check_handle(s);
     if (rc) return rc;
     s->plant = false;  // (the stores stay for the next override)
+    return TINYMPC_OK;
+}
+
+// ---- rollout metrics (the scored variant of k_plant_step)
+namespace {
+
+// What every metrics verb refuses first; `need_on`: the verbs that read or zero the rows want the metrics on.
+int metrics_refusals(const tinympc_solver *s, const char *verb, bool need_on) {
+    int rc = check_handle(s);
+    if (rc) return rc;
+    if (s->session_active || s->host_path()) return fail(TINYMPC_ERR_UNSUPPORTED, "%s: batched handles outside a session only", verb);
+    if (need_on && !s->metrics)
+        return fail(TINYMPC_ERR_INVALID_INPUT, "%s: the rollout metrics are off (tinympc_set_rollout_metrics turns them on)", verb);
+    return TINYMPC_OK;
+}
+
+}  // namespace
+
+int tinympc_set_rollout_metrics(tinympc_solver *s, const tinympc_rollout_score *score) {
+    const char *verb = "set_rollout_metrics";
+    int rc = metrics_refusals(s, verb, false);
+    if (rc) return rc;
+    if (!score || !score->qx || !score->ru) return fail(TINYMPC_ERR_INVALID_INPUT, "%s requires qx and ru", verb);
+    const size_t nx = s->nx, nu = s->nu;
+    for (size_t i = 0; i < nx + nu; ++i) {
+        const double v = i < nx ? score->qx[i] : score->ru[i - nx];
+        if (!std::isfinite(v) || v < 0.0)
+            return fail(TINYMPC_ERR_INVALID_INPUT, "%s: %s[%zu] = %g. Expected a finite weight >= 0.", verb, i < nx ? "qx" : "ru", i < nx ? i : i - nx, v);
+    }
+    if (!std::isfinite(score->settle_tol)) return fail(TINYMPC_ERR_INVALID_INPUT, "%s: settle_tol = %g. Expected a finite number.", verb, score->settle_tol);
+    if ((rc = bind_device(s))) return rc;
+    if (!s->rm_rows && (rc = dalloc(s, &s->rm_rows, (size_t)8 * s->batch))) return rc;
+    if (!s->rm_w && (rc = dalloc(s, &s->rm_w, nx + nu))) return rc;
+    std::vector<double> w(nx + nu);
+    for (size_t i = 0; i < nx + nu; ++i) w[i] = i < nx ? score->qx[i] : score->ru[i - nx];
+    HIP_TRY(hipMemsetAsync(s->rm_rows, 0, sizeof(double) * 8 * s->batch, s->stream));
+    if ((rc = upload(s, s->rm_w, w.data(), nx + nu))) return rc;  // (behind every step queued so far: they read the weights they were queued with)
+    s->rm_tol = score->settle_tol;
+    s->metrics = true;
+    return TINYMPC_OK;
+}
+
+int tinympc_reset_rollout_metrics(tinympc_solver *s) {
+    int rc = metrics_refusals(s, "reset_rollout_metrics", true);
+    if (rc) return rc;
+    if ((rc = bind_device(s))) return rc;
+    HIP_TRY(hipMemsetAsync(s->rm_rows, 0, sizeof(double) * 8 * s->batch, s->stream));
+    return TINYMPC_OK;
+}
+
+int tinympc_clear_rollout_metrics(tinympc_solver *s) {
+    int rc = metrics_refusals(s, "clear_rollout_metrics", false);
+    if (rc) return rc;
+    s->metrics = false;  // (the rows and the weights stay for the next call of tinympc_set_rollout_metrics, which zeroes the rows)
+    return TINYMPC_OK;
+}
+
+int tinympc_get_rollout_metrics(tinympc_solver *s, double *out) {
+    int rc = metrics_refusals(s, "get_rollout_metrics", true);
+    if (rc) return rc;
+    if (!out) return fail(TINYMPC_ERR_INVALID_INPUT, "get_rollout_metrics: out is NULL");
+    if ((rc = bind_device(s))) return rc;
+    return download(s, out, s->rm_rows, sizeof(double) * 8 * s->batch);
+}
+
+int tinympc_get_rollout_metrics_device_ptr(tinympc_solver *s, const double **d_rows) {
+    int rc = metrics_refusals(s, "get_rollout_metrics_device_ptr", true);
+    if (rc) return rc;
+    if (!d_rows) return fail(TINYMPC_ERR_INVALID_INPUT, "get_rollout_metrics_device_ptr: d_rows is NULL");
+    *d_rows = s->rm_rows;
     return TINYMPC_OK;
 }
 

@@ -322,6 +322,12 @@ struct tinympc_solver {
     double *rl_x = nullptr, *rl_u = nullptr, *rl_w = nullptr;
     int *rl_it = nullptr, *rl_st = nullptr;
     size_t rl_x_cap = 0, rl_u_cap = 0, rl_w_cap = 0, rl_it_cap = 0, rl_st_cap = 0;
+    // Rollout metrics (tinympc_set_rollout_metrics): while on, every plant step runs the scored variant of k_plant_step, which moves
+    // every instance's row of 8 doubles on (PlantMetricsParams, tinympc_rollout.h). rm_rows [batch][8] and rm_w (the weights qx | ru)
+    // are allocated by the first call and stay until the handle goes; tinympc_clear_rollout_metrics only turns the variant off.
+    bool metrics = false;
+    double *rm_rows = nullptr, *rm_w = nullptr;
+    double rm_tol = 0.0;
     size_t lds_bytes_a = 0;       // layout-A LDS plan (layout B, where it runs, replaces lds_bytes; the families and adaptive rho always use layout A)
     bool tables_in_lds_a = false;
 

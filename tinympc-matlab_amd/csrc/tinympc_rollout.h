@@ -25,8 +25,36 @@ struct PlantStepParams {
     int *iter_log, *status_log;
 };
 
+// The rollout metrics (tinympc_set_rollout_metrics): one row of 8 doubles per instance, accumulated by the scored variant of the step
+// from what the step holds in registers anyway. With x, u as above, e = x - xr, d = u - ur (xr, ur: the reference the solve tracked at
+// knot 0), lo / hi its bounds at knot 0 and t the row's own step count:
+//   [0] steps                      += 1
+//   [1] cost                       one chain from the stored value: + qx_i (e_i e_i), state rows ascending, then + ru_j (d_j d_j), input
+//                                  rows ascending; every product rounded once, nothing contracted into the add
+//   [2] worst state-bound breach   max(., max_i max(0, lo_i - x_i, x_i - hi_i))    (xlo NULL: the family is off, 0)
+//   [3] worst input-bound breach   the same for u                                    (ulo NULL: 0)
+//   [4] iterations                 += istats[2b]
+//   [5] most iterations of a step  max(., istats[2b])
+//   [6] unconverged steps          += (istats[2b+1] != 1: anything but TINYMPC_STATUS_SOLVED -- a tick that ran out of iterations reports 11)
+//   [7] settle step                t + 1 of this step where max_i |e_i| > settle_tol (and settle_tol > 0), else kept
+// A reference / bound operand is a pointer, an instance stride in doubles (0: shared) and a column: min(steps[b], T - 1) where T > 0 (a
+// half in track mode, read before the auto-advance), else 0. Columns are nx (nu) doubles apart.
+struct PlantMetricsParams {
+    double *rows;                      // [batch][8]
+    const double *qx, *ru;             // the weights, nx | nu, shared by the batch
+    double settle_tol;
+    const double *xr, *ur;
+    size_t xr_stride, ur_stride;
+    int xr_T, ur_T;
+    const int *steps;                  // the tracks' steps (read where xr_T or ur_T > 0)
+    const double *xlo, *xhi, *ulo, *uhi;
+    size_t xb_stride, ub_stride;
+};
+
 // W, KT: the handle's lanes per instance and padded operand length (choose_geometry); W > 64 (layout M's systems): the workgroup form.
 hipError_t launch_plant_step(const PlantStepParams &p, int W, int KT, hipStream_t stream);
+// ... and its scored variant: the same step (the same bits in x0 and the logs), and every instance's metrics row moves on
+hipError_t launch_plant_step_scored(const PlantStepParams &p, const PlantMetricsParams &q, int W, int KT, hipStream_t stream);
 // *flag = 1 where v holds a value that is not finite (device input of tinympc_set_plant_batch_device)
 hipError_t launch_check_finite(const double *v, size_t n, int *flag, hipStream_t stream);
 

@@ -768,6 +768,56 @@ class TinyMPC:
         self._check_setup()
         _lib.check(self._L.tinympc_clear_plant_batch(self._h))
 
+    # ------------------------------------------------------------------ rollout metrics
+    _METRICS = ("steps", "cost", "x_violation", "u_violation", "iterations", "max_iterations", "unconverged", "settle")
+    _METRICS_FLOAT = ("cost", "x_violation", "u_violation")
+
+    def set_rollout_metrics(self, qx=None, ru=None, settle_tol: float = 0.0):
+        """Turn the rollout metrics on (or replace their weights) and zero them: from now on every plant step of rollout() and
+        plant_step() scores the instance on the device (include/tinympc_hip.h, tinympc_set_rollout_metrics). qx: (nx,) weights of the
+        state error, ru: (nu,) weights of the input error; None: the diagonals of the Q / R given to setup. settle_tol: the state
+        counts as away from its reference while max_i |x_i - xr_i| > settle_tol (<= 0: the settle step is not kept)."""
+        self._check_setup()
+        w = []
+        for name, v, M, n in (("qx", qx, self.Q, self.nx), ("ru", ru, self.R, self.nu)):
+            a = np.asarray(np.diag(M) if M.ndim == 2 else M, dtype=np.float64) if v is None else np.asarray(v, dtype=np.float64)
+            if a.shape != (n,):
+                raise TinyMPCError(_lib.ERR_INVALID_INPUT, "rollout metrics: %s must have shape (%d,), got %s" % (name, n, a.shape))
+            w.append(np.ascontiguousarray(a))
+        if np.ndim(settle_tol) != 0:
+            raise TinyMPCError(_lib.ERR_INVALID_INPUT, "rollout metrics: settle_tol must be a scalar")
+        score = _lib.RolloutScore(_p(w[0]), _p(w[1]), float(settle_tol))
+        _lib.check(self._L.tinympc_set_rollout_metrics(self._h, C.byref(score)))
+
+    def reset_rollout_metrics(self):
+        """Zero every instance's metrics, queued on the solver's stream (the weights stay)."""
+        self._check_setup()
+        _lib.check(self._L.tinympc_reset_rollout_metrics(self._h))
+
+    def clear_rollout_metrics(self):
+        """Turn the rollout metrics off: plant steps run the plain kernel again."""
+        self._check_setup()
+        _lib.check(self._L.tinympc_clear_rollout_metrics(self._h))
+
+    def rollout_metrics(self, device: bool = False):
+        """The metrics accumulated since the last reset, a dict of (batch,) arrays: "steps", "cost", "x_violation", "u_violation",
+        "iterations", "max_iterations", "unconverged", "settle" (cost and the violations float64, the counts int64); waits for the
+        solver's stream. device=True: the rows themselves as a (batch, 8) float64 CUDA tensor view (columns in the order above) of
+        memory the solver owns -- no copy and no wait: order reads behind the solver's stream (synchronize())."""
+        self._check_setup()
+        if device:
+            import torch
+            ptr = c_double_p()
+            _lib.check(self._L.tinympc_get_rollout_metrics_device_ptr(self._h, C.byref(ptr)))
+
+            class _Rows:
+                __cuda_array_interface__ = dict(shape=(self.batch, 8), typestr="<f8", data=(C.cast(ptr, C.c_void_p).value, False), version=2)
+
+            return torch.as_tensor(_Rows(), device="cuda")  # (torch takes the device from the pointer)
+        rows = np.zeros((self.batch, 8))
+        _lib.check(self._L.tinympc_get_rollout_metrics(self._h, _p(rows)))
+        return {k: (rows[:, i].copy() if k in self._METRICS_FLOAT else rows[:, i].astype(np.int64)) for i, k in enumerate(self._METRICS)}
+
     def _set_batch(self, what, arrays, rows, full, f_host, f_device, first, *extra):
         """The per-instance verbs: numpy arrays of shape (rows, count) / (rows, cols, count), or contiguous float64 CUDA tensors with the
         same memory layout, (count, rows) / (count, cols, rows) -- one column held over the horizon, or cols = full. All arrays in the

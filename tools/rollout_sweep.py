@@ -16,7 +16,16 @@ full length, so that its log buffers exist), then starts again from the seeded x
 rounding (numpy's dot product against the kernel's chain), so their trajectories agree to rounding, not bit for bit: the mean
 iterations per tick are printed beside the times. The bar: leg c below leg a in every round at 4,096 and 8,192 instances (the exit
 status says so); at 256, where the zero-copy tick is already lean, the line says which way it went.
-    python tools/rollout_sweep.py --parent-lib /path/to/parent/libtinympc_hip.so [--batches 256,4096,8192] [--ticks 200] [--rounds 4]"""
+    python tools/rollout_sweep.py --parent-lib /path/to/parent/libtinympc_hip.so [--batches 256,4096,8192] [--ticks 200] [--rounds 4]
+
+--metrics: what a SCORED rollout costs (the rollout metrics, tinympc_set_rollout_metrics). The parent is then the commit that has the
+rollout but not the metrics; same workload, same protocol. The legs:
+  b   the parent's library: solve + plant_step per tick
+  c   the parent's library: one rollout call with all four logs, then the eight scores per instance reduced from the logs in numpy (the
+      only way to score a rollout there); both parts are timed, the line shows their sum and the numpy part
+  c0  the parent's library: one rollout call without logs -- the queue alone, nothing scored
+  d   this tree's library: set_rollout_metrics, one rollout call without logs, rollout_metrics() (64 bytes per instance)
+The claim: d below c and below b in every round at all three sizes (the exit status says so), and how far d sits above c0."""
 import argparse
 import json
 import os
@@ -81,6 +90,122 @@ def run_leg(pkg, leg, batch, ticks):
     return 1e6 * dt / ticks, iters, info, (gpu_us[-1] if gpu_us else None)
 
 
+def numpy_scores(prob, log):
+    """The eight scores per instance from a rollout's logs (references zero, the quadrotor's box): vectorised, as a study would write it."""
+    qx, ru = np.diag(prob.Q), np.diag(prob.R)
+    x, u = log["x"][:, :-1, :], log["u"]
+    cost = np.einsum("i,itb->b", qx, x * x) + np.einsum("i,itb->b", ru, u * u)
+    xv = np.maximum(0.0, np.maximum(prob.x_min[:, None, None] - x, x - prob.x_max[:, None, None])).max(axis=(0, 1))
+    uv = np.maximum(0.0, np.maximum(prob.u_min[:, None, None] - u, u - prob.u_max[:, None, None])).max(axis=(0, 1))
+    away = np.abs(x).max(axis=0) > 0.05
+    settle = np.where(away.any(axis=0), away.shape[0] - np.argmax(away[::-1], axis=0), 0)
+    return dict(cost=cost, x_violation=xv, u_violation=uv, iterations=log["iter"].sum(axis=0), max_iterations=log["iter"].max(axis=0),
+                unconverged=(log["status"] != 1).sum(axis=0), settle=settle)
+
+
+def run_metrics_leg(pkg, leg, batch, ticks):
+    """-> (wall us per tick, the numpy part of it (leg c), the mean cost, kernel line)"""
+    P = pkg.problems
+    prob = P.quadrotor(50)
+    s = pkg.TinyMPC()
+    s.setup(prob.A, prob.B, prob.Q, prob.R, prob.N, batch=batch, rho=prob.rho, max_iter=100, abs_pri_tol=1e-3, abs_dua_tol=1e-3)
+    s.set_bound_constraints(prob.x_min, prob.x_max, prob.u_min, prob.u_max)
+    x0 = np.asfortranarray(P.quadrotor_batch_x0(batch))
+    if leg == "d":
+        s.set_rollout_metrics(settle_tol=0.05)
+
+    def loop(n):
+        """-> (seconds, seconds of numpy scoring, mean cost or nan)"""
+        t0 = time.perf_counter()
+        if leg == "b":
+            for _ in range(n):
+                s.solve()
+                s.plant_step()
+            return time.perf_counter() - t0, 0.0, float("nan")
+        if leg == "c0":
+            s.rollout(n, log=())
+            return time.perf_counter() - t0, 0.0, float("nan")
+        if leg == "c":
+            log = s.rollout(n)
+            t1 = time.perf_counter()
+            m = numpy_scores(prob, log)
+            t2 = time.perf_counter()
+            return t2 - t0, t2 - t1, float(m["cost"].mean())
+        s.rollout(n, log=())
+        m = s.rollout_metrics()
+        return time.perf_counter() - t0, 0.0, float(m["cost"].mean())
+
+    def restart():
+        s.reset_workspace()
+        s.set_x0_batch(x0)
+        if leg == "d":
+            s.reset_rollout_metrics()
+
+    s.set_x0_batch(x0)
+    if leg != "b":
+        loop(ticks)
+        restart()
+    loop(WARMUP)
+    restart()
+    dt, dt_np, cost = loop(ticks)
+    info = "%s %s" % (s.launch_info()["layout"], s.jit_info())
+    s.reset()
+    return 1e6 * dt / ticks, 1e6 * dt_np / ticks, cost, info
+
+
+def child_metrics(pkg, a):
+    has = hasattr(pkg.load_library(), "tinympc_set_rollout_metrics")
+    out = dict(library="this" if has else "parent", tick_us={}, numpy_us={}, cost={}, kernel={})
+    for leg in (("d",) if has else ("b", "c", "c0")):
+        us, us_np, cost, info = run_metrics_leg(pkg, leg, a.batch, a.ticks)
+        out["tick_us"][leg], out["numpy_us"][leg], out["cost"][leg], out["kernel"][leg] = us, us_np, cost, info
+    print("ROLLOUT-CHILD " + json.dumps(out), flush=True)
+
+
+def sweep_metrics(a):
+    if not a.parent_lib or not os.path.exists(a.parent_lib):
+        raise SystemExit("needs --parent-lib: libtinympc_hip.so built from the parent commit")
+    ok = True
+    for batch in [int(b) for b in a.batches.split(",")]:
+        rows = {"this": [], "parent": []}
+        for rnd in range(a.rounds):
+            for lib in ("this", "parent") if rnd % 2 == 0 else ("parent", "this"):
+                env = dict(os.environ)
+                env.pop("TINYMPC_HIP_LIBRARY", None)
+                if lib == "parent":
+                    env["TINYMPC_HIP_LIBRARY"] = os.path.abspath(a.parent_lib)
+                cmd = [sys.executable, os.path.abspath(__file__), "--child", "--metrics", "--batch", str(batch), "--ticks", str(a.ticks)]
+                r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)
+                line = [l for l in r.stdout.splitlines() if l.startswith("ROLLOUT-CHILD ")]
+                if r.returncode != 0 or not line:
+                    raise SystemExit("batch %d round %d (%s) failed with %d:\n%s\n%s" % (batch, rnd, lib, r.returncode, r.stdout[-2000:], r.stderr[-2000:]))
+                rec = json.loads(line[0][len("ROLLOUT-CHILD "):])
+                assert rec["library"] == lib, rec
+                rows[lib].append(rec)
+                print("# batch %d round %d %-6s %s" % (batch, rnd, lib, json.dumps(rec["tick_us"])), flush=True)
+        print("scored closed-loop rollout, %d quadrotors N=50, tolerances 1e-3, max_iter 100, %d warm-started ticks, wall us per tick (%d rounds, a "
+              "fresh process each, the two libraries alternating)" % (batch, a.ticks, a.rounds))
+        print("%-66s | %-36s | %-9s | %-19s" % ("leg", "rounds", "median", "spread"))
+        med = {}
+        for leg, lib, name in (("b", "parent", "b  solve + plant_step per tick (parent)"), ("c", "parent", "c  one rollout call, all logs, scores in numpy (parent)"),
+                               ("c0", "parent", "c0 one rollout call, no logs, nothing scored (parent)"),
+                               ("d", "this", "d  one scored rollout call, no logs, rollout_metrics()")):
+            v = [r["tick_us"][leg] for r in rows[lib]]
+            med[leg] = float(np.median(v))
+            print("%-66s | %-36s | %9.1f | %8.1f - %8.1f" % (name, " ".join("%.1f" % x for x in v), med[leg], min(v), max(v)))
+        print("leg c's numpy part per tick (median of the rounds): %.1f us; mean cost c %.9g, d %.9g" %
+              (float(np.median([r["numpy_us"]["c"] for r in rows["parent"]])), rows["parent"][0]["cost"]["c"], rows["this"][0]["cost"]["d"]))
+        print("kernel: %s" % rows["this"][0]["kernel"]["d"])
+        below_c = all(rd["tick_us"]["d"] < rp["tick_us"]["c"] for rd, rp in zip(rows["this"], rows["parent"]))
+        below_b = all(rd["tick_us"]["d"] < rp["tick_us"]["b"] for rd, rp in zip(rows["this"], rows["parent"]))
+        print("batch %d: d against c %.2fx, d against b %.2fx, d above c0 by %.1f us per tick (%.1f %%); d below c in every round: %s; d below b in every "
+              "round: %s\n" % (batch, med["c"] / med["d"], med["b"] / med["d"], med["d"] - med["c0"], 100.0 * (med["d"] / med["c0"] - 1.0),
+                                "yes" if below_c else "NO", "yes" if below_b else "NO"))
+        ok = ok and below_c and below_b
+    if not ok:
+        raise SystemExit(1)
+
+
 def child(pkg, a):
     has = hasattr(pkg.load_library(), "tinympc_rollout_batch")
     out = dict(library="this" if has else "parent", tick_us={}, iters={}, kernel={}, gpu_us={})
@@ -143,11 +268,12 @@ def main():
     ap.add_argument("--rounds", type=int, default=4)
     ap.add_argument("--parent-lib", default="")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--metrics", action="store_true", help="the scored rollout against the parent's legs (see above)")
     a = ap.parse_args()
     if not a.child:
-        return sweep(a)
+        return sweep_metrics(a) if a.metrics else sweep(a)
     import __graft_entry__ as ge
-    child(ge.load_package(), a)
+    (child_metrics if a.metrics else child)(ge.load_package(), a)
 
 
 if __name__ == "__main__":
