@@ -678,6 +678,45 @@ int tinympc_clear_rollout_metrics(tinympc_solver *s);                           
 int tinympc_get_rollout_metrics(tinympc_solver *s, double *out);                        /* 8 x batch, synchronises */
 int tinympc_get_rollout_metrics_device_ptr(tinympc_solver *s, const double **d_rows);    /* ordered behind the handle's stream */
 
+/* Rollout noise: seeded process and measurement noise for Monte-Carlo studies, drawn on the device by the plant step itself -- no
+ * nx x ticks x batch disturbance to draw on the host and upload. While the noise is on, every plant step the handle queues
+ * (tinympc_rollout_batch / _device of any length, in any number of calls, and tinympc_plant_step_batch) runs a noisy variant of
+ * k_plant_step, scored as well while the metrics are on, with the handle's noise tick, which then moves on by one.
+ *   draw     n(g, tick, r, stream): a standard normal that is a pure function of the seed, the instance's global index
+ *            g = first_instance + b, the noise tick, the state row r and the stream (0: process, 1: measurement). Philox4x32-10
+ *            (multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85) with key (seed & 0xffffffff, seed >> 32) and
+ *            counter (g, tick, r, stream) gives the words o0..o3; u1 = ((o0 >> 5) 2^26 + (o1 >> 6) + 1) 2^-53 in (0, 1],
+ *            u2 = ((o2 >> 5) 2^26 + (o3 >> 6)) 2^-53 in [0, 1); n = sqrt(-2 log(u1)) * cos(6.283185307179586 * u2), every operation
+ *            rounded once, nothing contracted; |n| <= 8.58. It depends on nothing else: not on the layout, not on how a rollout is cut
+ *            into calls (T ticks equal T/2 + T/2), not on how a fleet is cut into handles (a shard with its first_instance draws what the
+ *            same instances draw unsharded).
+ *   step     with x the TRUE state (x_log and the metrics see this x), sw / sv the scales of the row:
+ *              x+ = (A_p x + B_p u + f_p + w[b][:, t]) + (sw_r n(g, tick, r, 0))      the plain step's chain and disturbance, then the
+ *                                                                                      process term: product rounded, then the add
+ *              x0[b][r] = x+ + (sv_r n(g, tick, r, 1))                                 the measurement the NEXT solve reads
+ *            Without measurement noise x0 is the true state as ever. With it the handle keeps the true state beside x0, in memory it
+ *            owns; the first tick's measurement is whatever x0 holds (a caller who wants it noisy adds its own). A verb that writes x0
+ *            from outside (tinympc_set_x0_batch / _device, tinympc_set_x0, tinympc_mpc_step_batch) restarts the true state of the
+ *            instances it names from what it wrote.
+ * tinympc_set_rollout_noise takes standard deviations per state row -- nx values shared by the batch, or nx x batch (instance b at
+ * nx b) with per_instance != 0; either array may be NULL: that family is off and nothing is drawn for it --, copies them to device
+ * memory the handle owns, and sets the noise tick to 0. A level sweep is one handle and one launch. tinympc_clear_rollout_noise turns
+ * the noise off: steps run the plain or scored kernels again, and where measurement noise was on the true state goes back into x0
+ * (queued), so the loop continues from it. tinympc_get_rollout_noise regenerates, by the step's own device function, what the steps of
+ * ticks first_tick .. first_tick + ticks - 1 add: w_out = sw_r n(., 0), v_out = sv_r n(., 1), each nx x ticks x batch in the
+ * disturbance's layout; either may be NULL, a family that is off yields zeros. A noise-free handle given w_out as its disturbance
+ * reproduces a process-noise rollout bit for bit. tinympc_get_plant_state_batch copies out the true state (nx x batch): the state
+ * beside x0 while measurement noise is on, else x0; it synchronises.
+ * Refusals (nothing is queued or changed): TINYMPC_ERR_UNSUPPORTED for single-instance handles that answer through pinned host memory
+ * and inside a session; TINYMPC_ERR_INVALID_INPUT for a NULL struct, both arrays NULL, a scale that is negative or not finite,
+ * first_instance + batch > 2^32, ticks < 1, a step (or a replay) whose tick would reach 2^32, and for get_rollout_noise / clear while
+ * the noise is off. */
+typedef struct { const double *process, *measurement; int per_instance; unsigned long long seed, first_instance; } tinympc_rollout_noise;
+int tinympc_set_rollout_noise(tinympc_solver *s, const tinympc_rollout_noise *noise);
+int tinympc_clear_rollout_noise(tinympc_solver *s);
+int tinympc_get_rollout_noise(tinympc_solver *s, unsigned long long first_tick, int ticks, double *w_out, double *v_out);
+int tinympc_get_plant_state_batch(tinympc_solver *s, double *x_out);
+
 /* Launch geometry of the solve kernel, for reports: lanes per instance, instances per wavefront,
  * workgroups in the grid, dynamic LDS bytes per workgroup, and whether the per-knot bound/reference
  * tables are LDS-resident. Any pointer may be NULL. */

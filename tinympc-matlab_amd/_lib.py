@@ -51,6 +51,13 @@ class RolloutScore(C.Structure):
     _fields_ = [("qx", c_double_p), ("ru", c_double_p), ("settle_tol", C.c_double)]
 
 
+class RolloutNoise(C.Structure):
+    """tinympc_rollout_noise (include/tinympc_hip.h): the standard deviations of the process and the measurement noise per state row (nx
+    values, or nx x batch with per_instance; either may be NULL), the seed and the global index of the handle's instance 0."""
+    _fields_ = [("process", c_double_p), ("measurement", c_double_p), ("per_instance", C.c_int), ("seed", C.c_ulonglong),
+                ("first_instance", C.c_ulonglong)]
+
+
 # name -> (restype, argtypes); mirrors include/tinympc_hip.h one to one
 SIGNATURES = {
     "tinympc_last_error": (C.c_char_p, []),
@@ -151,6 +158,10 @@ SIGNATURES = {
     "tinympc_clear_rollout_metrics": (C.c_int, [Handle]),
     "tinympc_get_rollout_metrics": (C.c_int, [Handle, c_double_p]),
     "tinympc_get_rollout_metrics_device_ptr": (C.c_int, [Handle, C.POINTER(c_double_p)]),
+    "tinympc_set_rollout_noise": (C.c_int, [Handle, C.POINTER(RolloutNoise)]),
+    "tinympc_clear_rollout_noise": (C.c_int, [Handle]),
+    "tinympc_get_rollout_noise": (C.c_int, [Handle, C.c_ulonglong, C.c_int, c_double_p, c_double_p]),
+    "tinympc_get_plant_state_batch": (C.c_int, [Handle, c_double_p]),
 }
 
 # include/tinympc_hip_bench.h: measurement helpers / diagnostics, not part of the drop-in boundary

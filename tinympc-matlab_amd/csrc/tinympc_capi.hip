@@ -259,6 +259,16 @@ int tinympc_setup(tinympc_solver **out, const double *A, const double *B, const 
     return tinympc_setup_batch(out, A, B, fdyn, Q, R, rho, nx, nu, N, 1, -1, verbose);
 }
 
+// While measurement noise is on (tinympc_set_rollout_noise) the handle keeps the TRUE state in rn_px and the measurement in x0. A verb that
+// writes x0 from outside restarts the true state of the instances it names from what it wrote: the same range, copied on the stream behind
+// the write (a range and not a flag for the whole batch: the other instances' true state is not their measurement).
+static int mirror_x0_into_px(tinympc_solver *s, int first, int count) {
+    if (!s->noise || !s->rn_v_on || count < 1) return TINYMPC_OK;
+    const size_t at = (size_t)first * s->nx;
+    HIP_TRY(hipMemcpyAsync(s->rn_px + at, s->dx0 + at, sizeof(double) * count * s->nx, hipMemcpyDeviceToDevice, s->stream));
+    return TINYMPC_OK;
+}
+
 int tinympc_set_x0(tinympc_solver *s, const double *x0, int len, int verbose) {
     int rc = check_handle(s);
     if (rc) return rc;
@@ -276,6 +286,7 @@ int tinympc_set_x0(tinympc_solver *s, const double *x0, int len, int verbose) {
     }
     if ((rc = bind_device(s))) return rc;
     rc = upload(s, s->dx0, x0, s->nx);
+    if (!rc) rc = mirror_x0_into_px(s, 0, 1);
     if (!rc && verbose) printf("Initial state set\n");
     return rc;
 }
@@ -564,6 +575,7 @@ int tinympc_mpc_step_batch(tinympc_solver *s, const double *x0s, double *u0_out)
         HIP_TRY(hipStreamSynchronize(s->stream));
     }
     std::memcpy(u0_out, s->h_u0, sizeof(double) * nu0);
+    if ((rc = mirror_x0_into_px(s, 0, s->batch))) return rc;  // (this call brought its own x0: the true state restarts from it)
     // reference tracks: every step moves AFTER the tick's solve -- one small kernel behind it on the stream, nothing read back; the next
     // launch rebuilds the rows
     if (s->inst.auto_advance && (rc = advance_ref_steps_after_tick(s))) return rc;
@@ -1017,7 +1029,8 @@ int tinympc_set_x0_batch(tinympc_solver *s, const double *x0s, int first, int co
         std::memcpy(s->h_x0, x0s, sizeof(double) * s->nx);
     }
     s->x0_on_host = false;
-    return upload(s, s->dx0 + (size_t)first * s->nx, x0s, (size_t)count * s->nx);
+    if ((rc = upload(s, s->dx0 + (size_t)first * s->nx, x0s, (size_t)count * s->nx))) return rc;
+    return mirror_x0_into_px(s, first, count);
 }
 
 int tinympc_set_x0_batch_device(tinympc_solver *s, const double *d_x0s, int first, int count) {
@@ -1029,6 +1042,7 @@ int tinympc_set_x0_batch_device(tinympc_solver *s, const double *d_x0s, int firs
     if ((rc = bind_device(s))) return rc;
     s->x0_on_host = false;
     HIP_TRY(hipMemcpyAsync(s->dx0 + (size_t)first * s->nx, d_x0s, sizeof(double) * count * s->nx, hipMemcpyDeviceToDevice, s->stream));
+    if ((rc = mirror_x0_into_px(s, first, count))) return rc;
     // (a single-instance handle: the pinned copy that resident solves read follows on the same stream, behind any launch still reading it)
     if (s->host_path() && count == 1) HIP_TRY(hipMemcpyAsync(s->h_x0, s->dx0, sizeof(double) * s->nx, hipMemcpyDeviceToHost, s->stream));
     // The copy runs on the handle's own (non-blocking) stream: wait for it here, so that the caller may free or reuse
@@ -2099,9 +2113,35 @@ void fill_metrics_operands(const tinympc_solver *s, PlantMetricsParams *q) {
     if (s->st.en_input_bound) { q->ulo = ib ? in.umin : s->dumin; q->uhi = ib ? in.umax : s->dumax; q->ub_stride = ib ? U : 0; }
 }
 
-// One plant step on the handle's stream: the scored variant while the metrics are on, the plain kernel otherwise.
+// The noise operands of a step (or of a replay) at `tick`: the key, the scales of the families that are on, the true state beside x0.
+void fill_noise_operands(const tinympc_solver *s, unsigned long long tick, PlantNoiseParams *n) {
+    *n = PlantNoiseParams{};
+    n->key0 = (unsigned)(s->rn_seed & 0xffffffffull); n->key1 = (unsigned)(s->rn_seed >> 32);
+    n->tick = (unsigned)tick;
+    n->first_instance = s->rn_first;
+    if (s->rn_w_on) { n->sw = s->rn_sw; n->sw_stride = s->rn_stride; }
+    if (s->rn_v_on) { n->sv = s->rn_sv; n->sv_stride = s->rn_stride; n->px = s->rn_px; }
+}
+
+// What a verb that queues `steps` plant steps refuses while the noise is on: a tick is 32 bits of the draw's counter.
+int noise_tick_refusal(const tinympc_solver *s, const char *verb, unsigned long long steps) {
+    if (s->noise && s->rn_tick + steps > (1ull << 32))
+        return fail(TINYMPC_ERR_INVALID_INPUT, "%s: the rollout noise is at tick %llu, and %llu more would reach 2^32 (tinympc_set_rollout_noise starts again at 0)",
+                    verb, s->rn_tick, steps);
+    return TINYMPC_OK;
+}
+
+// One plant step on the handle's stream: the scored variant while the metrics are on, the plain kernel otherwise; the noisy variant of
+// either while the rollout noise is on, at the handle's noise tick, which moves on by one.
 int queue_plant_step(tinympc_solver *s, const PlantStepParams &p) {
-    if (s->metrics) {
+    if (s->noise) {
+        PlantMetricsParams q;
+        PlantNoiseParams n;
+        if (s->metrics) fill_metrics_operands(s, &q);
+        fill_noise_operands(s, s->rn_tick, &n);
+        HIP_TRY(launch_plant_step_noisy(p, s->metrics ? &q : nullptr, n, s->W, s->KT, s->stream));
+        ++s->rn_tick;
+    } else if (s->metrics) {
         PlantMetricsParams q;
         fill_metrics_operands(s, &q);
         HIP_TRY(launch_plant_step_scored(p, q, s->W, s->KT, s->stream));
@@ -2119,6 +2159,7 @@ int rollout_refusals(tinympc_solver *s, const char *verb, int ticks) {
     if (s->session_active || s->host_path()) return fail(TINYMPC_ERR_UNSUPPORTED, "%s: batched handles outside a session only", verb);
     if (s->st.max_iter < 1)
         return fail(TINYMPC_ERR_INVALID_INPUT, "%s: max_iter must be >= 1 (a tick of %d iterations writes no control to roll out)", verb, s->st.max_iter);
+    if ((rc = noise_tick_refusal(s, verb, (unsigned long long)ticks))) return rc;
     if ((rc = bind_device(s))) return rc;
     if ((rc = resolve_plan(s))) return rc;  // (a run-time specialisation happens here, outside the queue)
     return check_launch(s, current_plan(s));  // (the launch's own refusal, with its message)
@@ -2234,6 +2275,7 @@ int tinympc_plant_step_batch(tinympc_solver *s, const double *disturbance) {
     int rc = check_handle(s);
     if (rc) return rc;
     if (s->session_active || s->host_path()) return fail(TINYMPC_ERR_UNSUPPORTED, "plant_step_batch: batched handles outside a session only");
+    if ((rc = noise_tick_refusal(s, "plant_step_batch", 1))) return rc;
     if ((rc = bind_device(s))) return rc;
     if ((rc = materialize_zero_solution(s))) return rc;  // (no solve since a reset: the first controls are zeros)
     const size_t n = (size_t)s->nx * s->batch;
@@ -2330,6 +2372,98 @@ int tinympc_get_rollout_metrics_device_ptr(tinympc_solver *s, const double **d_r
     if (!d_rows) return fail(TINYMPC_ERR_INVALID_INPUT, "get_rollout_metrics_device_ptr: d_rows is NULL");
     *d_rows = s->rm_rows;
     return TINYMPC_OK;
+}
+
+// ---- rollout noise (the noisy variants of k_plant_step; the draw: tinympc_rollout_noise.h)
+namespace {
+
+int noise_refusals(const tinympc_solver *s, const char *verb, bool need_on) {
+    int rc = check_handle(s);
+    if (rc) return rc;
+    if (s->session_active || s->host_path()) return fail(TINYMPC_ERR_UNSUPPORTED, "%s: batched handles outside a session only", verb);
+    if (need_on && !s->noise)
+        return fail(TINYMPC_ERR_INVALID_INPUT, "%s: the rollout noise is off (tinympc_set_rollout_noise turns it on)", verb);
+    return TINYMPC_OK;
+}
+
+// x0 <- the true state, queued: what ends measurement noise, so that the loop goes on from the state the plant carries
+int px_back_into_x0(tinympc_solver *s) {
+    HIP_TRY(hipMemcpyAsync(s->dx0, s->rn_px, sizeof(double) * s->nx * s->batch, hipMemcpyDeviceToDevice, s->stream));
+    return TINYMPC_OK;
+}
+
+}  // namespace
+
+int tinympc_set_rollout_noise(tinympc_solver *s, const tinympc_rollout_noise *noise) {
+    const char *verb = "set_rollout_noise";
+    int rc = noise_refusals(s, verb, false);
+    if (rc) return rc;
+    if (!noise || (!noise->process && !noise->measurement)) return fail(TINYMPC_ERR_INVALID_INPUT, "%s requires process or measurement scales", verb);
+    const size_t nx = s->nx, batch = s->batch, n = noise->per_instance ? nx * batch : nx;
+    for (int a = 0; a < 2; ++a) {
+        const double *v = a ? noise->measurement : noise->process;
+        for (size_t i = 0; v && i < n; ++i)
+            if (!std::isfinite(v[i]) || v[i] < 0.0)
+                return fail(TINYMPC_ERR_INVALID_INPUT, "%s: %s[%zu] = %g. Expected a finite standard deviation >= 0.", verb, a ? "measurement" : "process", i, v[i]);
+    }
+    if (noise->first_instance > (1ull << 32) || noise->first_instance + batch > (1ull << 32))
+        return fail(TINYMPC_ERR_INVALID_INPUT, "%s: first_instance %llu + batch %zu is beyond 2^32 (a global index is 32 bits of the draw's counter)",
+                    verb, noise->first_instance, batch);
+    if ((rc = bind_device(s))) return rc;
+    if (noise->process && !s->rn_sw && (rc = dalloc(s, &s->rn_sw, nx * batch))) return rc;
+    if (noise->measurement && !s->rn_sv && (rc = dalloc(s, &s->rn_sv, nx * batch))) return rc;
+    if (noise->measurement && !s->rn_px && (rc = dalloc(s, &s->rn_px, nx * batch))) return rc;
+    // (behind every step queued so far: they drew with the scales they were queued with)
+    if (noise->process && (rc = upload(s, s->rn_sw, noise->process, n))) return rc;
+    if (noise->measurement && (rc = upload(s, s->rn_sv, noise->measurement, n))) return rc;
+    const bool had_px = s->noise && s->rn_v_on;
+    if (had_px && !noise->measurement && (rc = px_back_into_x0(s))) return rc;
+    s->noise = true;
+    s->rn_w_on = noise->process != nullptr;
+    s->rn_v_on = noise->measurement != nullptr;
+    s->rn_stride = noise->per_instance ? nx : 0;
+    s->rn_seed = noise->seed; s->rn_first = noise->first_instance; s->rn_tick = 0;
+    if (!had_px) return mirror_x0_into_px(s, 0, s->batch);  // measurement noise just turned on: the true state is what x0 holds
+    return TINYMPC_OK;
+}
+
+int tinympc_clear_rollout_noise(tinympc_solver *s) {
+    int rc = noise_refusals(s, "clear_rollout_noise", true);
+    if (rc) return rc;
+    if (s->rn_v_on) {
+        if ((rc = bind_device(s))) return rc;
+        if ((rc = px_back_into_x0(s))) return rc;
+    }
+    s->noise = s->rn_w_on = s->rn_v_on = false;  // (the scales and px stay allocated for the next call of tinympc_set_rollout_noise)
+    return TINYMPC_OK;
+}
+
+int tinympc_get_rollout_noise(tinympc_solver *s, unsigned long long first_tick, int ticks, double *w_out, double *v_out) {
+    const char *verb = "get_rollout_noise";
+    int rc = noise_refusals(s, verb, true);
+    if (rc) return rc;
+    if (ticks < 1) return fail(TINYMPC_ERR_INVALID_INPUT, "%s: ticks must be >= 1 (got %d)", verb, ticks);
+    if (first_tick > (1ull << 32) || first_tick + (unsigned long long)ticks > (1ull << 32))
+        return fail(TINYMPC_ERR_INVALID_INPUT, "%s: ticks [%llu, %llu + %d) reach 2^32", verb, first_tick, first_tick, ticks);
+    if (!w_out && !v_out) return TINYMPC_OK;
+    if ((rc = bind_device(s))) return rc;
+    const size_t n = (size_t)s->nx * (size_t)ticks * s->batch;
+    if ((rc = grow_rollout_buffer(s, &s->rn_out, &s->rn_out_cap, 2 * n))) return rc;
+    PlantNoiseParams q;
+    fill_noise_operands(s, first_tick, &q);
+    HIP_TRY(launch_rollout_noise(q, s->nx, s->batch, ticks, w_out ? s->rn_out : nullptr, v_out ? s->rn_out + n : nullptr, s->stream));
+    if (w_out) HIP_TRY(hipMemcpyAsync(w_out, s->rn_out, sizeof(double) * n, hipMemcpyDeviceToHost, s->stream));
+    if (v_out) HIP_TRY(hipMemcpyAsync(v_out, s->rn_out + n, sizeof(double) * n, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return TINYMPC_OK;
+}
+
+int tinympc_get_plant_state_batch(tinympc_solver *s, double *x_out) {
+    int rc = noise_refusals(s, "get_plant_state_batch", false);
+    if (rc) return rc;
+    if (!x_out) return fail(TINYMPC_ERR_INVALID_INPUT, "get_plant_state_batch: x_out is NULL");
+    if ((rc = bind_device(s))) return rc;
+    return download(s, x_out, s->noise && s->rn_v_on ? s->rn_px : s->dx0, sizeof(double) * s->nx * s->batch);
 }
 
 #ifdef TINY_CLOCK_STAMP

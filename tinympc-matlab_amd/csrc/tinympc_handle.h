@@ -328,6 +328,17 @@ struct tinympc_solver {
     bool metrics = false;
     double *rm_rows = nullptr, *rm_w = nullptr;
     double rm_tol = 0.0;
+    // Rollout noise (tinympc_set_rollout_noise): while on, every plant step runs a noisy variant of k_plant_step (PlantNoiseParams,
+    // tinympc_rollout.h) with the tick rn_tick, which then moves on by one. rn_sw / rn_sv: the scales, nx values or [batch][nx]
+    // (rn_stride 0 / nx), each allocated for the whole batch by the first call that needs it; rn_w_on / rn_v_on: which family is on.
+    // rn_px [batch][nx]: the TRUE state while measurement noise is on (rn_v_on) -- x0 then holds the measurement the next solve reads.
+    // Every verb that writes x0 from outside writes the same range of rn_px behind it (mirror_x0_into_px, tinympc_capi.hip).
+    bool noise = false, rn_w_on = false, rn_v_on = false;
+    double *rn_sw = nullptr, *rn_sv = nullptr, *rn_px = nullptr;
+    size_t rn_stride = 0;
+    unsigned long long rn_seed = 0, rn_first = 0, rn_tick = 0;
+    double *rn_out = nullptr;     // tinympc_get_rollout_noise stages w | v here (grown on demand, capacity in elements)
+    size_t rn_out_cap = 0;
     size_t lds_bytes_a = 0;       // layout-A LDS plan (layout B, where it runs, replaces lds_bytes; the families and adaptive rho always use layout A)
     bool tables_in_lds_a = false;
 

@@ -51,10 +51,33 @@ struct PlantMetricsParams {
     size_t xb_stride, ub_stride;
 };
 
+// The rollout noise (tinympc_set_rollout_noise): the noisy variants of the step draw it on the device (rollout_normal,
+// tinympc_rollout_noise.h -- the draw n(g, tick, r, stream) is defined there). With x the TRUE state and acc the chain of the plain step
+// (f_p, A_p's columns, B_p's columns; + w[b][:, t] where there is a disturbance):
+//   x     = px ? px[b] : x0[b]                               x_log[b][:, t] = x; the scored block scores this x
+//   acc   = acc + (sw_r * n(g, tick, r, 0))   where sw       the product rounded, then the add
+//   x+    = acc  ->  px ? px[b] : x0[b]                      (and x_log[b][:, ticks] on the last tick)
+//   x0[b][r] = x+ + (sv_r * n(g, tick, r, 1)) where sv       the measurement the NEXT solve reads
+// g = first_instance + b. A scale vector is a pointer and an instance stride in doubles (0: one vector shared by the batch, nx: one per
+// instance); NULL: that family is off and nothing is drawn for it. px ([batch][nx]) is set exactly while sv is.
+struct PlantNoiseParams {
+    unsigned key0, key1;               // seed & 0xffffffff, seed >> 32
+    unsigned tick;                     // the handle's noise tick of this step
+    unsigned long long first_instance;
+    const double *sw, *sv;
+    size_t sw_stride, sv_stride;
+    double *px;
+};
+
 // W, KT: the handle's lanes per instance and padded operand length (choose_geometry); W > 64 (layout M's systems): the workgroup form.
 hipError_t launch_plant_step(const PlantStepParams &p, int W, int KT, hipStream_t stream);
 // ... and its scored variant: the same step (the same bits in x0 and the logs), and every instance's metrics row moves on
 hipError_t launch_plant_step_scored(const PlantStepParams &p, const PlantMetricsParams &q, int W, int KT, hipStream_t stream);
+// ... and the noisy variants of both (q NULL: not scored)
+hipError_t launch_plant_step_noisy(const PlantStepParams &p, const PlantMetricsParams *q, const PlantNoiseParams &n, int W, int KT, hipStream_t stream);
+// What the noisy steps of ticks n.tick .. n.tick + ticks - 1 add, regenerated: w_out = sw_r * n(g, tick, r, 0), v_out = sv_r * n(g, tick, r, 1),
+// each nx x ticks x batch in the disturbance's layout (either may be NULL; a family that is off yields zeros)
+hipError_t launch_rollout_noise(const PlantNoiseParams &n, int nx, int batch, int ticks, double *w_out, double *v_out, hipStream_t stream);
 // *flag = 1 where v holds a value that is not finite (device input of tinympc_set_plant_batch_device)
 hipError_t launch_check_finite(const double *v, size_t n, int *flag, hipStream_t stream);
 

@@ -27,13 +27,23 @@
 // order: max is exact). Lanes 0..7 of the instance then read, update and store one slot each: one 64-byte line per instance. The
 // workgroup form leaves the terms in LDS behind the barrier the plant has anyway; thread 0 runs the same sum and the maxima.
 // No atomics, no scratch; x0 and the logs get the bits of the plain kernel.
+//
+// Noisy variants (k_plant_step_noisy<W, KT>, k_plant_step_wg_noisy and the scored-and-noisy pair; PlantNoiseParams in tinympc_rollout.h):
+// the same text compiled with PLANT_NOISY. The step reads the TRUE state (px while measurement noise is on, else x0), adds the row's
+// process noise behind the chain and the disturbance -- (acc + w) + (sw_r n), the product rounded first --, stores the true state where
+// it read it, and where measurement noise is on writes x+ + (sv_r n) into x0: the measurement the next solve reads. The draw
+// (rollout_normal, tinympc_rollout_noise.h) is a pure function of (seed, global instance, tick, row, stream): lane r of the wavefront
+// form and row r of the workgroup form hand it the same counter. Lanes that are no state row draw nothing, a family that is off draws
+// nothing. k_rollout_noise regenerates the terms of a range of ticks through the same function (tinympc_get_rollout_noise).
 #include "tinympc_rollout.h"
+#include "tinympc_rollout_noise.h"
 #include "tinympc_sweep.h"
 
 namespace tinympc {
 
 constexpr int PLANT_WG_ROWS = 512;  // nx+nu of the largest system a handle takes (tinympc_setup_batch)
 
+#define PLANT_NOISY 0
 #define PLANT_SCORED 0
 #include "tinympc_rollout_body.h"  // k_plant_step<W, KT>, k_plant_step_wg
 #undef PLANT_SCORED
@@ -91,6 +101,72 @@ hipError_t launch_plant_step_scored(const PlantStepParams &p, const PlantMetrics
     if (W == 32 && KT == 32) return launch_plant_step_scored_w<32, 32>(p, q, stream);
     if (W == 64 && KT == 64) return launch_plant_step_scored_w<64, 64>(p, q, stream);
     return hipErrorInvalidValue;
+}
+
+#undef PLANT_NOISY
+#define PLANT_NOISY 1
+#define PLANT_SCORED 0
+#include "tinympc_rollout_body.h"  // k_plant_step_noisy<W, KT>, k_plant_step_wg_noisy
+#undef PLANT_SCORED
+#define PLANT_SCORED 1
+#include "tinympc_rollout_body.h"  // k_plant_step_scored_noisy<W, KT>, k_plant_step_wg_scored_noisy
+#undef PLANT_SCORED
+#undef PLANT_NOISY
+
+template <int W, int KT>
+static hipError_t launch_plant_step_noisy_w(const PlantStepParams &p, const PlantMetricsParams *q, const PlantNoiseParams &n, hipStream_t stream) {
+    const size_t blocks = ((size_t)p.batch * W + 255) / 256;
+    if (q) hipLaunchKernelGGL((k_plant_step_scored_noisy<W, KT>), dim3((unsigned)blocks), dim3(256), 0, stream, p, *q, n);
+    else hipLaunchKernelGGL((k_plant_step_noisy<W, KT>), dim3((unsigned)blocks), dim3(256), 0, stream, p, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_plant_step_noisy(const PlantStepParams &p, const PlantMetricsParams *q, const PlantNoiseParams &n, int W, int KT, hipStream_t stream) {
+    if (p.batch < 1 || p.nx < 1 || p.nu < 1 || p.ticks < 1 || p.t < 0 || p.t >= p.ticks || !p.A || !p.B || !p.f || !p.x0 || !p.sol_u || !p.istats)
+        return hipErrorInvalidValue;
+    if (q && (!q->rows || !q->qx || !q->ru || !q->xr || !q->ur || q->xr_T < 0 || q->ur_T < 0 || ((q->xr_T > 0 || q->ur_T > 0) && !q->steps) ||
+              (q->xlo && !q->xhi) || (q->ulo && !q->uhi)))
+        return hipErrorInvalidValue;
+    // (the true state lives beside x0 exactly while there is measurement noise; a global index is 32 bits of the counter)
+    if ((!n.sw && !n.sv) || (n.sv != nullptr) != (n.px != nullptr) || n.first_instance + (unsigned long long)p.batch > (1ull << 32))
+        return hipErrorInvalidValue;
+    if (W > 64) {
+        if (p.nx + p.nu > PLANT_WG_ROWS) return hipErrorInvalidValue;
+        if (q) hipLaunchKernelGGL(k_plant_step_wg_scored_noisy, dim3((unsigned)p.batch), dim3(256), 0, stream, p, *q, n);
+        else hipLaunchKernelGGL(k_plant_step_wg_noisy, dim3((unsigned)p.batch), dim3(256), 0, stream, p, n);
+        return hipGetLastError();
+    }
+    if (p.nx + p.nu > KT) return hipErrorInvalidValue;
+    if (W == 16 && KT == 8) return launch_plant_step_noisy_w<16, 8>(p, q, n, stream);
+    if (W == 16 && KT == 12) return launch_plant_step_noisy_w<16, 12>(p, q, n, stream);
+    if (W == 16 && KT == 16) return launch_plant_step_noisy_w<16, 16>(p, q, n, stream);
+    if (W == 32 && KT == 32) return launch_plant_step_noisy_w<32, 32>(p, q, n, stream);
+    if (W == 64 && KT == 64) return launch_plant_step_noisy_w<64, 64>(p, q, n, stream);
+    return hipErrorInvalidValue;
+}
+
+// One thread per (instance, tick, row) of the disturbance's layout: the terms the noisy steps of these ticks add, by the steps' own draw.
+__global__ void __launch_bounds__(256) k_rollout_noise(const PlantNoiseParams n, int nx, int batch, int ticks, double *w_out, double *v_out) {
+#pragma clang fp contract(off)
+    const size_t total = (size_t)batch * ticks * nx;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        const unsigned r = (unsigned)(i % nx);
+        const size_t bt = i / nx;
+        const size_t b = bt / ticks;
+        const unsigned tick = n.tick + (unsigned)(bt % ticks);
+        const unsigned g = (unsigned)(n.first_instance + (unsigned long long)b);
+        if (w_out) w_out[i] = n.sw ? n.sw[b * n.sw_stride + r] * rollout_normal(n.key0, n.key1, g, tick, r, 0u) : 0.0;
+        if (v_out) v_out[i] = n.sv ? n.sv[b * n.sv_stride + r] * rollout_normal(n.key0, n.key1, g, tick, r, 1u) : 0.0;
+    }
+}
+hipError_t launch_rollout_noise(const PlantNoiseParams &n, int nx, int batch, int ticks, double *w_out, double *v_out, hipStream_t stream) {
+    if (nx < 1 || batch < 1 || ticks < 1 || n.first_instance + (unsigned long long)batch > (1ull << 32) ||
+        (unsigned long long)n.tick + (unsigned long long)ticks > (1ull << 32))
+        return hipErrorInvalidValue;
+    if (!w_out && !v_out) return hipSuccess;
+    const size_t blocks = ((size_t)batch * ticks * nx + 255) / 256;
+    hipLaunchKernelGGL(k_rollout_noise, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, stream, n, nx, batch, ticks, w_out, v_out);
+    return hipGetLastError();
 }
 
 __global__ void __launch_bounds__(256) k_check_finite(const double *v, size_t n, int *flag) {

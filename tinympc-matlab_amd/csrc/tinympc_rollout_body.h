@@ -1,9 +1,19 @@
 // tinympc_rollout_body.h -- the two forms of k_plant_step, included by tinympc_rollout.hip once per variant (no include guard):
 //   PLANT_SCORED 0   k_plant_step<W, KT>, k_plant_step_wg                     (const PlantStepParams p)
 //   PLANT_SCORED 1   k_plant_step_scored<W, KT>, k_plant_step_wg_scored       (const PlantStepParams p, const PlantMetricsParams q)
-// One text for both: the plain kernels are what the preprocessor leaves without the scored blocks, token for token what they were before
-// the variant existed (a shared template body with a compile-time flag renamed scalar registers in the plain kernels; this does not).
-#if PLANT_SCORED
+// and, with PLANT_NOISY 1 beside either (the rollout noise: PlantNoiseParams n, tinympc_rollout.h; the draw: tinympc_rollout_noise.h),
+//   PLANT_SCORED 0   k_plant_step_noisy<W, KT>, k_plant_step_wg_noisy                  (p, n)
+//   PLANT_SCORED 1   k_plant_step_scored_noisy<W, KT>, k_plant_step_wg_scored_noisy    (p, q, n)
+// One text for all: the plain kernels are what the preprocessor leaves without the scored and the noisy blocks, token for token what they
+// were before the variants existed (a shared template body with a compile-time flag renamed scalar registers in the plain kernels; this
+// does not). Where a noisy block REPLACES a line, the line stands unchanged behind its #else.
+#if PLANT_SCORED && PLANT_NOISY
+#define PLANT_KERNEL(name) name##_scored_noisy
+#define PLANT_KERNEL_ARGS const PlantStepParams p, const PlantMetricsParams q, const PlantNoiseParams n
+#elif PLANT_NOISY
+#define PLANT_KERNEL(name) name##_noisy
+#define PLANT_KERNEL_ARGS const PlantStepParams p, const PlantNoiseParams n
+#elif PLANT_SCORED
 #define PLANT_KERNEL(name) name##_scored
 #define PLANT_KERNEL_ARGS const PlantStepParams p, const PlantMetricsParams q
 #else
@@ -35,8 +45,17 @@ __global__ void __launch_bounds__(256) PLANT_KERNEL(k_plant_step)(PLANT_KERNEL_A
             m[k] = (in && xrow) ? v : 0.0;
         }
     }
+#if PLANT_NOISY
+    double sw = 0.0, sv = 0.0;  // the row's noise scales (a family that is off, and a lane that is no state row: nothing drawn)
+#endif
     if (xrow) {
+#if PLANT_NOISY
+        z = (n.px ? n.px : p.x0)[(size_t)b * nx + r];  // the true state
+        if (n.sw) sw = n.sw[(size_t)b * n.sw_stride + r];
+        if (n.sv) sv = n.sv[(size_t)b * n.sv_stride + r];
+#else
         z = p.x0[(size_t)b * nx + r];
+#endif
         c = p.f[(size_t)b * p.f_stride + r];
         if (p.w) wd = p.w[((size_t)b * p.ticks + p.t) * nx + r];
         if (p.x_log) p.x_log[((size_t)b * (p.ticks + 1) + p.t) * nx + r] = z;
@@ -51,10 +70,21 @@ __global__ void __launch_bounds__(256) PLANT_KERNEL(k_plant_step)(PLANT_KERNEL_A
     // (every lane of the wavefront runs the chain: the DPP reads reach into lanes that store nothing)
     double acc = group_matvec<W, KT>(m, z, c);
     if (p.w) acc += wd;
+#if PLANT_NOISY
+    if (xrow) {
+#pragma clang fp contract(off)
+        const unsigned g = (unsigned)(n.first_instance + (unsigned long long)b);
+        if (n.sw) acc = acc + sw * rollout_normal(n.key0, n.key1, g, n.tick, (unsigned)r, 0u);
+        (n.px ? n.px : p.x0)[(size_t)b * nx + r] = acc;
+        if (p.t == p.ticks - 1 && p.x_log) p.x_log[((size_t)b * (p.ticks + 1) + p.ticks) * nx + r] = acc;
+        if (n.sv) p.x0[(size_t)b * nx + r] = acc + sv * rollout_normal(n.key0, n.key1, g, n.tick, (unsigned)r, 1u);  // what the next solve reads
+    }
+#else
     if (xrow) {
         p.x0[(size_t)b * nx + r] = acc;
         if (p.t == p.ticks - 1 && p.x_log) p.x_log[((size_t)b * (p.ticks + 1) + p.ticks) * nx + r] = acc;
     }
+#endif
 #if PLANT_SCORED
     {
 #pragma clang fp contract(off)
@@ -112,7 +142,11 @@ __global__ void __launch_bounds__(256) PLANT_KERNEL(k_plant_step_wg)(PLANT_KERNE
     const size_t b = blockIdx.x;
     for (int i = threadIdx.x; i < nxu; i += 256) {
         if (i < nx) {
+#if PLANT_NOISY
+            const double v = (n.px ? n.px : p.x0)[b * nx + i];  // the true state
+#else
             const double v = p.x0[b * nx + i];
+#endif
             zs[i] = v;
             if (p.x_log) p.x_log[(b * (p.ticks + 1) + p.t) * nx + i] = v;
 #if PLANT_SCORED
@@ -154,8 +188,19 @@ __global__ void __launch_bounds__(256) PLANT_KERNEL(k_plant_step_wg)(PLANT_KERNE
         for (int k = 0; k < nx; ++k) acc = fma(Ar[(size_t)k * nx], zs[k], acc);
         for (int k = 0; k < nu; ++k) acc = fma(Br[(size_t)k * nx], zs[nx + k], acc);
         if (p.w) acc += p.w[(b * p.ticks + p.t) * nx + r];
+#if PLANT_NOISY
+        {
+#pragma clang fp contract(off)
+            const unsigned g = (unsigned)(n.first_instance + (unsigned long long)b);
+            if (n.sw) acc = acc + n.sw[b * n.sw_stride + r] * rollout_normal(n.key0, n.key1, g, n.tick, (unsigned)r, 0u);
+            (n.px ? n.px : p.x0)[b * nx + r] = acc;
+            if (p.t == p.ticks - 1 && p.x_log) p.x_log[(b * (p.ticks + 1) + p.ticks) * nx + r] = acc;
+            if (n.sv) p.x0[b * nx + r] = acc + n.sv[b * n.sv_stride + r] * rollout_normal(n.key0, n.key1, g, n.tick, (unsigned)r, 1u);
+        }
+#else
         p.x0[b * nx + r] = acc;
         if (p.t == p.ticks - 1 && p.x_log) p.x_log[(b * (p.ticks + 1) + p.ticks) * nx + r] = acc;
+#endif
     }
 #if PLANT_SCORED
     if (threadIdx.x == 0) {  // the terms are behind the barrier above: the same chain, rows ascending, and the maxima

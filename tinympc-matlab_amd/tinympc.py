@@ -818,6 +818,65 @@ class TinyMPC:
         _lib.check(self._L.tinympc_get_rollout_metrics(self._h, _p(rows)))
         return {k: (rows[:, i].copy() if k in self._METRICS_FLOAT else rows[:, i].astype(np.int64)) for i, k in enumerate(self._METRICS)}
 
+    # ------------------------------------------------------------------ rollout noise
+    def set_rollout_noise(self, process=None, measurement=None, seed: int = 0, first_instance: int = 0):
+        """Turn the rollout noise on (or replace it) and set its tick to 0: from now on every plant step of rollout() and plant_step()
+        draws seeded normal noise on the device (include/tinympc_hip.h, tinympc_set_rollout_noise). process / measurement: standard
+        deviations per state row, (nx,) shared by the batch or (nx, batch) one column per instance (both given: the same form); None:
+        that family is off. Process noise is added to the state the plant carries on; measurement noise only to the state the next
+        solve reads (x_log, plant_state() and the metrics keep the true state). seed: 64 bits. first_instance: the global index of this
+        solver's instance 0 -- a shard of a fleet draws what the same instances draw unsharded."""
+        self._check_setup()
+        E = _lib.ERR_INVALID_INPUT
+        if process is None and measurement is None:
+            raise TinyMPCError(E, "rollout noise: process or measurement is required")
+        arrays, forms = [], set()
+        for name, v in (("process", process), ("measurement", measurement)):
+            if v is None:
+                arrays.append(None)
+                continue
+            a = np.asarray(v, dtype=np.float64)
+            if a.shape != (self.nx,) and a.shape != (self.nx, self.batch):
+                raise TinyMPCError(E, "rollout noise: %s must have shape (%d,) or (%d, %d), got %s" % (name, self.nx, self.nx, self.batch, a.shape))
+            forms.add(a.ndim)
+            arrays.append(_f(a) if a.ndim == 2 else np.ascontiguousarray(a))
+        if len(forms) != 1:
+            raise TinyMPCError(E, "rollout noise: process and measurement must both be (nx,) or both (nx, batch)")
+        for name, v in (("seed", seed), ("first_instance", first_instance)):
+            if np.ndim(v) != 0 or int(v) != v or not 0 <= int(v) < 2 ** 64:
+                raise TinyMPCError(E, "rollout noise: %s must be an integer in [0, 2^64), got %r" % (name, v))
+        noise = _lib.RolloutNoise(*[_p(a) if a is not None else None for a in arrays], 1 if forms == {2} else 0, int(seed), int(first_instance))
+        _lib.check(self._L.tinympc_set_rollout_noise(self._h, C.byref(noise)))
+
+    def clear_rollout_noise(self):
+        """Turn the rollout noise off: plant steps run the plain (or scored) kernel again, from the true state."""
+        self._check_setup()
+        _lib.check(self._L.tinympc_clear_rollout_noise(self._h))
+
+    def rollout_noise(self, first_tick: int, ticks: int) -> dict:
+        """What the plant steps of noise ticks first_tick .. first_tick + ticks - 1 add, regenerated on the device by the steps' own
+        draw: {"w": process terms, "v": measurement terms}, each (nx, ticks, batch) as a rollout's disturbance (zeros for a family
+        that is off). A noise-free solver given "w" as its disturbance reproduces a process-noise rollout bit for bit."""
+        self._check_setup()
+        E = _lib.ERR_INVALID_INPUT
+        for name, v, lo in (("first_tick", first_tick, 0), ("ticks", ticks, 1)):
+            if np.ndim(v) != 0 or int(v) != v or int(v) < lo:
+                raise TinyMPCError(E, "rollout_noise: %s must be an integer >= %d, got %r" % (name, lo, v))
+        if int(first_tick) + int(ticks) > 2 ** 32:
+            raise TinyMPCError(E, "rollout_noise: ticks [%d, %d) reach 2^32" % (int(first_tick), int(first_tick) + int(ticks)))
+        w = np.zeros((self.nx, int(ticks), self.batch), order="F")
+        v = np.zeros((self.nx, int(ticks), self.batch), order="F")
+        _lib.check(self._L.tinympc_get_rollout_noise(self._h, int(first_tick), int(ticks), _p(w), _p(v)))
+        return {"w": w, "v": v}
+
+    def plant_state(self) -> np.ndarray:
+        """The true state of every instance, (nx, batch): what the plant carries on while measurement noise is on, else x0. Waits for
+        the solver's stream."""
+        self._check_setup()
+        x = np.zeros((self.nx, self.batch), order="F")
+        _lib.check(self._L.tinympc_get_plant_state_batch(self._h, _p(x)))
+        return x
+
     def _set_batch(self, what, arrays, rows, full, f_host, f_device, first, *extra):
         """The per-instance verbs: numpy arrays of shape (rows, count) / (rows, cols, count), or contiguous float64 CUDA tensors with the
         same memory layout, (count, rows) / (count, cols, rows) -- one column held over the horizon, or cols = full. All arrays in the

@@ -25,7 +25,16 @@ rollout but not the metrics; same workload, same protocol. The legs:
       only way to score a rollout there); both parts are timed, the line shows their sum and the numpy part
   c0  the parent's library: one rollout call without logs -- the queue alone, nothing scored
   d   this tree's library: set_rollout_metrics, one rollout call without logs, rollout_metrics() (64 bytes per instance)
-The claim: d below c and below b in every round at all three sizes (the exit status says so), and how far d sits above c0."""
+The claim: d below c and below b in every round at all three sizes (the exit status says so), and how far d sits above c0.
+
+--noise: what a Monte-Carlo realisation costs (the rollout noise, tinympc_set_rollout_noise). The parent is then the commit that has the
+metrics but not the noise; same workload, same protocol, every leg a scored rollout without logs followed by rollout_metrics(). The legs:
+  p   the parent's library: the process noise drawn in numpy (standard_normal, nx x ticks x batch, 157 MB at 8,192 x 200) and handed to
+      the rollout as its disturbance; both parts are timed, the line shows their sum and the drawing
+  c0  the parent's library: no disturbance at all -- the queue alone
+  n   this tree's library: process noise drawn on the device
+  nm  this tree's library: process and measurement noise drawn on the device
+The claim: n below p in every round at 4,096 and 8,192 (the exit status says so); how far n and nm sit above c0, and the 256 row."""
 import argparse
 import json
 import os
@@ -206,6 +215,103 @@ def sweep_metrics(a):
         raise SystemExit(1)
 
 
+def run_noise_leg(pkg, leg, batch, ticks):
+    """-> (wall us per tick, the drawing's part of it (leg p), the mean cost, kernel line)"""
+    P = pkg.problems
+    prob = P.quadrotor(50)
+    s = pkg.TinyMPC()
+    s.setup(prob.A, prob.B, prob.Q, prob.R, prob.N, batch=batch, rho=prob.rho, max_iter=100, abs_pri_tol=1e-3, abs_dua_tol=1e-3)
+    s.set_bound_constraints(prob.x_min, prob.x_max, prob.u_min, prob.u_max)
+    x0 = np.asfortranarray(P.quadrotor_batch_x0(batch))
+    s.set_rollout_metrics(settle_tol=0.05)
+    sw, sv = np.full(prob.nx, 1e-3), np.full(prob.nx, 1e-2)
+    rng = np.random.default_rng(1)
+
+    def loop(n):
+        """-> (seconds, seconds of drawing, mean cost)"""
+        t0 = t1 = time.perf_counter()
+        w = None
+        if leg == "p":
+            w = rng.standard_normal((batch, n, prob.nx)).T  # (nx, n, batch) in the disturbance's memory order, no copy
+            w *= 1e-3
+            t1 = time.perf_counter()
+        s.rollout(n, disturbance=w, log=())
+        m = s.rollout_metrics()
+        return time.perf_counter() - t0, t1 - t0, float(m["cost"].mean())
+
+    def restart():
+        s.reset_workspace()
+        s.set_x0_batch(x0)
+        s.reset_rollout_metrics()
+        if leg in ("n", "nm"):
+            s.set_rollout_noise(process=sw, measurement=sv if leg == "nm" else None, seed=1)  # (the tick starts again at 0)
+
+    restart()
+    loop(ticks)
+    restart()
+    loop(WARMUP)
+    restart()
+    dt, dt_draw, cost = loop(ticks)
+    info = "%s %s" % (s.launch_info()["layout"], s.jit_info())
+    s.reset()
+    return 1e6 * dt / ticks, 1e6 * dt_draw / ticks, cost, info
+
+
+def child_noise(pkg, a):
+    has = hasattr(pkg.load_library(), "tinympc_set_rollout_noise")
+    out = dict(library="this" if has else "parent", tick_us={}, draw_us={}, cost={}, kernel={})
+    for leg in (("n", "nm") if has else ("p", "c0")):
+        us, us_draw, cost, info = run_noise_leg(pkg, leg, a.batch, a.ticks)
+        out["tick_us"][leg], out["draw_us"][leg], out["cost"][leg], out["kernel"][leg] = us, us_draw, cost, info
+    print("ROLLOUT-CHILD " + json.dumps(out), flush=True)
+
+
+def sweep_noise(a):
+    if not a.parent_lib or not os.path.exists(a.parent_lib):
+        raise SystemExit("needs --parent-lib: libtinympc_hip.so built from the parent commit")
+    ok = True
+    for batch in [int(b) for b in a.batches.split(",")]:
+        rows = {"this": [], "parent": []}
+        for rnd in range(a.rounds):
+            for lib in ("this", "parent") if rnd % 2 == 0 else ("parent", "this"):
+                env = dict(os.environ)
+                env.pop("TINYMPC_HIP_LIBRARY", None)
+                if lib == "parent":
+                    env["TINYMPC_HIP_LIBRARY"] = os.path.abspath(a.parent_lib)
+                cmd = [sys.executable, os.path.abspath(__file__), "--child", "--noise", "--batch", str(batch), "--ticks", str(a.ticks)]
+                r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)
+                line = [l for l in r.stdout.splitlines() if l.startswith("ROLLOUT-CHILD ")]
+                if r.returncode != 0 or not line:
+                    raise SystemExit("batch %d round %d (%s) failed with %d:\n%s\n%s" % (batch, rnd, lib, r.returncode, r.stdout[-2000:], r.stderr[-2000:]))
+                rec = json.loads(line[0][len("ROLLOUT-CHILD "):])
+                assert rec["library"] == lib, rec
+                rows[lib].append(rec)
+                print("# batch %d round %d %-6s %s" % (batch, rnd, lib, json.dumps(rec["tick_us"])), flush=True)
+        print("noisy scored closed-loop rollout, %d quadrotors N=50, tolerances 1e-3, max_iter 100, %d warm-started ticks, no logs, wall us per tick "
+              "(%d rounds, a fresh process each, the two libraries alternating)" % (batch, a.ticks, a.rounds))
+        print("%-66s | %-36s | %-9s | %-19s" % ("leg", "rounds", "median", "spread"))
+        med = {}
+        for leg, lib, name in (("p", "parent", "p  disturbance drawn in numpy and uploaded (parent)"), ("c0", "parent", "c0 no disturbance at all (parent)"),
+                               ("n", "this", "n  process noise drawn on the device"), ("nm", "this", "nm process and measurement noise drawn on the device")):
+            v = [r["tick_us"][leg] for r in rows[lib]]
+            med[leg] = float(np.median(v))
+            print("%-66s | %-36s | %9.1f | %8.1f - %8.1f" % (name, " ".join("%.1f" % x for x in v), med[leg], min(v), max(v)))
+        draw = float(np.median([r["draw_us"]["p"] for r in rows["parent"]]))
+        print("leg p's drawing per tick (median of the rounds): %.1f us, p without it %.1f us; mean cost p %.9g, c0 %.9g, n %.9g, nm %.9g" %
+              (draw, med["p"] - draw, rows["parent"][0]["cost"]["p"], rows["parent"][0]["cost"]["c0"], rows["this"][0]["cost"]["n"], rows["this"][0]["cost"]["nm"]))
+        print("kernel: %s" % rows["this"][0]["kernel"]["n"])
+        below = all(rn["tick_us"]["n"] < rp["tick_us"]["p"] for rn, rp in zip(rows["this"], rows["parent"]))
+        below_bare = all(rn["tick_us"]["n"] < rp["tick_us"]["p"] - rp["draw_us"]["p"] for rn, rp in zip(rows["this"], rows["parent"]))
+        print("batch %d: n against p %.2fx (against p without the drawing %.2fx), n above c0 by %.1f us per tick (%.1f %%), nm above c0 by %.1f us "
+              "(%.1f %%); n below p in every round: %s; below p without the drawing in every round: %s\n"
+              % (batch, med["p"] / med["n"], (med["p"] - draw) / med["n"], med["n"] - med["c0"], 100.0 * (med["n"] / med["c0"] - 1.0),
+                 med["nm"] - med["c0"], 100.0 * (med["nm"] / med["c0"] - 1.0), "yes" if below else "NO", "yes" if below_bare else "NO"))
+        if batch >= 4096 and not below:
+            ok = False
+    if not ok:
+        raise SystemExit(1)
+
+
 def child(pkg, a):
     has = hasattr(pkg.load_library(), "tinympc_rollout_batch")
     out = dict(library="this" if has else "parent", tick_us={}, iters={}, kernel={}, gpu_us={})
@@ -269,11 +375,12 @@ def main():
     ap.add_argument("--parent-lib", default="")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--metrics", action="store_true", help="the scored rollout against the parent's legs (see above)")
+    ap.add_argument("--noise", action="store_true", help="noise drawn on the device against a disturbance drawn in numpy (see above)")
     a = ap.parse_args()
     if not a.child:
-        return sweep_metrics(a) if a.metrics else sweep(a)
+        return sweep_noise(a) if a.noise else sweep_metrics(a) if a.metrics else sweep(a)
     import __graft_entry__ as ge
-    (child_metrics if a.metrics else child)(ge.load_package(), a)
+    (child_noise if a.noise else child_metrics if a.metrics else child)(ge.load_package(), a)
 
 
 if __name__ == "__main__":
